@@ -2,6 +2,16 @@
 """Headline benchmark: MPC solves/sec of the MPPI / iLQR inner solve on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--workload c3|c2|c1|arx|c4|c5] [--precision f64|f32]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, pre-heats, warms up, times exactly K steps and prints the line (metric, value,
+unit, higher_is_better, dtype, ms_per_step = milliseconds of one timed step).  --full adds what takes
+instrumentation or runs of its own: the kernel-event roofline, the CPU baseline, repeated timed
+windows and, on the default line, the f32 / batched / other-configuration side records.
+--dump-outputs DIR writes what the last timed step returned (c3 / c2 / c1 / arx: u, act_seq, costs;
+c4: objective, converged, iters, status; c5: scores) as DIR/<name>.npy in float64.  The inputs are
+seeded and the solver state is reset after the time-bounded pre-heat, so the same arguments give
+the same inputs on every run.
 
 One "step" = one pass of the hot path over one batch of synthetic input:
   c3 (default, headline)  one complete MPPI solve of BASELINE.json config 3 (HalfCheetah-shaped MLP
@@ -58,14 +68,36 @@ def parse():
     ap.add_argument("--preheat", type=float, default=1.0,
                     help="seconds of untimed solves before the warm-up steps, so that short runs "
                          "(--steps 20) are timed at the settled clock like long ones")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the f32 fast-mode side report")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: kernel-event roofline, CPU baseline, repeated "
+                         "windows and the side records (f32, batched, other configurations).  Without it a run "
+                         "sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (f64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the side records")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
-                    help="time budget of EACH cpu_baseline leg (all cores, one thread)")
+                    help="--full: time budget of EACH cpu_baseline leg (all cores, one thread)")
     ap.add_argument("--repeats", type=int, default=7,
-                    help="default line: the timed window of --steps solves is repeated this many times "
+                    help="--full default line: the timed window of --steps solves is repeated this many times "
                          "(value = the first window, as the contract says; repeat_windows = median / min / max)")
     return ap.parse_args()
+
+
+DUMP_BYTES = 64 << 20                        # --dump-outputs: at most this much in all
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy in float64; an array above its share of
+    DUMP_BYTES is replaced by a fixed, seeded sample of its elements (flattened, in index order)."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.nbytes > share:
+            keep = np.sort(np.random.default_rng(0).choice(a.size, share // 8, replace=False))
+            a = a.reshape(-1)[keep]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -353,16 +385,19 @@ class Ranks:
             self.dist.destroy_process_group()
 
 
-def timed_loop(R, step, steps, warmup, preheat_s, before_timed=None):
+def timed_loop(R, step, steps, warmup, preheat_s, before_timed=None, after_preheat=None):
     """preheat_s seconds of untimed steps (clock settling), W untimed warm-up steps, then EXACTLY
     `steps` timed steps bracketed by barrier + synchronize; returns (elapsed max over ranks,
-    number of pre-heat steps)."""
+    number of pre-heat steps).  after_preheat: restores the starting state, so that what the
+    steps compute does not depend on how many pre-heat steps fitted into preheat_s."""
     n_pre, t0 = 0, time.perf_counter()
     while time.perf_counter() - t0 < preheat_s:
         step(-1 - n_pre)
         n_pre += 1
         if n_pre % 16 == 0:
             R.torch.cuda.synchronize()
+    if after_preheat is not None:
+        after_preheat()
     for i in range(warmup):
         step(i)
     if before_timed is not None:
@@ -390,9 +425,9 @@ def secondary_workload(args, R, emit=True):
     B = args.batch if args.batch > 0 else (64 if args.workload == "c5" else 1024)
     mlp_macs = sum(a * b for a, b in zip([nx + nu] + spec["hidden"], spec["hidden"] + [nx]))
     extra = {}
-    steps, warm = max(1, min(args.steps, 10)), max(1, min(args.warmup, 2))
+    steps, warm = max(1, args.steps), max(0, args.warmup)
     peak = PEAK_TFLOPS[args.precision]
-    roof = None
+    roof = kt = None
 
     if args.workload == "c4":
         # Headline c4 = the CONVERGING problem set (controls clipped to +-0.25: the reference's bounded
@@ -429,16 +464,18 @@ def secondary_workload(args, R, emit=True):
         metric, unit = "MPC solves/sec (iLQR, full compute_ilqr_default per solve)", "solves/s"
         elapsed, n_pre = timed_loop(R, step, steps, warm, min(args.preheat, 0.3))
         ob = last["out"]
-        # per-kernel times: ONE more step of the same problems with HIP events around the launches of every iteration
-        # (their work differs: all of them are bracketed) -- five event records per iteration cost 1-2 % of the step,
-        # so they stay out of the timed region; the kernel durations are the same
-        plan.set_timing(True)
-        plan.solve_queue(x0[:P], max_iter=50, gains=False, trajectories=False)
-        kt = plan.timing()
-        plan.set_timing(False)
+        outputs = {k: v for k, v in ob.items() if isinstance(v, np.ndarray)}
+        if args.full:
+            # per-kernel times: ONE more step of the same problems with HIP events around the launches of every
+            # iteration (their work differs: all of them are bracketed) -- five event records per iteration cost
+            # 1-2 % of the step, so they stay out of the timed region; the kernel durations are the same
+            plan.set_timing(True)
+            plan.solve_queue(x0[:P], max_iter=50, gains=False, trajectories=False)
+            kt = plan.timing()
+            plan.set_timing(False)
         kt_steps = 1
         sub = {}
-        if not args.no_extras:
+        if args.full and not args.no_extras:
             def once(fn):
                 fn()
                 R.sync_all()
@@ -611,10 +648,12 @@ def secondary_workload(args, R, emit=True):
 
         def step(i):
             scores = evaluate_sharded(
-                lambda shard, lo: ev.evaluate(shard, seed=max(i, 0), index_offset=lo, timing=last),
+                lambda shard, lo: ev.evaluate(shard, seed=max(i, 0), index_offset=lo,
+                                              timing=last if args.full else None),
                 cands, weights="auto")      # shards balanced by num_path x horizon (the gather is max-over-ranks bound)
             if not np.all(np.isfinite(scores)) or scores.shape[0] != B * world:
                 raise RuntimeError("candidate scores incomplete")
+            last["scores"] = scores
         label = ("c5: %d tuning candidates (MPPI horizon/sigma/lmda/num_path + QuadCost weights from "
                  "the reference's config ranges) x one eval_cfg episode (task.set_num_steps(200): 200 rows = "
                  "%d closed-loop control steps, pipeline_tuner.py:222-231) per step per GPU" % (B, n_ctl))
@@ -622,6 +661,7 @@ def secondary_workload(args, R, emit=True):
         extra["control_steps_per_episode"] = n_ctl
         metric, unit = "MPC solves/sec (MPPI inside the batched closed-loop candidate evaluator)", "solves/s"
         elapsed, n_pre = timed_loop(R, step, steps, warm, 0.0)
+        outputs = {"scores": last["scores"]}
         kt = last.get("timing")
         if rank == 0:
             from autompc_amd.tuning import balanced_shards, candidate_work
@@ -650,7 +690,7 @@ def secondary_workload(args, R, emit=True):
                "config": {"workload": label, "parallelism": "independent problems per GPU (dp%d)" % world},
                "roofline": roof, **extra}
         trimmed = getattr(args, "trimmed_cpu_seconds", 0.0)     # (sub-record of the default line)
-        if (not args.no_cpu_baseline or trimmed > 0) and world == 1:
+        if ((args.full and not args.no_cpu_baseline) or trimmed > 0) and world == 1:
             only = ("one_thread",) if trimmed > 0 else None
             budget = trimmed if trimmed > 0 else args.cpu_seconds
             if args.workload == "c4":
@@ -659,6 +699,8 @@ def secondary_workload(args, R, emit=True):
                 out["cpu_baseline"] = cpu_baseline_c5(system, spec, cands, budget, n_ctl=4 if trimmed > 0 else 16, only=only)
             out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
         if emit:
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, outputs)
             print(json.dumps(out))
         return out
     return None
@@ -841,11 +883,11 @@ def main():
         plan = _lib.MppiPlan(h, [N] * nb, [H] * nb, [1.0] * nb, [1.0] * nb)
         return h, plan, task, spec
 
-    def timed_run(precision, steps, warmup, preheat_s, workload=None, windows=1, nb=None):
+    def timed_run(precision, steps, warmup, preheat_s, workload=None, windows=1, nb=None, outputs=False):
         """pre-heat + W untimed + K timed solves, bracketed by barrier + synchronize; max over ranks.
         windows > 1: the timed window is repeated (same plan, noise stream running on); the first
         window is the one returned as `elapsed`, all of them in `rates`.  nb: solves per launch (default:
-        --batch)."""
+        --batch).  outputs: spec["outputs"] = what the last solve of the first window returns."""
         batch = nb if nb else batch_default
         h, plan, task, spec = build_plan(precision, batch, workload)
         nx, nu, N, H = spec["nx"], spec["nu"], spec["num_path"], spec["horizon"]
@@ -864,12 +906,19 @@ def main():
             if args.noise == "device":
                 plan.generate_eps(rank, i & 0xffffffff)
             plan.solve()
-        # HIP events (on the launch stream) around the kernels of every EVENT_STRIDE-th timed solve: the three
-        # event records of a solve cost ~11 us on the stream (3.7 % of a c3 solve) -- instrumentation, not work
+        # --full: HIP events (on the launch stream) around the kernels of every EVENT_STRIDE-th timed solve: the
+        # three event records of a solve cost ~11 us on the stream (3.7 % of a c3 solve) -- instrumentation, not work
         elapsed, n_pre = timed_loop(R, step, steps, warmup, preheat_s,
-                                    before_timed=lambda: plan.set_timing(True, every=EVENT_STRIDE))
-        kt = plan.timing()
-        plan.set_timing(False)
+                                    before_timed=(lambda: plan.set_timing(True, every=EVENT_STRIDE)) if args.full else None,
+                                    after_preheat=lambda: plan.upload(x0, act0, eps0))
+        kt = None
+        if args.full:
+            kt = plan.timing()
+            plan.set_timing(False)
+        outs = None
+        if outputs:
+            a, u, c, _ = plan.download(act_seq=True, u=True, costs=True)
+            outs = {"u": u, "act_seq": a.reshape(batch, H, nu), "costs": c.reshape(batch, N)}
         rates = [world * steps * batch / elapsed]
         for wdw in range(1, windows):
             ew, _ = timed_loop(R, lambda i: step(i + wdw * steps), steps, 0, 0.0)
@@ -879,7 +928,7 @@ def main():
             raise RuntimeError("non-finite control returned by the solve")
         plan.close()
         h.close()
-        spec = dict(spec, window_rates=rates)
+        spec = dict(spec, window_rates=rates, outputs=outs)
         return elapsed, kt, info, spec, n_pre
 
     def mppi_record(workload, steps, warmup):
@@ -965,25 +1014,20 @@ def main():
         return {"cost_rel_err": rel(res["f32"][1], res["f64"][1]),
                 "act_sequence_rel_err": rel(res["f32"][0], res["f64"][0]), "tolerance": 1e-4}
 
-    default_line = world == 1 and args.workload == "c3" and args.precision == "f64" and not args.no_extras
+    default_line = args.full and world == 1 and args.workload == "c3" and args.precision == "f64" and not args.no_extras
     elapsed, kt, info, spec, n_pre = timed_run(args.precision, args.steps, args.warmup, args.preheat,
-                                               windows=max(1, args.repeats) if default_line else 1)
+                                               windows=max(1, args.repeats) if default_line else 1,
+                                               outputs=bool(args.dump_outputs))
     nx, nu, N, H, B = spec["nx"], spec["nu"], spec["num_path"], spec["horizon"], batch
     sharded = None
-    if world > 1 and args.workload == "c3" and not args.no_extras:
+    if args.full and world > 1 and args.workload == "c3" and not args.no_extras:
         sharded = c5_sharded_record(args, R)             # collective: every rank calls it
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, spec["outputs"])
     if rank == 0:
         solves = world * args.steps * B
         value = solves / elapsed
-        rollout_s = kt["rollout_ms"] * 1e-3
-        if "linear" in spec:          # algorithmic work of x' = A x + B u, not of its staging
-            info["flops"] = float(B * N * H * 2 * nx * (nx + nu))
-        if "sindy" in spec:           # library evaluation + Theta Xi' (VALU path: no MFMA roofline)
-            info["flops"] = float(B * N * H * 2 * nx * spec["sindy"]["n_feat"])
-        achieved = info["flops"] / rollout_s / 1e12 if rollout_s > 0 else 0.0
-        peak = PEAK_TFLOPS[args.precision]
-        traffic = measured_traffic(args, B, "mppi_rollout")
         out = {
             "metric": "MPC solves/sec (MPPI, n_samples x horizon rollouts + update per solve)",
             "value": value, "unit": "solves/s", "n_gpus": world, "steps": args.steps,
@@ -996,16 +1040,29 @@ def main():
                                    "noise=%s" % (args.workload, spec["label"], B, args.noise),
                        "n_samples": N, "horizon": H, "state_dim": nx, "ctrl_dim": nu,
                        "hidden": spec["hidden"], "parallelism": "independent solves per GPU (dp%d)" % world},
-            "roofline": {"bound": "mfma", "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
-                         "frac": achieved / peak, "traffic": traffic["bytes"] if traffic else None,
-                         "traffic_source": traffic["source"] if traffic else None,
-                         "kernel": "mppi_rollout4_kernel" if info["samples_per_wg"] == 4 else "mppi_rollout_kernel",
-                         "kernel_ms": kt["rollout_ms"],
-                         "update_kernel_ms": kt["update_ms"], "launches_timed": kt["count"], "event_stride": EVENT_STRIDE,
-                         "algorithmic_flops_per_launch": info["flops"],
-                         "algorithmic_bytes_per_launch": info["bytes"],
-                         "workgroups": info["workgroups"], "samples_per_workgroup": info["samples_per_wg"]},
+            "roofline": None,
         }
+        if not args.full:
+            print(json.dumps(out))
+            R.close()
+            return
+        rollout_s = kt["rollout_ms"] * 1e-3
+        if "linear" in spec:          # algorithmic work of x' = A x + B u, not of its staging
+            info["flops"] = float(B * N * H * 2 * nx * (nx + nu))
+        if "sindy" in spec:           # library evaluation + Theta Xi' (VALU path: no MFMA roofline)
+            info["flops"] = float(B * N * H * 2 * nx * spec["sindy"]["n_feat"])
+        achieved = info["flops"] / rollout_s / 1e12 if rollout_s > 0 else 0.0
+        peak = PEAK_TFLOPS[args.precision]
+        traffic = measured_traffic(args, B, "mppi_rollout")
+        out["roofline"] = {"bound": "mfma", "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
+                           "frac": achieved / peak, "traffic": traffic["bytes"] if traffic else None,
+                           "traffic_source": traffic["source"] if traffic else None,
+                           "kernel": "mppi_rollout4_kernel" if info["samples_per_wg"] == 4 else "mppi_rollout_kernel",
+                           "kernel_ms": kt["rollout_ms"],
+                           "update_kernel_ms": kt["update_ms"], "launches_timed": kt["count"], "event_stride": EVENT_STRIDE,
+                           "algorithmic_flops_per_launch": info["flops"],
+                           "algorithmic_bytes_per_launch": info["bytes"],
+                           "workgroups": info["workgroups"], "samples_per_workgroup": info["samples_per_wg"]}
         if len(spec["window_rates"]) > 1:
             wr = np.array(spec["window_rates"])
             out["repeat_windows"] = {"windows": len(wr), "steps_each": args.steps, "unit": "solves/s",

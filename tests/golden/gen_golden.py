@@ -1240,7 +1240,36 @@ def gen_mlpfit():
              pred=model.pred_batch(states, ctrls), torch_version=torch.__version__, **out)
 
 
-GENERATORS = {"mlpfit": gen_mlpfit, "ilqr_arx4": gen_ilqr_arx4, "evalcfg_twomodels": gen_evalcfg_twomodels, "mppi_indicator": gen_mppi_indicator, "linear_wide": gen_linear_wide, "sindy": gen_sindy, "linear": gen_linear, "mlp": gen_mlp, "cost": gen_cost, "mppi": gen_mppi, "ilqr": gen_ilqr,
+# --------------------------------------------------------------------------- configurations -> factories
+def gen_config_factories():
+    """What the reference's QuadCostFactory / MLPFactory build when called the way Pipeline.__call__ calls them
+    (pipeline.py:138-166) on the sub-configurations of six sampled pipeline configurations (tests/test_configs.py):
+    the configurations, the cost matrices and the hidden layer sizes, as JSON."""
+    import json
+    from autompc.costs import QuadCostFactory
+    from autompc.sysid.mlp import MLPFactory as RefMLPFactory
+    from autompc_amd import System
+    from autompc_amd.tuning import DictConfiguration, candidate_from_config, sample_pipeline_configs
+    from autompc_amd.tuning.configs import subspace
+    system = make_system(4, 2)
+    ours = System(["x%d" % i for i in range(4)], ["u%d" % i for i in range(2)], dt=0.05)
+    task = Task(system)
+    task.set_cost(QuadCost(system, np.eye(4), np.eye(2), goal=np.array([0.1, 0.0, -0.2, 0.0])))
+    recs = []
+    for cfg in sample_pipeline_configs(ours, 6, np.random.default_rng(5), model_axis=True):
+        cand = candidate_from_config(ours, cfg)
+        Q, R, F = QuadCostFactory(system)(subspace(cfg, "_cost"), task, []).get_cost_matrices()
+        model = quiet(RefMLPFactory(system, use_cuda=False), DictConfiguration(cand["model_cfg"]), [],
+                      skip_train_model=True)
+        recs.append({"config": dict(cfg), "Q": np.asarray(Q).tolist(), "R": np.asarray(R).tolist(),
+                     "F": np.asarray(F).tolist(), "hidden_sizes": [int(m.out_features) for m in model.net.layers.values()]})
+    path = os.path.join(HERE, "config_factories.json")
+    with open(path, "w") as f:
+        json.dump(recs, f, indent=1)
+    print("wrote %-40s %7.1f KB" % ("config_factories.json", os.path.getsize(path) / 1024))
+
+
+GENERATORS = {"config_factories": gen_config_factories, "mlpfit": gen_mlpfit, "ilqr_arx4": gen_ilqr_arx4, "evalcfg_twomodels": gen_evalcfg_twomodels, "mppi_indicator": gen_mppi_indicator, "linear_wide": gen_linear_wide, "sindy": gen_sindy, "linear": gen_linear, "mlp": gen_mlp, "cost": gen_cost, "mppi": gen_mppi, "ilqr": gen_ilqr,
               "closed_loop": gen_closed_loop, "evalcfg": gen_evalcfg, "cost_terms": gen_cost_terms, "sumcost": gen_sumcost, "linear_wide2": gen_linear_wide2, "evalcfg_koopman": gen_evalcfg_koopman}
 
 if __name__ == "__main__":

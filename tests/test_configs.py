@@ -2,8 +2,8 @@
 (``BatchPipelineTuner(model_factory=..., trajs=...)``: a model built and FITTED per configuration, as
 ``eval_cfg`` does through ``pipeline(cfg, task, trajs)``, pipeline.py:138-145).  CPU: host logic; the
 evaluator is a stand-in that reads the candidate's fitted model."""
+import json
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -139,32 +139,23 @@ def test_model_axis_fits_a_model_per_configuration_in_lockstep_groups_and_caches
         BatchPipelineTuner(system, ev).run(4, np.random.default_rng(0), configs=cfgs[:4])
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/autompc"), reason="needs the reference tree: build container only")
 def test_configurations_mean_to_the_references_factories_what_they_mean_here():
-    """The reference's REAL QuadCostFactory / MLPFactory (ConfigSpace stubbed as in gen_golden.py) called the way
-    Pipeline.__call__ calls them (pipeline.py:138-166) on the sub-configurations of sampled configurations:
-    the cost it builds has the candidate's Q / R / F, the model it builds has the candidate's layer sizes."""
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
-    import gen_golden as gg
-    from autompc.costs import QuadCost, QuadCostFactory
-    from autompc.sysid.mlp import MLPFactory as RefMLPFactory
-    from autompc.tasks import Task
-    from autompc_amd.tuning.configs import subspace
-    system = gg.make_system(4, 2)
-    task = Task(system)
-    task.set_cost(QuadCost(system, np.eye(4), np.eye(2), goal=np.array([0.1, 0.0, -0.2, 0.0])))
-    for cfg in sample_pipeline_configs(make_system(4, 2), 6, np.random.default_rng(5), model_axis=True):
+    """The reference's REAL QuadCostFactory / MLPFactory called the way Pipeline.__call__ calls them
+    (pipeline.py:138-166) on the sub-configurations of sampled configurations, as recorded in
+    tests/golden/config_factories.json (gen_golden.gen_config_factories): the cost it built has the candidate's
+    Q / R / F, the model it built has the candidate's layer sizes."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "config_factories.json")) as f:
+        recorded = json.load(f)
+    cfgs = sample_pipeline_configs(make_system(4, 2), 6, np.random.default_rng(5), model_axis=True)
+    assert len(recorded) == len(cfgs) == 6
+    for cfg, rec in zip(cfgs, recorded):
+        assert dict(cfg) == rec["config"]                   # the configurations the reference was given
         cand = candidate_from_config(make_system(4, 2), cfg)
-        cost = QuadCostFactory(system)(subspace(cfg, "_cost"), task, [])
-        Q, R, F = cost.get_cost_matrices()
-        np.testing.assert_array_equal(Q, np.diag(cand["Q"]))
-        np.testing.assert_array_equal(R, np.diag(cand["R"]))
-        np.testing.assert_array_equal(F, np.diag(cand["F"]))
-        model = gg.quiet(RefMLPFactory(system, use_cuda=False), DictConfiguration(cand["model_cfg"]), [],
-                         skip_train_model=True)
+        np.testing.assert_array_equal(np.array(rec["Q"]), np.diag(cand["Q"]))
+        np.testing.assert_array_equal(np.array(rec["R"]), np.diag(cand["R"]))
+        np.testing.assert_array_equal(np.array(rec["F"]), np.diag(cand["F"]))
         ours = MLPFactory(make_system(4, 2))(DictConfiguration(cand["model_cfg"]), [], skip_train_model=True)
-        ref_sizes = [m.out_features for m in model.net.layers.values()]
-        assert ref_sizes == ours.hidden_sizes
+        assert rec["hidden_sizes"] == ours.hidden_sizes
 
 
 def _axis_worker(rank, world, port, q):

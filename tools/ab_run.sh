@@ -2,7 +2,7 @@
 # Time the product library and every variants/lib_*.so named on the command line with the headline
 # bench (c3 f64, 200 steps) -- run on the GPU box:  bash tools/ab_run.sh [extra bench args --] name1 name2 ...
 cd "$GRAFT_REPO_ROOT"
-ARGS="--no-cpu-baseline --no-extras --steps 200 --warmup 20"
+ARGS="--full --no-cpu-baseline --no-extras --steps 200 --warmup 20"
 run() {
   python bench.py $ARGS $EXTRA 2>/dev/null | python -c "
 import json,sys

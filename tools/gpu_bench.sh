@@ -1,17 +1,18 @@
 #!/bin/bash
 # Quick perf loop on the GPU box: parity tests (fast) + bench variants.  Run via gpurun.
 set -u
-mkdir -p gpurun_out
+OUT=${OUT:-bench_out}              # where the logs and bench lines go
+mkdir -p "$OUT"
 export TMPDIR=/tmp
-timeout 900 python -m pytest tests -m gpu -x -q 2>&1 | tail -8 > gpurun_out/pytest_gpu.log
-cat gpurun_out/pytest_gpu.log
+timeout 900 python -m pytest tests -m gpu -x -q 2>&1 | tail -8 > "$OUT"/pytest_gpu.log
+cat "$OUT"/pytest_gpu.log
 run() { # name, args...
   local name=$1; shift
-  timeout 300 python bench.py --no-cpu-baseline "$@" > gpurun_out/$name.json 2> gpurun_out/$name.err || tail -3 gpurun_out/$name.err
+  timeout 300 python bench.py --full --no-cpu-baseline "$@" > "$OUT"/$name.json 2> "$OUT"/$name.err || tail -3 "$OUT"/$name.err
   python - <<PY
 import json
 try:
-    d=json.load(open("gpurun_out/$name.json")); r=d["roofline"]
+    d=json.load(open("$OUT/$name.json")); r=d["roofline"]
     print("%-14s value=%8.1f ms/step=%.3f kernel_ms=%.3f upd=%.3f TF=%.1f frac=%.3f wgs=%d spw=%d" % ("$name", d["value"], d["ms_per_step"], r["kernel_ms"], r["update_kernel_ms"], r["achieved"], r["frac"], r["workgroups"], r["samples_per_workgroup"]))
 except Exception as e:
     print("$name failed", e)

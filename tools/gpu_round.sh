@@ -8,7 +8,7 @@ mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
 timeout 1200 python -m pytest tests -m gpu -q -rs -p no:cacheprovider 2>&1 | tail -25 > $OUT/pytest_gpu.log      # (-rs: skip reasons in the log)
 timeout 300 python __graft_entry__.py --smoke > $OUT/smoke.log 2>&1
-b() { name=$1; shift; timeout 900 python bench.py "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err; }
+b() { name=$1; shift; timeout 900 python bench.py --full "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err; }
 b c3_f64 
 b c3_f64_driver --steps 20 --warmup 5 --no-cpu-baseline
 b c3_f32 --precision f32 --no-cpu-baseline
@@ -22,8 +22,8 @@ b c4_ilqr_f64_b512 --workload c4 --batch 512 --steps 2 --warmup 1 --no-cpu-basel
 b c5_candidates_f64 --workload c5 --steps 2 --warmup 1
 # launcher plumbing: `bench.py --gpus 2` starts its own two ranks; both mapped onto this box's one
 # GPU (gloo for the barriers / all-gather; RCCL refuses two ranks on one device).  Not a performance number.
-AMPC_BENCH_FORCE_DEVICE=0 AMPC_BENCH_BACKEND=gloo timeout 600 python bench.py --gpus 2 --steps 50 --warmup 5 --no-cpu-baseline > $OUT/bench_2rank_plumbing.json 2> $OUT/bench_2rank_plumbing.err
-AMPC_BENCH_FORCE_DEVICE=0 AMPC_BENCH_BACKEND=gloo timeout 600 python bench.py --gpus 2 --workload c5 --batch 8 --steps 1 --warmup 1 --no-cpu-baseline > $OUT/bench_2rank_c5_plumbing.json 2> $OUT/bench_2rank_c5_plumbing.err
+AMPC_BENCH_FORCE_DEVICE=0 AMPC_BENCH_BACKEND=gloo timeout 600 python bench.py --full --gpus 2 --steps 50 --warmup 5 --no-cpu-baseline > $OUT/bench_2rank_plumbing.json 2> $OUT/bench_2rank_plumbing.err
+AMPC_BENCH_FORCE_DEVICE=0 AMPC_BENCH_BACKEND=gloo timeout 600 python bench.py --full --gpus 2 --workload c5 --batch 8 --steps 1 --warmup 1 --no-cpu-baseline > $OUT/bench_2rank_c5_plumbing.json 2> $OUT/bench_2rank_c5_plumbing.err
 timeout 300 python tools/dropin_rate.py > $OUT/dropin_rate.log 2>&1
 timeout 300 python tools/dropin_breakdown.py > $OUT/dropin_breakdown.log 2>&1
 timeout 600 python tools/model_axis_rate.py > $OUT/model_axis_rate.log 2>&1

@@ -8,7 +8,7 @@ mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
 (timeout 1500 python -m pytest tests -m gpu -q 2>&1 | tail -15) > $OUT/pytest_gpu.log
 timeout 300 python __graft_entry__.py --smoke > $OUT/smoke.log 2>&1
-b() { name=$1; shift; timeout 900 python bench.py "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err; }
+b() { name=$1; shift; timeout 900 python bench.py --full "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err; }
 b c3_f64
 b c3_f64_driver --steps 20 --warmup 5 --no-cpu-baseline
 b c3_f32 --precision f32 --no-cpu-baseline
