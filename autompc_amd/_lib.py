@@ -103,6 +103,8 @@ SIGNATURES = {
                                           _ip, POINTER(ctypes.c_longlong)]),
     "ampc_ilqr_plan_set_models": (c_int, [c_void_p, c_int, POINTER(c_void_p)]),
     "ampc_mppi_plan_set_models": (c_int, [c_void_p, c_int, POINTER(c_void_p), _ip]),
+    "ampc_kstep_errors": (c_int, [POINTER(c_void_p), c_int, c_int, _ip, c_int, _dp, _dp, _dp, c_int, _dp, _dp,
+                                  _dp]),
 }
 
 

@@ -1,0 +1,64 @@
+"""Model evaluators: score a model configuration by prediction accuracy (reference:
+autompc/evaluation/evaluator.py, holdout_evaluator.py).
+
+``evaluator(factory, cfg)`` builds and trains one model and scores it, as the reference's does.
+``evaluator.evaluate_batch(factory, cfgs)`` is the batched form the tuner uses: every model is built with
+``skip_train_model=True``, the MLPs are fitted together by one ``sysid.mlp_fit.fit_mlps`` call (lockstep,
+each model exactly as its own ``train()``), the others are trained one by one, and all are scored by
+``model_errors`` (one k-step kernel call per model shape).
+
+Deviation from the reference (bug not reproduced): the reference's ``"rmsmens"`` string raises ``NameError``
+(evaluator.py:32-38: ``get_model_rmsmens`` is not imported and is called with ``horizon=``); here it scores
+RMSMENS at the evaluator's horizon.
+"""
+from abc import ABC, abstractmethod
+
+import numpy as np
+
+from .model_metrics import METRICS, get_model_rmse, get_model_rmsmens, model_errors
+
+
+class ModelEvaluator(ABC):
+    """Evaluates models by prediction accuracy.  metric: "rmse", "rmsmens" or a callable
+    ``(model, [Trajectory]) -> float``."""
+
+    def __init__(self, system, trajs, metric, rng, horizon=1):
+        self.system = system
+        self.trajs = trajs
+        self.rng = rng
+        self.horizon = int(horizon)
+        if isinstance(metric, str):
+            if metric == "rmse":
+                self.metric = lambda model, trajs: get_model_rmse(model, trajs, horizon=self.horizon)
+            elif metric == "rmsmens":
+                self.metric = lambda model, trajs: get_model_rmsmens(model, trajs, horiz=self.horizon)
+            else:
+                raise ValueError("metric must be one of %s or a callable, not %r" % (", ".join(METRICS), metric))
+            self.metric_name = metric
+        elif callable(metric):
+            self.metric, self.metric_name = metric, None
+        else:
+            raise ValueError("metric must be one of %s or a callable, not %r" % (", ".join(METRICS), metric))
+
+    @abstractmethod
+    def __call__(self, model_factory, configuration):
+        """Score of the model `model_factory` builds from `configuration`."""
+        raise NotImplementedError
+
+    # -- the batched form ----------------------------------------------------------------------------
+    def _train_and_score(self, model_factory, configurations, train_trajs, test_trajs):
+        from ..sysid.mlp import MLP
+        from ..sysid.mlp_fit import fit_mlps
+        models = [model_factory(cfg, train_trajs, skip_train_model=True) for cfg in configurations]
+        for m in models:
+            # a model per configuration lives for one evaluation: no run-time kernel build for its shape
+            m.jit_kernels = False
+        mlps = [m for m in models if isinstance(m, MLP)]
+        if mlps:
+            fit_mlps(mlps, train_trajs)
+        for m in models:
+            if not isinstance(m, MLP):
+                m.train(train_trajs, silent=True)
+        if self.metric_name is not None:
+            return model_errors(models, test_trajs, [self.horizon], self.metric_name)[:, 0]
+        return np.array([float(self.metric(m, test_trajs)) for m in models])

@@ -39,7 +39,8 @@ enum { AMPC_TERM_REFERENCE = 0, AMPC_TERM_PER_PARTICLE = 1 };
 const char* ampc_last_error(void);
 int ampc_version(void);   /* 100 * major + minor; 104: + ampc_mppi_run_legacy; 105: + ampc_set_affine_quad_costs;
                            * 106: + ampc_ilqr_solve_queue_var, ampc_ilqr_closed_loop_var, ampc_set_indicator_costs,
-                           *      ampc_mppi_plan_set_models, ampc_ilqr_plan_set_models; 107: + ampc_set_mlp_dev, ampc_ilqr_plan_set_constants */
+                           *      ampc_mppi_plan_set_models, ampc_ilqr_plan_set_models; 107: + ampc_set_mlp_dev, ampc_ilqr_plan_set_constants;
+                           * 108: + ampc_kstep_errors */
 int ampc_device_count(void);
 
 /* ---- handle ------------------------------------------------------------------------------ */
@@ -465,6 +466,19 @@ int ampc_ilqr_closed_loop_var(ampc_ilqr_plan* p, ampc_handle* surrogate, int n_c
                               const int* cost_index, const int* horizon, const int* model_index, int n_steps,
                               int max_iter, double* traj_obs, double* traj_ctrls, int* failed, int* steps_done,
                               long long* iterations);
+
+/* ---- model accuracy ---------------------------------------------------------------------- */
+/* k-step prediction error sums (evaluation/model_metrics.py:12-43 get_model_rmse, :45-111 get_model_rmsmens, for
+ * every horizon 1..kmax in one pass).  models[n_models]: handles of one shape (ampc_*_plan_set_models rules; MLP
+ * models and linear models of at most 64 states -- SINDy and wide linear models are refused).
+ * traj_len[n_traj]; obs [sum len][obs_dim], ctrls [sum len][nu] (row-major, trajectories concatenated);
+ * init_states: NULL (model state = observation) or [n_models][sum len][state_dim] (traj_to_states rows);
+ * inv_std [obs_dim] (needed only for sq_delta_err); outputs sq_err / sq_delta_err [n_models][kmax]
+ * = sums over counted rows and obs dims (sq_delta_err may be NULL).  A start point (trajectory i, time t) counts
+ * towards horizon h when t + h <= len_i - 1.  Deterministic (fixed-order f64 sums).  Synchronises. */
+int ampc_kstep_errors(ampc_handle* const* models, int n_models, int n_traj, const int* traj_len,
+                      int obs_dim, const double* obs, const double* ctrls, const double* init_states,
+                      int kmax, const double* inv_std, double* sq_err, double* sq_delta_err);
 
 #ifdef __cplusplus
 }
