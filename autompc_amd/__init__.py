@@ -12,9 +12,9 @@ from .costs import Cost, QuadCost, SumCost, ThresholdCost, BoxThresholdCost
 from .sysid import (Model, ModelFactory, MLP, MLPFactory, SINDy, SINDyFactory, ARX, ARXFactory,
                     Koopman, KoopmanFactory)
 from .control import (Controller, ControllerFactory, MPPI, MPPIFactory, IterativeLQR,
-                      IterativeLQRFactory)
+                      IterativeLQRFactory, LQR, LQRFactory)
 from .utils import simulate
 
 __all__ = ["Model", "ModelFactory", "MLP", "MLPFactory", "SINDy", "SINDyFactory", "ARX", "ARXFactory", "Koopman", "KoopmanFactory", "Controller", "ControllerFactory",
-           "MPPI", "MPPIFactory", "IterativeLQR", "IterativeLQRFactory", "simulate", "System", "Trajectory", "TimeStep", "zeros", "empty", "extend", "Task",
+           "MPPI", "MPPIFactory", "IterativeLQR", "IterativeLQRFactory", "LQR", "LQRFactory", "simulate", "System", "Trajectory", "TimeStep", "zeros", "empty", "extend", "Task",
            "Cost", "QuadCost", "SumCost", "ThresholdCost", "BoxThresholdCost"]

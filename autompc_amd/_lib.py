@@ -105,6 +105,13 @@ SIGNATURES = {
     "ampc_mppi_plan_set_models": (c_int, [c_void_p, c_int, POINTER(c_void_p), _ip]),
     "ampc_kstep_errors": (c_int, [POINTER(c_void_p), c_int, c_int, _ip, c_int, _dp, _dp, _dp, c_int, _dp, _dp,
                                   _dp]),
+    "ampc_lqr_plan_create": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
+    "ampc_lqr_plan_destroy": (c_int, [c_void_p]),
+    "ampc_lqr_plan_set_models": (c_int, [c_void_p, POINTER(c_void_p)]),
+    "ampc_lqr_gains": (c_int, [c_void_p, _ip, _dp, _dp, _dp, _dp, _ip]),
+    "ampc_lqr_plan_set_loop": (c_int, [c_void_p, _ip, _ip, _ip, _dp, _dp, _dp, _dp]),
+    "ampc_lqr_closed_loop": (c_int, [c_void_p, c_void_p, _dp, _dp, c_int, _dp, _dp]),
+    "ampc_lqr_closed_loop_scored": (c_int, [c_void_p, c_void_p, _dp, _dp, c_int, c_int, _ip, _dp, _dp, _dp, _dp]),
 }
 
 
@@ -789,3 +796,90 @@ class IlqrPlan:
                                                  dptr(out.get("ks")), iptr(out["converged"]), iptr(out["iters"]),
                                                  iptr(out["status"]), dptr(out["objective"])))
         return out
+
+
+class LqrPlan:
+    """Finite-horizon LQR controllers of B problems (ampc_lqr_*): linear controller models of any state dimension
+    up to 256 in one plan, gains kept on the device for the closed loop.  f64 only."""
+
+    def __init__(self, models, obs_dim, ctrl_dim, device=0):
+        """models: B f64 Handles staged with set_linear (one per problem; the same handle may repeat)."""
+        lib = load()
+        if lib.ampc_device_count() <= 0:
+            raise AmpcError("no HIP device visible: the MI355X path cannot run here "
+                            "(there is no CPU fallback by design)")
+        self.lib, self.models = lib, list(models)
+        self.B, self.no, self.nu = len(self.models), int(obs_dim), int(ctrl_dim)
+        self._p = c_void_p()
+        check(lib.ampc_lqr_plan_create(int(device), self.B, self.no, self.nu, ctypes.byref(self._p)))
+        _live_plans.add(self)
+        for h in set(self.models):
+            h._plans.add(self)
+        arr = (c_void_p * self.B)(*[h._h for h in self.models])
+        check(lib.ampc_lqr_plan_set_models(self._p, arr))
+        self.n = np.array([int(h.nx) for h in self.models])
+        self.k_off = np.concatenate([[0], np.cumsum(self.nu * self.n)])
+
+    def close(self):
+        if getattr(self, "_p", None) is not None and self._p:
+            self.lib.ampc_lqr_plan_destroy(self._p)
+            self._p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def gains(self, horizons, Q, R, F):
+        """K of every problem (list of [nu][n_i] arrays) and status [B] (0 ok, 1 singular / non-finite)."""
+        B, no, nu = self.B, self.no, self.nu
+        hz = np.broadcast_to(np.asarray(horizons, dtype=np.int32), (B,)).copy()
+        Q = as_f64(np.broadcast_to(Q, (B, no, no)))
+        R = as_f64(np.broadcast_to(R, (B, nu, nu)))
+        F = as_f64(np.broadcast_to(F, (B, no, no)))
+        K = np.empty(int(self.k_off[-1]))
+        status = np.zeros(B, dtype=np.int32)
+        check(self.lib.ampc_lqr_gains(self._p, iptr(hz), dptr(Q), dptr(R), dptr(F), dptr(K), iptr(status)))
+        return [K[self.k_off[i]:self.k_off[i + 1]].reshape(nu, self.n[i]) for i in range(B)], status
+
+    def set_loop(self, rules, goal, ctrl_lo, ctrl_hi, lifts=None):
+        """rules [B]: 0 observation, 1 ARX shift, 2 lift; lifts: per problem None or (kinds, params); goal [B][no]
+        (or [no]); ctrl_lo / ctrl_hi [nu]."""
+        B = self.B
+        rules = np.asarray(rules, dtype=np.int32).reshape(B).copy()
+        nb = np.zeros(B, dtype=np.int32)
+        kinds, params = [], []
+        for i in range(B):
+            if rules[i] == 2:
+                k, p = lifts[i]
+                nb[i] = len(k)
+                kinds += [int(v) for v in k]
+                params += [float(v) for v in p]
+        kinds = np.array(kinds + [0], dtype=np.int32)
+        params = np.array(params + [0.0])
+        goal = as_f64(np.broadcast_to(goal, (B, self.no)))
+        check(self.lib.ampc_lqr_plan_set_loop(self._p, iptr(rules), iptr(nb), iptr(kinds), dptr(params), dptr(goal),
+                                              dptr(as_f64(ctrl_lo)), dptr(as_f64(ctrl_hi))))
+
+    def closed_loop(self, surrogate, init_states, init_sim, n_steps, terms=None, trajectories=True):
+        """Episodes of n_steps control steps against `surrogate` (a Handle).  init_states: list of each problem's
+        initial model state; init_sim [B][surrogate state dim].  Returns (obs [B][T+1][no], ctrls [B][T+1][nu])
+        or, with cost `terms` ((kinds, params) of ampc_score_trajectories), (scores, obs, ctrls)."""
+        B, T1 = self.B, int(n_steps) + 1
+        st = as_f64(np.concatenate([np.asarray(s, dtype=np.float64).ravel() for s in init_states]))
+        sim = as_f64(init_sim).reshape(B, -1)
+        obs = np.empty((B, T1, self.no)) if trajectories else None
+        ctl = np.empty((B, T1, self.nu)) if trajectories else None
+        if terms is None:
+            check(self.lib.ampc_lqr_closed_loop(self._p, surrogate._h, dptr(st), dptr(sim), int(n_steps), dptr(obs),
+                                                dptr(ctl)))
+            return obs, ctl
+        kinds, params = terms
+        kinds = np.ascontiguousarray(kinds, dtype=np.int32)
+        params = as_f64(params)
+        scores = np.empty(B)
+        check(self.lib.ampc_lqr_closed_loop_scored(self._p, surrogate._h, dptr(st), dptr(sim), int(n_steps),
+                                                   len(kinds), iptr(kinds), dptr(params), dptr(scores), dptr(obs),
+                                                   dptr(ctl)))
+        return scores, obs, ctl

@@ -1,0 +1,176 @@
+"""Finite-horizon LQR whose gain is computed on MI355X.
+
+Drop-in for the reference's ``autompc.control.LQR`` / ``LQRFactory`` / ``FiniteHorizonLQR`` /
+``InfiniteHorizonLQR`` (reference: autompc/control/lqr.py:139-253): same constructors, ``state_dim``,
+``traj_to_state``, ``run`` and ``is_compatible``.
+
+The gain K = -(R + B'PB)^-1 B'PA after horizon + 1 Riccati steps from P = F (``_finite_horz_dt_lqr``,
+lqr.py:35-47; Q and F zero-padded to the model state, :146-151) comes from a one-problem ``ampc_lqr_gains``
+call (csrc/lqr_kernels.hpp).  A singular R + B'PB raises ``numpy.linalg.LinAlgError`` as the reference's
+``la.inv`` does.  ``run`` is the reference's host arithmetic (lqr.py:174-192): a nu x n matrix-vector product
+per step is cheaper on the host than a device round trip.
+
+Deviations, on purpose: the reference prints P after every gain (lqr.py:44-45) -- not reproduced;
+``InfiniteHorizonLQR`` calls ``dare``, which the reference never defines (lqr.py:104), so it raises
+``NotImplementedError`` here; a nonlinear model raises ``TypeError`` (what ``is_compatible`` implies); a horizon
+outside LQRFactory's range 1..1000 raises ``ValueError`` (the device refuses longer recursions).
+"""
+import numpy as np
+
+from .. import _lib
+from .controller import Controller, ControllerFactory
+
+
+# LQRFactory's space (lqr.py:214-224): finite_horizon {"true", "false"} (default "true"); horizon 1..1000
+# (default 10), active when finite_horizon == "true"
+FINITE_HORIZON_CHOICES = ("true", "false")
+HORIZON_RANGE = (1, 1000)
+HORIZON_DEFAULT = 10
+
+
+def _is_linear(model):
+    return bool(getattr(model, "is_linear", False))
+
+
+def _compatible(task, model):
+    # (a task type without constraint support has none)
+    eq = getattr(task, "eq_cons_present", lambda: False)()
+    ineq = getattr(task, "ineq_cons_present", lambda: False)()
+    return _is_linear(model) and task.is_cost_quad() and not task.are_obs_bounded() and not eq and not ineq
+
+
+def lqr_gain(A, B, Q, R, F, horizon, device=0):
+    """K of _finite_horz_dt_lqr(A, B, Q, R, 0, F, horizon) (lqr.py:35-47) on the device; Q, F of obs_dim
+    (padded there).  Raises LinAlgError where the reference's inversion fails."""
+    if not HORIZON_RANGE[0] <= int(horizon) <= HORIZON_RANGE[1]:
+        raise ValueError("LQR horizon %r is outside LQRFactory's range %d..%d (lqr.py:214-224)"
+                         % (horizon, HORIZON_RANGE[0], HORIZON_RANGE[1]))
+    A, B = _lib.as_f64(A), _lib.as_f64(B)
+    Q, R, F = _lib.as_f64(Q), _lib.as_f64(R), _lib.as_f64(F)
+    h = _lib.Handle(device, "f64", jit=False)
+    try:
+        h.set_linear(A, B)
+        plan = _lib.LqrPlan([h], Q.shape[0], B.shape[1], device=device)
+        try:
+            K, status = plan.gains([int(horizon)], Q[None], R[None], F[None])
+        finally:
+            plan.close()
+    finally:
+        h.close()
+    if status[0] != 0:
+        raise np.linalg.LinAlgError("LQR: R + B'PB is singular (or the Riccati recursion overflowed)")
+    return K[0]
+
+
+class FiniteHorizonLQR(Controller):
+    def __init__(self, system, task, model, horizon, device=None):
+        super().__init__(system, task, model)
+        if not _is_linear(model):
+            raise TypeError("LQR needs a linear model (ARX, Koopman: to_linear()); %s is not one "
+                            "(the reference's is_compatible, lqr.py:161-168)" % type(model).__name__)
+        A, B = model.to_linear()
+        self.horizon = horizon
+        Q, R, F = task.get_cost().get_cost_matrices()
+        self.device = device if device is not None else getattr(model, "device", 0)
+        self.K = lqr_gain(A, B, Q, R, F, int(horizon), device=self.device)
+        self.model = model
+        self.umin = task.get_ctrl_bounds()[:, 0]
+        self.umax = task.get_ctrl_bounds()[:, 1]
+
+    @property
+    def state_dim(self):
+        return self.model.state_dim + self.system.ctrl_dim
+
+    @staticmethod
+    def is_compatible(system, task, model):
+        return _compatible(task, model)
+
+    def traj_to_state(self, traj):
+        return np.concatenate([self.model.traj_to_state(traj), traj[-1].ctrl])
+
+    def run(self, state, new_obs):
+        nu = self.system.ctrl_dim
+        modelstate = self.model.update_state(state[:-nu], state[-nu:], new_obs)
+        x0 = np.asarray(self.task.get_cost().get_goal())
+        if x0.size < modelstate.size:
+            state0 = np.zeros(modelstate.size)
+            state0[:x0.size] = x0
+        else:
+            state0 = x0
+        u = self.K @ (modelstate - state0)
+        u = np.minimum(u, self.umax)
+        u = np.maximum(u, self.umin)
+        return u, np.concatenate([modelstate, u])
+
+
+class InfiniteHorizonLQR(Controller):
+    def __init__(self, system, task, model):
+        super().__init__(system, task, model)
+        raise NotImplementedError("infinite-horizon LQR: the reference calls dare(), which it never defines "
+                                  "(autompc/control/lqr.py:104); use finite_horizon=True")
+
+    @property
+    def state_dim(self):
+        return self.model.state_dim + self.system.ctrl_dim
+
+    @staticmethod
+    def is_compatible(system, task, model):
+        return _compatible(task, model) and not task.are_ctrl_bounded()
+
+    def traj_to_state(self, traj):
+        return np.concatenate([self.model.traj_to_state(traj), traj[-1].ctrl])
+
+    def run(self, state, new_obs):
+        raise NotImplementedError
+
+
+class LQR(Controller):
+    def __init__(self, system, task, model, finite_horizon, horizon=None, device=None):
+        super().__init__(system, task, model)
+        if not isinstance(finite_horizon, bool):
+            finite_horizon = finite_horizon == "true"
+        if finite_horizon:
+            self._controller = FiniteHorizonLQR(system, task, model, horizon, device=device)
+        else:
+            self._controller = InfiniteHorizonLQR(system, task, model)
+
+    @property
+    def K(self):
+        return self._controller.K
+
+    @property
+    def state_dim(self):
+        return self._controller.state_dim
+
+    @staticmethod
+    def is_compatible(system, task, model):
+        return _compatible(task, model)
+
+    def traj_to_state(self, traj):
+        return self._controller.traj_to_state(traj)
+
+    def run(self, state, new_obs):
+        return self._controller.run(state, new_obs)
+
+
+class LQRFactory(ControllerFactory):
+    """Hyper-parameters as lqr.py:214-224: finite_horizon {"true", "false"}, horizon int 1..1000 (default 10)
+    conditioned on finite_horizon == "true"."""
+    Controller = LQR
+    name = "LQR"
+
+    def get_configuration_space(self):
+        try:
+            import ConfigSpace as CS
+            import ConfigSpace.conditions as CSC
+            import ConfigSpace.hyperparameters as CSH
+        except ImportError as e:
+            raise ImportError("ConfigSpace is required for get_configuration_space()") from e
+        cs = CS.ConfigurationSpace()
+        finite = CSH.CategoricalHyperparameter("finite_horizon", choices=list(FINITE_HORIZON_CHOICES),
+                                               default_value="true")
+        horizon = CSH.UniformIntegerHyperparameter("horizon", lower=HORIZON_RANGE[0], upper=HORIZON_RANGE[1],
+                                                   default_value=HORIZON_DEFAULT)
+        cs.add_hyperparameters([horizon, finite])
+        cs.add_condition(CSC.InCondition(child=horizon, parent=finite, values=["true"]))
+        return cs

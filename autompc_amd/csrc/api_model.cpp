@@ -313,6 +313,7 @@ extern "C" int ampc_set_mlp(ampc_handle* h, int nx, int nu, int n_hidden, const 
                             const double* const* biases, const double* xu_mean,
                             const double* xu_std, const double* dy_mean, const double* dy_std) {
   if (int rc = check_shape(h, nx, nu, n_hidden, hidden_sizes, activation, "ampc_set_mlp")) return rc;
+  h->lin_n = 0;
   REQUIRE(weights && biases && xu_mean && xu_std && dy_mean && dy_std, "ampc_set_mlp: NULL argument");
   HIP_OK(hipSetDevice(h->device));
   h->W.assign(n_hidden + 1, {});
@@ -419,6 +420,7 @@ extern "C" int ampc_set_mlp_dev(ampc_handle* h, int nx, int nu, int n_hidden, co
                                 const double* const* biases_dev, const double* xu_mean_dev,
                                 const double* xu_std_dev, const double* dy_mean_dev, const double* dy_std_dev) {
   if (int rc = check_shape(h, nx, nu, n_hidden, hidden_sizes, activation, "ampc_set_mlp_dev")) return rc;
+  h->lin_n = 0;
   REQUIRE(weights_dev && biases_dev && xu_mean_dev && xu_std_dev && dy_mean_dev && dy_std_dev,
           "ampc_set_mlp_dev: NULL argument");
   HIP_OK(hipSetDevice(h->device));
@@ -485,11 +487,29 @@ static int set_linear_wide(ampc_handle* h, int nx, int nu, const double* A, cons
 //   x' = x + I * ([A - I | B] [x; u])
 // so that every kernel written for the MLP (rollout, Jacobians, iLQR, closed loop) serves the
 // linear models too.  Multiplying by the identity output layer is exact; A - I rounds once.
+static int set_linear_mlp(ampc_handle* h, int nx, int nu, const double* A, const double* B);
 extern "C" int ampc_set_linear(ampc_handle* h, int nx, int nu, const double* A, const double* B) {
   REQUIRE(h && A && B, "ampc_set_linear: NULL argument");
   REQUIRE(nx >= 1 && nx <= kLinMaxNx, "ampc_set_linear: state dim must be in 1..256");
   REQUIRE(nu >= 1 && nu <= kMaxNu, "ampc_set_linear: ctrl dim must be in 1..16");
-  if (nx > 64 || env_int("AMPC_LINEAR_WIDE", 0) != 0) return set_linear_wide(h, nx, nu, A, B);
+  h->lin_n = 0;
+  const int rc = (nx > 64 || env_int("AMPC_LINEAR_WIDE", 0) != 0) ? set_linear_wide(h, nx, nu, A, B)
+                                                                  : set_linear_mlp(h, nx, nu, A, B);
+  if (rc) return rc;
+  // the exact [A | B] in f64 whatever the compute precision, for the LQR plans' Riccati recursion: a host copy
+  // here, uploaded only when a plan takes the model (ampc_lqr_plan_set_models)
+  std::vector<double>& ab = h->lin_ab_host;
+  ab.resize((size_t)nx * (nx + nu));
+  for (int i = 0; i < nx; ++i) {
+    for (int j = 0; j < nx; ++j) ab[(size_t)i * (nx + nu) + j] = A[(size_t)i * nx + j];
+    for (int j = 0; j < nu; ++j) ab[(size_t)i * (nx + nu) + nx + j] = B[(size_t)i * nu + j];
+  }
+  h->lin_n = nx;
+  h->lin_gen++;
+  return 0;
+}
+
+static int set_linear_mlp(ampc_handle* h, int nx, int nu, const double* A, const double* B) {
   const int kin = nx + nu;
   std::vector<double> w0((size_t)nx * kin), w1((size_t)nx * nx, 0.0), b0(nx, 0.0);
   for (int i = 0; i < nx; ++i) {
@@ -724,6 +744,7 @@ extern "C" int ampc_set_sindy(ampc_handle* h, int nx, int nu, int n_feat, const 
                               const double* xi, int continuous, double dt, int strict_reference,
                               int n_pairs, const int* pair_var, const int* pair_exp) {
   REQUIRE(h && kind && arg0 && arg1 && param && xi, "ampc_set_sindy: NULL argument");
+  h->lin_n = 0;
   REQUIRE(nx >= 1 && nx <= 64 && nu >= 1 && nu <= kMaxNu, "ampc_set_sindy: nx in 1..64, nu in 1..16");
   REQUIRE(n_feat >= 1 && n_feat <= 4096, "ampc_set_sindy: n_feat in 1..4096");
   REQUIRE(n_pairs >= 0 && n_pairs <= 10 * 4096 && (n_pairs == 0 || (pair_var && pair_exp)),

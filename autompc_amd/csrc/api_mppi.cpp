@@ -1237,6 +1237,13 @@ static int score_device(ampc_handle* h, const void* d_obs, const void* d_ctl, in
   return 0;
 }
 
+int score_device_f64(ampc_handle* h, const void* d_obs, const void* d_ctl, int B, int T1, int nx, int nu, int no,
+                     int n_terms, const int* kinds, const double* params, double* scores) {
+  ScoreSpec sp;
+  sp.n_terms = n_terms; sp.kinds = kinds; sp.params = params;
+  return score_device<double>(h, d_obs, d_ctl, B, T1, nx, nu, no, sp, scores);
+}
+
 template <typename T>
 static int score_host_impl(ampc_handle* h, int B, int T1, int nx, int nu, int no, const double* obs,
                            const double* ctrls, const ScoreSpec& sp, double* scores) {

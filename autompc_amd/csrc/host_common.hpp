@@ -132,6 +132,11 @@ struct ampc_handle {
   int l_nxp = 0, l_kp = 0;
   DevBuf lin_buf;                 // fragments of [A | B], then the plain row-major copy
   bool has_model() const { return has_mlp || has_sindy || has_lin; }
+  int lin_n = 0;                  // > 0: the model came from ampc_set_linear with this many states
+  unsigned lin_gen = 0;           // counts ampc_set_linear calls (an LQR plan notices a re-staged model)
+  std::vector<double> lin_ab_host;  // its exact [A | B], f64 row-major [lin_n][lin_n + nu] (the LQR plans) ...
+  DevBuf lin_ab;                  // ... uploaded when a plan first needs it (api_lqr.cpp)
+  unsigned lin_ab_gen = ~0u;      // lin_gen of what lin_ab holds
   int s_nfeat = 0, s_continuous = 0, s_strict = 1, s_ntrig = 0, s_npow = 0, s_ntab = 0, s_nmon = 0, s_npool = 0;
   double s_dt = 0.0;
   DevBuf sindy_int, sindy_flt;    // kind|a0|a1 (int), par|xi (T)
@@ -165,6 +170,11 @@ void ampc_internal_jit_kick(ampc_handle* h);
 
 // Plans hold references on their handles (api.cpp).
 void handle_release(ampc_handle* h);
+
+// Task-cost scores of device-resident f64 trajectories (api_mppi.cpp: score_device), for other closed loops:
+// d_obs [B][T1][nx], d_ctl [B][T1][nu] on h's device, enqueued on h's stream; scores [B] on the host.
+int score_device_f64(ampc_handle* h, const void* d_obs, const void* d_ctl, int B, int T1, int nx, int nu, int no,
+                     int n_terms, const int* kinds, const double* params, double* scores);
 
 template <typename T> inline MlpDev<T>& model_of(ampc_handle* h);
 template <> inline MlpDev<double>& model_of<double>(ampc_handle* h) { return h->md; }

@@ -51,6 +51,12 @@ def candidate_from_config(system, cfg):
     ``"cfg"`` (tuners report it back unchanged)."""
     d = config_dict(cfg)
     ctrl, cost, model = subspace(d, CTRLR), subspace(d, COST), subspace(d, MODEL)
+    if "finite_horizon" in ctrl:
+        # LQRFactory's sub-space (control/lqr.py:214-224).  No batched evaluator scores LQR candidates yet: refused
+        # here, before the fall-through below would score them as iLQR candidates of the same horizon
+        raise NotImplementedError("%s:finite_horizon: LQR pipelines are not tunable by the batched evaluators yet "
+                                  "(build the controller with autompc_amd.LQRFactory and score it with simulate())"
+                                  % CTRLR)
     if "horizon" not in ctrl:
         raise KeyError("configuration has no %s:horizon (MPPIFactory / IterativeLQRFactory sub-space)" % CTRLR)
     cand = {"horizon": int(ctrl["horizon"])}

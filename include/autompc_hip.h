@@ -29,6 +29,7 @@ extern "C" {
 typedef struct ampc_handle ampc_handle;
 typedef struct ampc_mppi_plan ampc_mppi_plan;
 typedef struct ampc_ilqr_plan ampc_ilqr_plan;
+typedef struct ampc_lqr_plan ampc_lqr_plan;
 
 enum { AMPC_F64 = 0, AMPC_F32 = 1 };
 enum { AMPC_ACT_RELU = 0, AMPC_ACT_TANH = 1, AMPC_ACT_SIGMOID = 2, AMPC_ACT_SELU = 3 };
@@ -40,7 +41,7 @@ const char* ampc_last_error(void);
 int ampc_version(void);   /* 100 * major + minor; 104: + ampc_mppi_run_legacy; 105: + ampc_set_affine_quad_costs;
                            * 106: + ampc_ilqr_solve_queue_var, ampc_ilqr_closed_loop_var, ampc_set_indicator_costs,
                            *      ampc_mppi_plan_set_models, ampc_ilqr_plan_set_models; 107: + ampc_set_mlp_dev, ampc_ilqr_plan_set_constants;
-                           * 108: + ampc_kstep_errors */
+                           * 108: + ampc_kstep_errors; 109: + ampc_lqr_* */
 int ampc_device_count(void);
 
 /* ---- handle ------------------------------------------------------------------------------ */
@@ -479,6 +480,50 @@ int ampc_ilqr_closed_loop_var(ampc_ilqr_plan* p, ampc_handle* surrogate, int n_c
 int ampc_kstep_errors(ampc_handle* const* models, int n_models, int n_traj, const int* traj_len,
                       int obs_dim, const double* obs, const double* ctrls, const double* init_states,
                       int kmax, const double* inv_std, double* sq_err, double* sq_delta_err);
+
+/* ---- finite-horizon LQR (f64 only) ---------------------------------------------------------- */
+/* A plan of n_problems LQR controllers (reference: autompc/control/lqr.py:139-192 FiniteHorizonLQR) that keeps
+ * their gains on the device between ampc_lqr_gains and the closed loop.  obs_dim 1..256, ctrl_dim 1..16. */
+int ampc_lqr_plan_create(int device, int n_problems, int obs_dim, int ctrl_dim, ampc_lqr_plan** out);
+int ampc_lqr_plan_destroy(ampc_lqr_plan* p);
+/* models[n_problems]: one controller model per problem, handles staged with ampc_set_linear (the reference's
+ * is_compatible requires a linear model, lqr.py:161-168), f64, on the plan's device, ctrl_dim controls and
+ * obs_dim..256 states; state dimensions may differ between problems.  The plan holds a reference on each.  A model
+ * re-staged afterwards makes every later call on the plan fail until the models are set again. */
+int ampc_lqr_plan_set_models(ampc_lqr_plan* p, ampc_handle* const* models);
+/* Gains of every problem in ONE launch (_finite_horz_dt_lqr, lqr.py:35-47, with N = 0): from P = F, horizon[i] + 1
+ * Riccati steps P <- A'PA - (A'PB)(R + B'PB)^-1 (B'PA) + Q, then K = -(R + B'PB)^-1 B'PA of the last P.
+ *   horizons [n] in 1..1000 (LQRFactory's range, lqr.py:214-224); Q [n][obs_dim][obs_dim], R [n][nu][nu], F [n][obs_dim][obs_dim] (FiniteHorizonLQR.__init__ pads
+ *   Q and F with zeros to the model state, lqr.py:146-151: so does the device);
+ *   K [sum_i nu * n_i] (NULL: keep on the device only): problem i's K [nu][n_i] row-major, problems in order;
+ *   status [n] (may be NULL): 0 ok, 1 R + B'PB singular (an exact zero pivot of the partial-pivot elimination) or
+ *   a non-finite value -- the reference's LinAlgError / NaN; that problem's K is NaN.
+ * A problem's result does not depend on the other problems of the call (fixed-order sums).  Synchronises. */
+int ampc_lqr_gains(ampc_lqr_plan* p, const int* horizons, const double* Q, const double* R, const double* F,
+                   double* K, int* status);
+/* How each problem's controller updates its model state in the closed loop (model.update_state, lqr.py:176-177):
+ *   rules [n]: 0 = the observation (model state == observation), 1 = ARX shift A s + B u_prev with the
+ *   observation slot overwritten (arx.py:94-99), 2 = lift of the observation (koopman.py:105-122, 166-168)
+ *   with n_basis[i] basis functions (kind, parameter) taken in order from lift_kinds / lift_params (kinds of
+ *   ampc_mppi_plan_set_state_lift; n_basis[i] * obs_dim = n_i); n_basis / lift_* may be NULL without rule 2;
+ *   goal [n][obs_dim]: the cost's goal (state0 = goal zero-padded to the model state, lqr.py:178-182);
+ *   ctrl_lo / ctrl_hi [nu]: control bounds (u is clipped, lqr.py:184-185; +-inf for none). */
+int ampc_lqr_plan_set_loop(ampc_lqr_plan* p, const int* rules, const int* n_basis, const int* lift_kinds,
+                           const double* lift_params, const double* goal, const double* ctrl_lo,
+                           const double* ctrl_hi);
+/* simulate(controller, init_obs, sim_model=surrogate, max_steps=n_steps) for every problem at once, on the device
+ * (utils/simulation.py:44-63; FiniteHorizonLQR.run, lqr.py:174-192): per control step the controller state update,
+ * u = clip(K (s - state0)), simstate = surrogate.pred(simstate, u).  Needs ampc_lqr_gains and ampc_lqr_plan_set_loop.
+ *   surrogate: f64 handle with any model (MLP, SINDy, linear) whose state starts with the observation;
+ *   init_state [sum_i n_i]: each problem's model.traj_to_state of the one-row trajectory (the previous control is 0);
+ *   init_sim [n][surrogate state dim]: sim_model.traj_to_state of that trajectory;
+ *   traj_obs [n][n_steps+1][obs_dim], traj_ctrls [n][n_steps+1][nu] (last control row zero); either may be NULL. */
+int ampc_lqr_closed_loop(ampc_lqr_plan* p, ampc_handle* surrogate, const double* init_state, const double* init_sim,
+                         int n_steps, double* traj_obs, double* traj_ctrls);
+/* ... ending in the task-cost score of every trajectory (cost terms as ampc_score_trajectories): scores [n]. */
+int ampc_lqr_closed_loop_scored(ampc_lqr_plan* p, ampc_handle* surrogate, const double* init_state,
+                                const double* init_sim, int n_steps, int n_terms, const int* kinds,
+                                const double* params, double* scores, double* traj_obs, double* traj_ctrls);
 
 #ifdef __cplusplus
 }
