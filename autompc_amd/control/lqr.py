@@ -39,12 +39,44 @@ def _compatible(task, model):
     return _is_linear(model) and task.is_cost_quad() and not task.are_obs_bounded() and not eq and not ineq
 
 
-def lqr_gain(A, B, Q, R, F, horizon, device=0):
-    """K of _finite_horz_dt_lqr(A, B, Q, R, 0, F, horizon) (lqr.py:35-47) on the device; Q, F of obs_dim
-    (padded there).  Raises LinAlgError where the reference's inversion fails."""
+def check_horizon(horizon):
     if not HORIZON_RANGE[0] <= int(horizon) <= HORIZON_RANGE[1]:
         raise ValueError("LQR horizon %r is outside LQRFactory's range %d..%d (lqr.py:214-224)"
                          % (horizon, HORIZON_RANGE[0], HORIZON_RANGE[1]))
+
+
+def check_linear(model):
+    if not _is_linear(model):
+        raise TypeError("LQR needs a linear model (ARX, Koopman: to_linear()); %s is not one "
+                        "(the reference's is_compatible, lqr.py:161-168)" % type(model).__name__)
+
+
+def lqr_gain_host(A, B, Q, R, F, horizon):
+    """K of _finite_horz_dt_lqr(A, B, Q, R, 0, F, horizon) on the host, in the reference's own order of operations
+    (lqr.py:15-20, 35-47; Q and F zero-padded to the model state, :146-151).  For models the device cannot take
+    (more than 256 states).  Raises LinAlgError where the reference's ``la.inv`` does."""
+    check_horizon(horizon)
+    A, B = np.asarray(A, dtype=np.float64), np.asarray(B, dtype=np.float64)
+    n = A.shape[0]
+    Q, F = np.asarray(Q, dtype=np.float64), np.asarray(F, dtype=np.float64)
+    Qp, Fp = np.zeros((n, n)), np.zeros((n, n))
+    Qp[:Q.shape[0], :Q.shape[1]] = Q
+    Fp[:F.shape[0], :F.shape[1]] = F
+    R = np.asarray(R, dtype=np.float64)
+    N = np.zeros((n, B.shape[1]))
+
+    def riccati(Pk):
+        return A.T @ Pk @ A - (A.T @ Pk @ B + N) @ np.linalg.inv(R + B.T @ Pk @ B) @ (B.T @ Pk @ A + N.T) + Qp
+    P2 = riccati(Fp)
+    for _ in range(int(horizon)):
+        P2 = riccati(P2)
+    return -np.linalg.inv(R + B.T @ P2 @ B) @ B.T @ P2 @ A
+
+
+def lqr_gain(A, B, Q, R, F, horizon, device=0):
+    """K of _finite_horz_dt_lqr(A, B, Q, R, 0, F, horizon) (lqr.py:35-47) on the device; Q, F of obs_dim
+    (padded there).  Raises LinAlgError where the reference's inversion fails."""
+    check_horizon(horizon)
     A, B = _lib.as_f64(A), _lib.as_f64(B)
     Q, R, F = _lib.as_f64(Q), _lib.as_f64(R), _lib.as_f64(F)
     h = _lib.Handle(device, "f64", jit=False)
@@ -65,9 +97,7 @@ def lqr_gain(A, B, Q, R, F, horizon, device=0):
 class FiniteHorizonLQR(Controller):
     def __init__(self, system, task, model, horizon, device=None):
         super().__init__(system, task, model)
-        if not _is_linear(model):
-            raise TypeError("LQR needs a linear model (ARX, Koopman: to_linear()); %s is not one "
-                            "(the reference's is_compatible, lqr.py:161-168)" % type(model).__name__)
+        check_linear(model)
         A, B = model.to_linear()
         self.horizon = horizon
         Q, R, F = task.get_cost().get_cost_matrices()

@@ -32,8 +32,19 @@ def shard_bounds(n_items, rank, world):
 
 def candidate_work(c):
     """Relative device work of one candidate's episode: rollouts per control step for MPPI candidates
-    (num_path x horizon), the horizon for iLQR candidates -- what evaluate_sharded balances."""
-    return float(c.get("num_path", 1)) * float(c.get("horizon", 1)) if isinstance(c, dict) else 1.0
+    (num_path x horizon), the horizon for iLQR candidates -- what evaluate_sharded balances.  LQR candidates
+    (controller "lqr"): the gain recursion, (horizon + 2) n^2 (n + nu) for a model of n states (n = nu = 1 while
+    the candidate carries no model yet); an infinite-horizon candidate is not run (1)."""
+    if not isinstance(c, dict):
+        return 1.0
+    if c.get("controller") == "lqr":
+        if c.get("finite_horizon", True) in (False, "false"):
+            return 1.0
+        m = c.get("model")
+        n = float(m.state_dim) if m is not None else 1.0
+        nu = float(m.system.ctrl_dim) if m is not None else 1.0
+        return (float(c.get("horizon", 1)) + 2.0) * n * n * (n + nu)
+    return float(c.get("num_path", 1)) * float(c.get("horizon", 1))
 
 
 def balanced_shards(weights, world):

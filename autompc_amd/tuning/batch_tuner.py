@@ -25,7 +25,9 @@ import numpy as np
 
 from .batch_eval import (IlqrCandidateEvaluator, evaluate_sharded, global_ids, random_candidates,
                          random_ilqr_candidates)
-from .configs import (DictConfiguration, candidates_from_configs, config_from_candidate, sample_mlp_config)
+from .configs import (DictConfiguration, candidates_from_configs, config_from_candidate, lqr_candidates_from_configs,
+                      sample_arx_config, sample_koopman_config, sample_mlp_config)
+from .lqr_eval import LqrCandidateEvaluator, random_lqr_candidates
 
 # same fields, same order as the reference's namedtuple (pipeline_tuner.py:19-21)
 PipelineTuneResult = namedtuple("PipelineTuneResult", [
@@ -101,12 +103,40 @@ class BatchPipelineTuner:
         self.surr_trajs = []
         self._inc_cfg, self._inc_cost, self._inc_truedyn = None, float("inf"), None
 
+    def _is_lqr(self):
+        return isinstance(self.evaluator, LqrCandidateEvaluator)
+
+    def _model_cfg_sampler(self):
+        """What draws a candidate's `_model:` sub-configuration: the factory's own ``sample_configuration`` if it
+        has one; for LQR pipelines ARXFactory's / KoopmanFactory's space; else MLPFactory's."""
+        draw_cfg = getattr(self.model_factory, "sample_configuration", None)
+        if draw_cfg is not None:
+            return lambda rng: dict(draw_cfg(rng))
+        if self._is_lqr():
+            from ..sysid.linear import ARXFactory, KoopmanFactory
+            if isinstance(self.model_factory, ARXFactory):
+                return sample_arx_config
+            if isinstance(self.model_factory, KoopmanFactory):
+                return sample_koopman_config
+            raise TypeError("LQR pipelines need a linear model factory (ARXFactory or KoopmanFactory), not %s"
+                            % type(self.model_factory).__name__)
+        return sample_mlp_config
+
     def _random_search(self, n, rng):
-        draw = random_ilqr_candidates if isinstance(self.evaluator, IlqrCandidateEvaluator) else random_candidates
+        if self._is_lqr():
+            draw = random_lqr_candidates
+        elif isinstance(self.evaluator, IlqrCandidateEvaluator):
+            draw = random_ilqr_candidates
+        else:
+            draw = random_candidates
         cands = draw(self.system, n, seed=int(rng.integers(1 << 31)))
         if self.models:
             for c, k in zip(cands, rng.integers(len(self.models), size=n)):
                 c["model"], c["model_index"] = self.models[int(k)], int(k)
+        elif self.model_factory is not None and self._is_lqr():
+            draw_cfg = self._model_cfg_sampler()
+            for c in cands:
+                c["model_cfg"] = draw_cfg(rng)
         elif self.model_factory is not None:
             draw_cfg = getattr(self.model_factory, "sample_configuration", None)
             for c in cands:
@@ -210,7 +240,17 @@ class BatchPipelineTuner:
         task.set_cost(QuadCost(self.system, mat(cand["Q"], no), mat(cand["R"], nu), mat(cand["F"], no),
                                goal=ev.goal))
         task.set_ctrl_bounds(ev.umin, ev.umax)
-        if "num_path" not in cand:            # an iLQR candidate (horizon + cost weights)
+        if cand.get("controller") == "lqr":   # the drop-in LQR (gain on the device, run() on the host)
+            from ..control.lqr import LQR
+            from .lqr_eval import is_finite_horizon
+            if not is_finite_horizon(cand.get("finite_horizon", True)):
+                return float("inf")           # InfiniteHorizonLQR: the reference's dare is undefined
+            try:
+                ctl = LQR(self.system, task, cand.get("model") or ev.model, "true", int(cand["horizon"]),
+                          device=ev.device)
+            except np.linalg.LinAlgError:
+                return float("inf")           # eval_cfg's LinAlgError branch (pipeline_tuner.py:236-239)
+        elif "num_path" not in cand:          # an iLQR candidate (horizon + cost weights)
             ctl = IterativeLQR(self.system, task, cand.get("model") or ev.model, int(cand["horizon"]),
                                precision=ev.precision, device=ev.device)
         else:
@@ -248,7 +288,8 @@ class BatchPipelineTuner:
             if configs is not None:
                 if len(configs) < done + n:
                     raise ValueError("%d configurations given, %d evaluations asked" % (len(configs), n_iters))
-                batch = candidates_from_configs(self.system, configs[done:done + n])
+                from_cfgs = lqr_candidates_from_configs if self._is_lqr() else candidates_from_configs
+                batch = from_cfgs(self.system, configs[done:done + n])
             else:
                 batch = self.ask(n, rng)
             # randomness keyed by (seed, global evaluation index): scores do not depend on the
