@@ -112,6 +112,8 @@ SIGNATURES = {
     "ampc_lqr_plan_set_loop": (c_int, [c_void_p, _ip, _ip, _ip, _dp, _dp, _dp, _dp]),
     "ampc_lqr_closed_loop": (c_int, [c_void_p, c_void_p, _dp, _dp, c_int, _dp, _dp]),
     "ampc_lqr_closed_loop_scored": (c_int, [c_void_p, c_void_p, _dp, _dp, c_int, c_int, _ip, _dp, _dp, _dp, _dp]),
+    "ampc_linfit_fit": (c_int, [c_int, c_int, _ip, c_int, c_int, _dp, _dp, c_int, _ip, c_int, _ip, _ip, _dp, _dp, _ip,
+                                _dp]),
 }
 
 
@@ -883,3 +885,32 @@ class LqrPlan:
                                                    len(kinds), iptr(kinds), dptr(params), dptr(scores), dptr(obs),
                                                    dptr(ctl)))
         return scores, obs, ctl
+
+
+def linfit_fit(traj_len, obs, ctrls, arx_histories=(), koopman_bases=(), device=0):
+    """ampc_linfit_fit: least-squares fits of ARX histories and Koopman bases ((kinds, params) pairs) of one data set.
+    obs [R][no], ctrls [R][nu]: the trajectories concatenated, traj_len their lengths.  Returns (coeffs, status,
+    min_pivot): a list of coefficient matrices -- ARX [no][1 + k (no + nu)], Koopman [n][n + nu] -- ARX configurations
+    first, and the two per-configuration arrays."""
+    lib = load()
+    if lib.ampc_device_count() <= 0:
+        raise AmpcError("no HIP device visible: the MI355X path cannot run here "
+                        "(there is no CPU fallback by design)")
+    obs, ctrls = as_f64(obs), as_f64(ctrls)
+    no, nu = obs.shape[1], ctrls.shape[1]
+    lens = np.ascontiguousarray(traj_len, dtype=np.int32)
+    if int(lens.sum()) != obs.shape[0] or obs.shape[0] != ctrls.shape[0]:
+        raise ValueError("traj_len does not add up to the rows of obs / ctrls")
+    hist = np.ascontiguousarray(list(arx_histories) + [0], dtype=np.int32)
+    n_arx, n_koop = len(hist) - 1, len(koopman_bases)
+    nb = np.array([len(k) for k, _ in koopman_bases] + [0], dtype=np.int32)
+    kinds = np.array([int(v) for k, _ in koopman_bases for v in k] + [0], dtype=np.int32)
+    params = np.array([float(v) for _, p in koopman_bases for v in p] + [0.0])
+    shapes = [(no, 1 + int(k) * (no + nu)) for k in hist[:-1]] + [(int(b) * no, int(b) * no + nu) for b in nb[:-1]]
+    off = np.concatenate([[0], np.cumsum([r * c for r, c in shapes])]).astype(np.int64)
+    coeffs = np.empty(int(off[-1]))
+    status = np.zeros(n_arx + n_koop, dtype=np.int32)
+    pivot = np.empty(n_arx + n_koop)
+    check(lib.ampc_linfit_fit(int(device), len(lens), iptr(lens), no, nu, dptr(obs), dptr(ctrls), n_arx, iptr(hist),
+                              n_koop, iptr(nb), iptr(kinds), dptr(params), dptr(coeffs), iptr(status), dptr(pivot)))
+    return [coeffs[off[i]:off[i + 1]].reshape(shapes[i]) for i in range(len(shapes))], status, pivot

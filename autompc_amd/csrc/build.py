@@ -1,8 +1,8 @@
 """Build libautompc_hip.so for gfx950 with hipcc (cross-compiles without a GPU).
 
-Fourteen translation units compiled in parallel and linked into one shared library: api.cpp + api_{model,mppi,ilqr,lqr}.cpp
-(the C ABI and host logic by family), launch_{mlp,mppi,ilqr,kstep}.cpp once per precision (-DAMPC_T=double|float) and
-launch_lqr.cpp (f64 only).
+Sixteen translation units compiled in parallel and linked into one shared library: api.cpp +
+api_{model,mppi,ilqr,lqr,linfit}.cpp (the C ABI and host logic by family), launch_{mlp,mppi,ilqr,kstep}.cpp once per
+precision (-DAMPC_T=double|float), launch_lqr.cpp and launch_linfit.cpp (f64 only).
 """
 import concurrent.futures
 import os
@@ -25,7 +25,9 @@ UNITS = [("api", "api.cpp", []), ("api_model", "api_model.cpp", []), ("api_mppi"
          ("api_ilqr", "api_ilqr.cpp", [])] + [
     ("%s_%s" % (fam, t), "launch_%s.cpp" % fam, ["-DAMPC_T=%s" % t] + (["-DAMPC_T_IS_F64=1"] if t == "double" else []))
     for fam in ("mlp", "mppi", "ilqr", "kstep") for t in ("double", "float")] + [
-    ("api_lqr", "api_lqr.cpp", []), ("lqr_double", "launch_lqr.cpp", ["-DAMPC_T=double", "-DAMPC_T_IS_F64=1"])]
+    ("api_lqr", "api_lqr.cpp", []), ("lqr_double", "launch_lqr.cpp", ["-DAMPC_T=double", "-DAMPC_T_IS_F64=1"]),
+    ("api_linfit", "api_linfit.cpp", []),
+    ("linfit_double", "launch_linfit.cpp", ["-DAMPC_T=double", "-DAMPC_T_IS_F64=1"])]
 SOURCES = sorted({u[1] for u in UNITS})
 
 

@@ -4,7 +4,8 @@ autompc/evaluation/evaluator.py, holdout_evaluator.py).
 ``evaluator(factory, cfg)`` builds and trains one model and scores it, as the reference's does.
 ``evaluator.evaluate_batch(factory, cfgs)`` is the batched form the tuner uses: every model is built with
 ``skip_train_model=True``, the MLPs are fitted together by one ``sysid.mlp_fit.fit_mlps`` call (lockstep,
-each model exactly as its own ``train()``), the others are trained one by one, and all are scored by
+each model exactly as its own ``train()``), the others are trained one by one -- or, with ``linear_fit="device"``,
+the ARX / Koopman models by one ``sysid.linear_fit.fit_linear_models`` call -- and all are scored by
 ``model_errors`` (one k-step kernel call per model shape).
 
 Deviation from the reference (bug not reproduced): the reference's ``"rmsmens"`` string raises ``NameError``
@@ -22,7 +23,13 @@ class ModelEvaluator(ABC):
     """Evaluates models by prediction accuracy.  metric: "rmse", "rmsmens" or a callable
     ``(model, [Trajectory]) -> float``."""
 
-    def __init__(self, system, trajs, metric, rng, horizon=1):
+    def __init__(self, system, trajs, metric, rng, horizon=1, linear_fit="host"):
+        """linear_fit: how ``evaluate_batch`` fits ARX / Koopman models -- "host": each by its own ``train()``;
+        "device": all of a batch by one ``sysid.linear_fit.fit_linear_models`` call (one Gram pass on the device,
+        equal configurations fitted once)."""
+        if linear_fit not in ("host", "device"):
+            raise ValueError("linear_fit must be 'host' or 'device'")
+        self.linear_fit = linear_fit
         self.system = system
         self.trajs = trajs
         self.rng = rng
@@ -56,9 +63,16 @@ class ModelEvaluator(ABC):
         mlps = [m for m in models if isinstance(m, MLP)]
         if mlps:
             fit_mlps(mlps, train_trajs)
-        for m in models:
-            if not isinstance(m, MLP):
-                m.train(train_trajs, silent=True)
+        others = [m for m in models if not isinstance(m, MLP)]
+        if self.linear_fit == "device":
+            from ..sysid.linear import ARX, Koopman
+            from ..sysid.linear_fit import fit_linear_models
+            linear = [m for m in others if isinstance(m, (ARX, Koopman))]
+            if linear:
+                self.last_linear_fit = fit_linear_models(linear, train_trajs)
+            others = [m for m in others if not isinstance(m, (ARX, Koopman))]
+        for m in others:
+            m.train(train_trajs, silent=True)
         if self.metric_name is not None:
             return model_errors(models, test_trajs, [self.horizon], self.metric_name)[:, 0]
         return np.array([float(self.metric(m, test_trajs)) for m in models])

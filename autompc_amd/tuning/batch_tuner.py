@@ -45,7 +45,7 @@ class BatchPipelineTuner:
 
     def __init__(self, system, evaluator, batch_size=64, sampler=None, truedyn_noise="device",
                  eval_kwargs=None, keep_trajs=False, balance=None, models=None, model_factory=None,
-                 trajs=None, as_configs=False):
+                 trajs=None, as_configs=False, linear_fit="host"):
         """truedyn_noise: the noise mode of the controllers scored against the true dynamics
         (MPPI(noise=...): "device" Philox, or "numpy" / "numpy_device" = the reference's global
         legacy stream).  eval_kwargs: extra keyword arguments for every ``evaluator.evaluate`` call
@@ -60,6 +60,10 @@ class BatchPipelineTuner:
         HIP-graph captured; each model exactly as its own ``train(trajs)``), their parameters staged from
         device memory (ampc_set_mlp_dev).  Fits are cached by configuration; every rank fits only the models
         of its own shard.  ``fit_seconds`` / ``eval_seconds`` accumulate what the two phases took.
+
+        linear_fit: "host" fits every ARX / Koopman configuration by its own ``train()``; "device" fits all fresh
+        ones of a shard by one ``sysid.linear_fit.fit_linear_models`` call (one Gram pass on the device);
+        ``linear_host_fits`` counts the models that call handed back to ``train()``.
 
         as_configs: report ``cfgs`` / ``inc_cfg`` as pipeline configurations with the reference's key names
         (`_ctrlr:horizon`, `_cost:<obs>_Q`, `_model:lr`, ...; tuning/configs.py) instead of candidate dicts;
@@ -91,6 +95,10 @@ class BatchPipelineTuner:
         self._fitted = {}                      # model configuration -> fitted model
         self.fit_seconds = self.eval_seconds = 0.0
         self.models_fitted = 0
+        if linear_fit not in ("host", "device"):
+            raise ValueError("linear_fit must be 'host' or 'device'")
+        self.linear_fit = linear_fit
+        self.linear_host_fits = 0
         self.batch_size = int(batch_size)
         if self.batch_size < 1:
             raise ValueError("batch_size must be >= 1")
@@ -173,9 +181,16 @@ class BatchPipelineTuner:
             mlps = [m for m in fresh.values() if isinstance(m, MLP)]
             if mlps:
                 fit_mlps(mlps, self.trajs)
-            for m in fresh.values():
-                if not isinstance(m, MLP):
-                    m.train(self.trajs, silent=True)
+            others = [m for m in fresh.values() if not isinstance(m, MLP)]
+            if self.linear_fit == "device":
+                from ..sysid.linear import ARX, Koopman
+                from ..sysid.linear_fit import fit_linear_models
+                linear = [m for m in others if isinstance(m, (ARX, Koopman))]
+                if linear:
+                    self.linear_host_fits += fit_linear_models(linear, self.trajs).host_fits
+                others = [m for m in others if not isinstance(m, (ARX, Koopman))]
+            for m in others:
+                m.train(self.trajs, silent=True)
             self._fitted.update(fresh)
             self.models_fitted += len(fresh)
         for c in want:

@@ -11,7 +11,8 @@ Here configurations are proposed in batches (``ask``), a whole batch is scored a
 ``evaluate_batch`` fits every MLP of the batch in one lockstep fit and scores all models with one k-step
 kernel call per shape (evaluation/), sharded over the ranks of the default ``torch.distributed`` group by
 ``evaluate_sharded`` -- and reported back (``tell``).  The proposal rule is random search over the factories'
-ranges (the default sampler covers ``MLPFactory`` through ``sample_mlp_config``); any other proposer drives
+ranges (the default sampler covers ``MLPFactory``, ``ARXFactory`` and ``KoopmanFactory`` through
+``sample_mlp_config`` / ``sample_arx_config`` / ``sample_koopman_config``); any other proposer drives
 ``ask`` / ``tell`` through ``sampler=`` or passes ``configs=`` to ``run``.  Scores that are not finite count as
 ``inf``; only a strict improvement replaces the incumbent.
 """
@@ -20,7 +21,7 @@ from collections import namedtuple
 import numpy as np
 
 from .batch_eval import evaluate_sharded
-from .configs import DictConfiguration, config_dict, sample_mlp_config
+from .configs import DictConfiguration, config_dict, sample_arx_config, sample_koopman_config, sample_mlp_config
 
 # same fields, same order as the reference's namedtuple (model_tuner.py:37-38)
 ModelTuneResult = namedtuple("ModelTuneResult", ["inc_cfg", "cfgs", "inc_cfgs", "costs", "inc_costs"])
@@ -30,7 +31,8 @@ class BatchModelTuner:
     """evaluator: a ``ModelEvaluator`` (``evaluate_batch(factory, cfgs) -> scores`` is used when it has one,
     else ``evaluator(factory, cfg)`` per configuration) with the full data set as ``evaluator.trajs``.
     sampler: ``sampler(tuner, n, rng) -> n combined configurations``; the default draws a factory uniformly and
-    its configuration from its ranges (``MLPFactory``: ``sample_mlp_config``; other factories need a
+    its configuration from its ranges (``MLPFactory`` / ``ARXFactory`` / ``KoopmanFactory``: ``sample_mlp_config`` /
+    ``sample_arx_config`` / ``sample_koopman_config``; other factories need a
     ``sample_configuration(rng)`` method, ``sampler=`` or ``run(..., configs=...)``)."""
 
     def __init__(self, system, evaluator, batch_size=64, sampler=None):
@@ -82,14 +84,19 @@ class BatchModelTuner:
         for _ in range(n):
             k = int(rng.integers(len(self.model_factories))) if len(self.model_factories) > 1 else 0
             factory = self.model_factories[k]
+            from ..sysid.linear import ARXFactory, KoopmanFactory
             from ..sysid.mlp import MLPFactory
             if isinstance(factory, MLPFactory):
                 cfg = sample_mlp_config(rng)
             elif hasattr(factory, "sample_configuration"):
                 cfg = factory.sample_configuration(rng)
+            elif isinstance(factory, ARXFactory):
+                cfg = sample_arx_config(rng)
+            elif isinstance(factory, KoopmanFactory):
+                cfg = sample_koopman_config(rng)
             else:
-                raise ValueError("the default sampler covers MLPFactory only: pass sampler= or run(..., configs=...) "
-                                 "for %s" % factory.name)
+                raise ValueError("the default sampler covers MLPFactory, ARXFactory and KoopmanFactory: pass sampler= or "
+                                 "run(..., configs=...) for %s" % factory.name)
             out.append(self.combined_config(factory, cfg))
         return out
 

@@ -41,7 +41,7 @@ const char* ampc_last_error(void);
 int ampc_version(void);   /* 100 * major + minor; 104: + ampc_mppi_run_legacy; 105: + ampc_set_affine_quad_costs;
                            * 106: + ampc_ilqr_solve_queue_var, ampc_ilqr_closed_loop_var, ampc_set_indicator_costs,
                            *      ampc_mppi_plan_set_models, ampc_ilqr_plan_set_models; 107: + ampc_set_mlp_dev, ampc_ilqr_plan_set_constants;
-                           * 108: + ampc_kstep_errors; 109: + ampc_lqr_* */
+                           * 108: + ampc_kstep_errors; 109: + ampc_lqr_*; 110: + ampc_linfit_fit */
 int ampc_device_count(void);
 
 /* ---- handle ------------------------------------------------------------------------------ */
@@ -480,6 +480,26 @@ int ampc_ilqr_closed_loop_var(ampc_ilqr_plan* p, ampc_handle* surrogate, int n_c
 int ampc_kstep_errors(ampc_handle* const* models, int n_models, int n_traj, const int* traj_len,
                       int obs_dim, const double* obs, const double* ctrls, const double* init_states,
                       int kmax, const double* inv_std, double* sq_err, double* sq_delta_err);
+
+/* ---- least-squares model fits (f64 only) ---------------------------------------------------- */
+/* Fits ARX models (sysid/arx.py:62-116) and Koopman models of method "lstsq" (sysid/koopman.py:141-154) of ONE data
+ * set in one call.  traj_len[n_traj]; obs [sum len][obs_dim], ctrls [sum len][ctrl_dim] (row-major, trajectories
+ * concatenated, as ampc_kstep_errors takes them).  Row t of a trajectory with a successor is one design row with
+ * target obs[t + 1]; trajectories of one row contribute nothing.
+ * arx_history[n_arx]: one ARX configuration each (state 1 + history (obs_dim + ctrl_dim) - ctrl_dim <= 256).
+ * koopman_n_basis[n_koopman] and the concatenated koopman_kinds / koopman_params (as ampc_mppi_plan_set_state_lift:
+ * 0 identity, 1 power, 2 sin, 3 cos): one Koopman configuration each, state n_basis * obs_dim <= 256, basis-major;
+ * configurations with the same basis share one Gram pass.
+ * Outputs, ARX configurations first, each group in the order given: coeffs, packed: ARX [obs_dim][1 + history
+ * (obs_dim + ctrl_dim)] in ARX's feature order, Koopman [n][n + ctrl_dim] = [A | B]; status[n_arx + n_koopman]:
+ * 0 fitted, 1 not fitted here (the scaled normal equations are singular or too ill conditioned for a Cholesky
+ * solve: smallest squared pivot below n_features * 2^-26; fit that model on the host); min_pivot: the smallest
+ * squared pivot of the unit-diagonal Gram's factor.  Deterministic: a configuration's result does not depend on
+ * the other configurations of the call or on their order.  Synchronises. */
+int ampc_linfit_fit(int device, int n_traj, const int* traj_len, int obs_dim, int ctrl_dim, const double* obs,
+                    const double* ctrls, int n_arx, const int* arx_history, int n_koopman,
+                    const int* koopman_n_basis, const int* koopman_kinds, const double* koopman_params,
+                    double* coeffs, int* status, double* min_pivot);
 
 /* ---- finite-horizon LQR (f64 only) ---------------------------------------------------------- */
 /* A plan of n_problems LQR controllers (reference: autompc/control/lqr.py:139-192 FiniteHorizonLQR) that keeps
