@@ -6,7 +6,8 @@ autompc/evaluation/evaluator.py, holdout_evaluator.py).
 ``skip_train_model=True``, the MLPs are fitted together by one ``sysid.mlp_fit.fit_mlps`` call (lockstep,
 each model exactly as its own ``train()``), the others are trained one by one -- or, with ``linear_fit="device"``,
 the ARX / Koopman models by one ``sysid.linear_fit.fit_linear_models`` call -- and all are scored by
-``model_errors`` (one k-step kernel call per model shape).
+``model_errors`` (one k-step kernel call per model shape; with ``linear_kstep="device"`` the ARX / Koopman models
+wider than 64 states too, all of them in one ``ampc_kstep_errors_linear`` call, instead of the host loop).
 
 Deviation from the reference (bug not reproduced): the reference's ``"rmsmens"`` string raises ``NameError``
 (evaluator.py:32-38: ``get_model_rmsmens`` is not imported and is called with ``horizon=``); here it scores
@@ -16,29 +17,38 @@ from abc import ABC, abstractmethod
 
 import numpy as np
 
-from .model_metrics import METRICS, get_model_rmse, get_model_rmsmens, model_errors
+from .model_metrics import METRICS, KstepReport, get_model_rmse, get_model_rmsmens, model_errors
 
 
 class ModelEvaluator(ABC):
     """Evaluates models by prediction accuracy.  metric: "rmse", "rmsmens" or a callable
     ``(model, [Trajectory]) -> float``."""
 
-    def __init__(self, system, trajs, metric, rng, horizon=1, linear_fit="host"):
+    def __init__(self, system, trajs, metric, rng, horizon=1, linear_fit="host", linear_kstep="host"):
         """linear_fit: how ``evaluate_batch`` fits ARX / Koopman models -- "host": each by its own ``train()``;
         "device": all of a batch by one ``sysid.linear_fit.fit_linear_models`` call (one Gram pass on the device,
-        equal configurations fitted once)."""
+        equal configurations fitted once).
+        linear_kstep: how the string metrics score linear models wider than 64 states -- "host": the loop over
+        ``pred_batch``; "device": one ``ampc_kstep_errors_linear`` call per batch (``model_errors``).
+        ``last_kstep`` holds the ``KstepReport`` of the last ``evaluate_batch`` (``host_fallbacks``)."""
         if linear_fit not in ("host", "device"):
             raise ValueError("linear_fit must be 'host' or 'device'")
+        if linear_kstep not in ("host", "device"):
+            raise ValueError("linear_kstep must be 'host' or 'device'")
         self.linear_fit = linear_fit
+        self.linear_kstep = linear_kstep
+        self.last_kstep = None
         self.system = system
         self.trajs = trajs
         self.rng = rng
         self.horizon = int(horizon)
         if isinstance(metric, str):
             if metric == "rmse":
-                self.metric = lambda model, trajs: get_model_rmse(model, trajs, horizon=self.horizon)
+                self.metric = lambda model, trajs: get_model_rmse(model, trajs, horizon=self.horizon,
+                                                                  linear_kstep=self.linear_kstep)
             elif metric == "rmsmens":
-                self.metric = lambda model, trajs: get_model_rmsmens(model, trajs, horiz=self.horizon)
+                self.metric = lambda model, trajs: get_model_rmsmens(model, trajs, horiz=self.horizon,
+                                                                     linear_kstep=self.linear_kstep)
             else:
                 raise ValueError("metric must be one of %s or a callable, not %r" % (", ".join(METRICS), metric))
             self.metric_name = metric
@@ -74,5 +84,7 @@ class ModelEvaluator(ABC):
         for m in others:
             m.train(train_trajs, silent=True)
         if self.metric_name is not None:
-            return model_errors(models, test_trajs, [self.horizon], self.metric_name)[:, 0]
+            self.last_kstep = KstepReport()
+            return model_errors(models, test_trajs, [self.horizon], self.metric_name,
+                                linear_kstep=self.linear_kstep, report=self.last_kstep)[:, 0]
         return np.array([float(self.metric(m, test_trajs)) for m in models])

@@ -12,6 +12,15 @@ models (``MLP``; ``ARX`` / ``Koopman`` of at most 64 states) are grouped by shap
 error sums of every horizon (csrc/kstep_kernels.hpp).  Every other model -- SINDy, wide linear models, any
 foreign ``Model`` -- takes the host fallback, the reference's own algorithm over ``model.pred_batch``.
 
+``linear_kstep="device"`` (opt-in; the default ``"host"`` is the path above, bit for bit) scores trained
+``_LinearModel``s of 65..256 states on the GPU too: they are grouped by ``(precision, device, ctrl_dim)``
+(``wide_linear_key``) and each group is ONE ``ampc_kstep_errors_linear`` call, whatever mix of state dimensions it
+holds -- ARX histories 4..10 and Koopman lifts side by side (csrc/kstep_linear_kernels.hpp).  Initial states are
+formed on the device by the model's state rule (``linear_state_rule``: the ARX lag gather, the Koopman lift, or
+``traj_to_states`` rows uploaded for that model only); the ARX gather is bit-identical to ``traj_to_states``, the
+lift's powers / sin / cos differ from numpy's at rounding level.  ``model_errors`` fills a ``KstepReport`` (also kept
+as ``model_metrics.last_report``): ``host_fallbacks`` counts the models the host loop scored.
+
 Definitions (the reference's, for horizon h; only start points t with t + h <= L_i - 1 count, so a trajectory
 of at most h rows contributes nothing):
     RMSE(h)    = sqrt(S_h / N_h),  S_h = sum over counted rows and the first obs_dim state entries of
@@ -33,6 +42,25 @@ from .. import _lib
 
 METRICS = ("rmse", "rmsmens")
 _DEVICE_MAX_LINEAR_STATES = 64          # wider linear models are refused by ampc_kstep_errors
+_WIDE_MAX_LINEAR_STATES = 256           # ampc_set_linear / ampc_kstep_errors_linear
+_WIDE_MAX_CTRLS = 16
+_LDS_BYTES = 160 * 1024
+LINEAR_KSTEP = ("host", "device")
+
+
+class KstepReport:
+    """What one ``model_errors`` call did: ``device_models`` scored by ``ampc_kstep_errors``, ``wide_models`` by
+    ``ampc_kstep_errors_linear`` in ``wide_calls`` calls, ``host_fallbacks`` by the host loop over ``pred_batch``."""
+
+    def __init__(self):
+        self.device_models = self.wide_models = self.wide_calls = self.host_fallbacks = 0
+
+    def __repr__(self):
+        return "KstepReport(device_models=%d, wide_models=%d, wide_calls=%d, host_fallbacks=%d)" % (
+            self.device_models, self.wide_models, self.wide_calls, self.host_fallbacks)
+
+
+last_report = KstepReport()
 
 
 def normalize(means, std, A):
@@ -125,6 +153,128 @@ def device_shape_key(model):
     return None
 
 
+# ---- wide linear models: state rules and the one-launch entry ------------------------------------------
+def linear_state_rule(model, obs_dim=None):
+    """How ``ampc_kstep_errors_linear`` forms the model's initial states, as plain values:
+    ``{"rule": 1, "history": k}`` (ARX: the lag gather), ``{"rule": 2, "kinds": int32[], "params": float64[]}``
+    (Koopman without product terms: the lift) or ``{"rule": 0}`` (rows from ``traj_to_states``, or the observation
+    itself for a model without it).  Rules 1 and 2 are given only when the class's own ``traj_to_states`` is in
+    use and the rule's state size is the width of the trained ``A``."""
+    from ..sysid.linear import ARX, Koopman
+    cls = type(model)
+    no = model.system.obs_dim if obs_dim is None else int(obs_dim)
+    nu = model.system.ctrl_dim
+    width = None if getattr(model, "A", None) is None else int(np.shape(model.A)[0])
+    if (isinstance(model, ARX) and cls.traj_to_states is ARX.traj_to_states
+            and cls._get_all_feature_vectors is ARX._get_all_feature_vectors
+            and width in (None, 1 + model.k * (no + nu) - nu)):
+        return {"rule": 1, "history": int(model.k)}
+    if (isinstance(model, Koopman) and cls.traj_to_states is Koopman.traj_to_states
+            and cls._transform_observations is Koopman._transform_observations
+            and cls._apply_basis is Koopman._apply_basis):
+        lift = model.device_lift()
+        if lift is not None and width in (None, len(lift[0]) * no):
+            return {"rule": 2, "kinds": np.asarray(lift[0], dtype=np.int32),
+                    "params": np.asarray(lift[1], dtype=np.float64)}
+    return {"rule": 0}
+
+
+def rule_states(rule, obs, ctrls):
+    """The states of ONE trajectory (obs [T][obs_dim], ctrls [T][ctrl_dim]) by a ``linear_state_rule`` of kind 1
+    or 2, evaluated in numpy the way the device evaluates it: column by column, row ``max(t - lag, 0)``."""
+    obs, ctrls = np.asarray(obs, dtype=np.float64), np.asarray(ctrls, dtype=np.float64)
+    T = obs.shape[0]
+    if rule["rule"] == 1:
+        cols = [obs]
+        for lag in range(1, int(rule["history"])):
+            idx = np.maximum(np.arange(T) - lag, 0)
+            cols += [obs[idx], ctrls[idx]]
+        cols.append(np.ones((T, 1)))
+        return np.concatenate(cols, axis=1)
+    if rule["rule"] == 2:
+        parts = []
+        for kind, p in zip(rule["kinds"], rule["params"]):
+            parts.append(obs if kind == 0 else obs ** int(p) if kind == 1
+                         else np.sin(p * obs) if kind == 2 else np.cos(p * obs))
+        return np.concatenate(parts, axis=1)
+    raise ValueError("rule 0 has no formula: its rows are the model's traj_to_states")
+
+
+def _wide_lds_bytes(obs_dim, delta, width, ctrl_dim, esz):
+    """kstep_lin_lds_bytes (csrc/kstep_linear_kernels.hpp)."""
+    kp = (width + ctrl_dim + 3) // 4 * 4
+    xs = (kp | 1) if esz == 8 else ((kp + 2) | 2)
+    return (4 if delta else 2) * 16 * obs_dim * 8 + 128 + 2 * 16 * xs * esz
+
+
+def wide_linear_key(model, obs_dim=None, delta=False):
+    """Key of the wide linear models that share one ``ampc_kstep_errors_linear`` call -- (precision, device,
+    ctrl_dim): state dimensions may differ -- or None: not a trained ``_LinearModel`` of 65..256 states and at most
+    16 controls with the class's own ``pred_batch`` (or, with the delta sums of an observation of more than ~200
+    entries, error blocks that do not fit LDS)."""
+    from ..sysid.linear import _LinearModel
+    if not isinstance(model, _LinearModel) or type(model).pred_batch is not _LinearModel.pred_batch:
+        return None
+    if getattr(model, "A", None) is None:
+        return None
+    s = model.system
+    no = s.obs_dim if obs_dim is None else int(obs_dim)
+    width = int(np.shape(model.A)[0])
+    if not (_DEVICE_MAX_LINEAR_STATES < width <= _WIDE_MAX_LINEAR_STATES) or not (1 <= s.ctrl_dim <= _WIDE_MAX_CTRLS):
+        return None
+    if np.shape(model.A) != (width, width) or np.shape(model.B) != (width, s.ctrl_dim) or no > width:
+        return None
+    if not hasattr(model, "traj_to_states") and width != no:
+        return None
+    if _wide_lds_bytes(no, delta, width, s.ctrl_dim, 8 if model.precision == "f64" else 4) > _LDS_BYTES:
+        return None
+    return ("wide-linear", model.precision, int(model.device), s.ctrl_dim)
+
+
+def kstep_sums_linear(models, trajs, kmax, delta=False):
+    """(S [n_models][kmax], D or None) of wide linear models of ONE ``wide_linear_key``: one
+    ``ampc_kstep_errors_linear`` call."""
+    import ctypes
+    obs_dim = _obs_dim(trajs, models[0])
+    lens, obs, ctrls = _concat(trajs)
+    n = len(models)
+    handles = [m._dev() for m in models]
+    hp = (ctypes.c_void_p * n)(*[h._h.value for h in handles])
+    rules = np.zeros(n, dtype=np.int32)
+    history = np.zeros(n, dtype=np.int32)
+    n_basis = np.zeros(n, dtype=np.int32)
+    kinds, params, keep = [], [], []
+    rows = (ctypes.c_void_p * n)()
+    for i, m in enumerate(models):
+        r = linear_state_rule(m, obs_dim)
+        rules[i] = r["rule"]
+        if r["rule"] == 1:
+            history[i] = r["history"]
+        elif r["rule"] == 2:
+            n_basis[i] = len(r["kinds"])
+            kinds.append(r["kinds"])
+            params.append(r["params"])
+        elif hasattr(m, "traj_to_states"):
+            a = np.ascontiguousarray(np.concatenate([m.traj_to_states(t) for t in trajs]), dtype=np.float64)
+            keep.append(a)
+            rows[i] = a.ctypes.data
+    kinds = np.ascontiguousarray(np.concatenate(kinds), dtype=np.int32) if kinds else None
+    params = np.ascontiguousarray(np.concatenate(params), dtype=np.float64) if params else None
+    inv_std = None
+    if delta:
+        _, std = _increment_stats(trajs)
+        with np.errstate(divide="ignore"):
+            inv_std = np.ascontiguousarray(1.0 / std)
+    S = np.empty((n, kmax))
+    D = np.empty((n, kmax)) if delta else None
+    lib = handles[0].lib
+    _lib.check(lib.ampc_kstep_errors_linear(hp, n, len(trajs), _lib.iptr(lens), obs_dim, _lib.dptr(obs),
+                                            _lib.dptr(ctrls), _lib.iptr(rules), _lib.iptr(history),
+                                            _lib.iptr(n_basis), _lib.iptr(kinds), _lib.dptr(params), rows, int(kmax),
+                                            _lib.dptr(inv_std), _lib.dptr(S), _lib.dptr(D)))
+    return S, D
+
+
 def _concat(trajs):
     lens = np.array([len(t) for t in trajs], dtype=np.int32)
     obs = np.ascontiguousarray(np.concatenate([np.asarray(t.obs, dtype=np.float64) for t in trajs]))
@@ -164,12 +314,20 @@ def row_counts(trajs, kmax):
     return np.array([np.maximum(lens - h, 0).sum() for h in range(1, kmax + 1)], dtype=np.float64)
 
 
-def model_errors(models, trajs, horizons, metric="rmse"):
+def model_errors(models, trajs, horizons, metric="rmse", linear_kstep="host", report=None):
     """RMSE or RMSMENS of every model at every horizon: ndarray [len(models), len(horizons)] in input order
     (the data of a ``KstepPredAccGraph`` curve).  Device models are grouped by shape, one ``ampc_kstep_errors``
-    call per group covering every horizon; the others take the host fallback (module docstring)."""
+    call per group covering every horizon; the others take the host fallback (module docstring) -- except, with
+    ``linear_kstep="device"``, the wide linear models: one ``ampc_kstep_errors_linear`` call per
+    ``wide_linear_key``.  ``report``: a ``KstepReport`` to fill (one is made otherwise; either way it becomes
+    ``model_metrics.last_report``)."""
+    global last_report
     if metric not in METRICS:
         raise ValueError("metric must be one of %s, not %r" % (", ".join(METRICS), metric))
+    if linear_kstep not in LINEAR_KSTEP:
+        raise ValueError("linear_kstep must be 'host' or 'device'")
+    report = KstepReport() if report is None else report
+    last_report = report
     models = list(models)
     horizons = [int(h) for h in np.atleast_1d(horizons)]
     if not horizons or min(horizons) < 1:
@@ -180,32 +338,45 @@ def model_errors(models, trajs, horizons, metric="rmse"):
     if metric == "rmsmens":
         for m in models:
             _check_rmsmens_model(m, obs_dim)
-    groups = {}
+    delta = metric == "rmsmens"
+    groups, wide = {}, {}
     for i, m in enumerate(models):
         key = device_shape_key(m) if trajs else None
-        if key is None:
+        if key is not None:
+            groups.setdefault(key, []).append(i)
+            continue
+        if linear_kstep == "device" and trajs:
+            key = wide_linear_key(m, obs_dim, delta)
+        if key is not None:
+            wide.setdefault(key, []).append(i)
+        else:
             host = host_rmse if metric == "rmse" else host_rmsmens
             out[i] = [host(m, trajs, h) for h in horizons]
-        else:
-            groups.setdefault(key, []).append(i)
-    if groups:
+            report.host_fallbacks += 1
+    if groups or wide:
         kmax = max(horizons)
         N = row_counts(trajs, kmax)
         hidx = np.array(horizons) - 1
-        for idx in groups.values():
-            S, D = kstep_sums([models[i] for i in idx], trajs, kmax, delta=(metric == "rmsmens"))
-            with np.errstate(divide="ignore", invalid="ignore"):
-                val = np.sqrt(S / N) if metric == "rmse" else np.sqrt(D / (N * obs_dim))
-            out[idx] = val[:, hidx]
+        for sums, grp in ((kstep_sums, groups), (kstep_sums_linear, wide)):
+            for idx in grp.values():
+                S, D = sums([models[i] for i in idx], trajs, kmax, delta=delta)
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    val = np.sqrt(S / N) if metric == "rmse" else np.sqrt(D / (N * obs_dim))
+                out[idx] = val[:, hidx]
+                if grp is wide:
+                    report.wide_models += len(idx)
+                    report.wide_calls += 1
+                else:
+                    report.device_models += len(idx)
     return out
 
 
-def get_model_rmse(model, trajs, horizon=1):
+def get_model_rmse(model, trajs, horizon=1, linear_kstep="host"):
     """Unnormalised RMSE at a fixed horizon (model_metrics.py:12-43); see the module docstring."""
-    return float(model_errors([model], trajs, [horizon], "rmse")[0, 0])
+    return float(model_errors([model], trajs, [horizon], "rmse", linear_kstep=linear_kstep)[0, 0])
 
 
-def get_model_rmsmens(model, trajs, horiz=1):
+def get_model_rmsmens(model, trajs, horiz=1, linear_kstep="host"):
     """Root mean squared model error, normalised step-wise (model_metrics.py:45-111); see the module
     docstring for the deviations from the reference."""
-    return float(model_errors([model], trajs, [horiz], "rmsmens")[0, 0])
+    return float(model_errors([model], trajs, [horiz], "rmsmens", linear_kstep=linear_kstep)[0, 0])

@@ -41,7 +41,8 @@ const char* ampc_last_error(void);
 int ampc_version(void);   /* 100 * major + minor; 104: + ampc_mppi_run_legacy; 105: + ampc_set_affine_quad_costs;
                            * 106: + ampc_ilqr_solve_queue_var, ampc_ilqr_closed_loop_var, ampc_set_indicator_costs,
                            *      ampc_mppi_plan_set_models, ampc_ilqr_plan_set_models; 107: + ampc_set_mlp_dev, ampc_ilqr_plan_set_constants;
-                           * 108: + ampc_kstep_errors; 109: + ampc_lqr_*; 110: + ampc_linfit_fit */
+                           * 108: + ampc_kstep_errors; 109: + ampc_lqr_*; 110: + ampc_linfit_fit;
+                           * 111: + ampc_kstep_errors_linear */
 int ampc_device_count(void);
 
 /* ---- handle ------------------------------------------------------------------------------ */
@@ -480,6 +481,28 @@ int ampc_ilqr_closed_loop_var(ampc_ilqr_plan* p, ampc_handle* surrogate, int n_c
 int ampc_kstep_errors(ampc_handle* const* models, int n_models, int n_traj, const int* traj_len,
                       int obs_dim, const double* obs, const double* ctrls, const double* init_states,
                       int kmax, const double* inv_std, double* sq_err, double* sq_delta_err);
+
+/* ... of WIDE linear models (handles staged with ampc_set_linear, 65..256 states, at most 16 controls), any mix of
+ * state dimensions in ONE launch (csrc/kstep_linear_kernels.hpp).  The models share precision, device, ctrl_dim and
+ * the data (traj_len, obs, ctrls, kmax, inv_std, outputs: as ampc_kstep_errors); obs_dim <= every state dim.
+ * Initial states are formed on the device by a state rule per model, the rules of ampc_lqr_plan_set_loop:
+ *   rules [n_models]: 0 = rows supplied by the caller, init_rows[i] [sum len][state_dim_i] (traj_to_states rows;
+ *     init_rows or init_rows[i] may be NULL when the model state is the observation, state_dim_i == obs_dim);
+ *   1 = ARX (arx.py:47-76): state [obs_t, (obs_t-1, ctrl_t-1), .., (obs_t-k+1, ctrl_t-k+1), 1] with k =
+ *     arx_history[i], rows before the trajectory's first repeated as the first (a pure gather: bit-identical to
+ *     ARX.traj_to_states); 1 + k (obs_dim + ctrl_dim) - ctrl_dim must equal state_dim_i;
+ *   2 = Koopman lift (koopman.py:105-122) with n_basis[i] basis functions (kind, parameter) taken in order from
+ *     lift_kinds / lift_params (kinds of ampc_mppi_plan_set_state_lift; rule-2 models only consume entries);
+ *     n_basis[i] * obs_dim must equal state_dim_i.
+ *   arx_history / n_basis [n_models] are read for their rule's models only and may be NULL without that rule.
+ * Refused: MLP, SINDy and narrow linear handles, mixed precision / device / ctrl_dim, a rule whose state size is not
+ * the handle's.  Deterministic: a model's sums do not depend on the other models of the call or on their order
+ * (fixed 16-row tiles, fixed-order f64 sums).  Synchronises. */
+int ampc_kstep_errors_linear(ampc_handle* const* models, int n_models, int n_traj, const int* traj_len,
+                             int obs_dim, const double* obs, const double* ctrls, const int* rules,
+                             const int* arx_history, const int* n_basis, const int* lift_kinds,
+                             const double* lift_params, const double* const* init_rows, int kmax,
+                             const double* inv_std, double* sq_err, double* sq_delta_err);
 
 /* ---- least-squares model fits (f64 only) ---------------------------------------------------- */
 /* Fits ARX models (sysid/arx.py:62-116) and Koopman models of method "lstsq" (sysid/koopman.py:141-154) of ONE data
