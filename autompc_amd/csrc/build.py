@@ -1,7 +1,7 @@
 """Build libautompc_hip.so for gfx950 with hipcc (cross-compiles without a GPU).
 
-Eighteen translation units compiled in parallel and linked into one shared library: api.cpp +
-api_{model,mppi,ilqr,lqr,linfit}.cpp (the C ABI and host logic by family), launch_{mlp,mppi,ilqr,kstep,kstep_linear}.cpp
+Twenty translation units compiled in parallel and linked into one shared library: api.cpp +
+api_{model,mppi,ilqr,lqr,linfit}.cpp (the C ABI and host logic by family), launch_{mlp,mppi,ilqr,kstep,kstep_linear,kstep_sindy}.cpp
 once per precision (-DAMPC_T=double|float), launch_lqr.cpp and launch_linfit.cpp (f64 only).
 """
 import concurrent.futures
@@ -24,7 +24,7 @@ def _headers():
 UNITS = [("api", "api.cpp", []), ("api_model", "api_model.cpp", []), ("api_mppi", "api_mppi.cpp", []),
          ("api_ilqr", "api_ilqr.cpp", [])] + [
     ("%s_%s" % (fam, t), "launch_%s.cpp" % fam, ["-DAMPC_T=%s" % t] + (["-DAMPC_T_IS_F64=1"] if t == "double" else []))
-    for fam in ("mlp", "mppi", "ilqr", "kstep", "kstep_linear") for t in ("double", "float")] + [
+    for fam in ("mlp", "mppi", "ilqr", "kstep", "kstep_linear", "kstep_sindy") for t in ("double", "float")] + [
     ("api_lqr", "api_lqr.cpp", []), ("lqr_double", "launch_lqr.cpp", ["-DAMPC_T=double", "-DAMPC_T_IS_F64=1"]),
     ("api_linfit", "api_linfit.cpp", []),
     ("linfit_double", "launch_linfit.cpp", ["-DAMPC_T=double", "-DAMPC_T_IS_F64=1"])]

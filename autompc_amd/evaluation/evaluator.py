@@ -7,7 +7,8 @@ autompc/evaluation/evaluator.py, holdout_evaluator.py).
 each model exactly as its own ``train()``), the others are trained one by one -- or, with ``linear_fit="device"``,
 the ARX / Koopman models by one ``sysid.linear_fit.fit_linear_models`` call -- and all are scored by
 ``model_errors`` (one k-step kernel call per model shape; with ``linear_kstep="device"`` the ARX / Koopman models
-wider than 64 states too, all of them in one ``ampc_kstep_errors_linear`` call, instead of the host loop).
+wider than 64 states too, all of them in one ``ampc_kstep_errors_linear`` call, instead of the host loop; with
+``sindy_kstep="device"`` the SINDy models in one ``ampc_kstep_errors_sindy`` call).
 
 Deviation from the reference (bug not reproduced): the reference's ``"rmsmens"`` string raises ``NameError``
 (evaluator.py:32-38: ``get_model_rmsmens`` is not imported and is called with ``horizon=``); here it scores
@@ -24,19 +25,25 @@ class ModelEvaluator(ABC):
     """Evaluates models by prediction accuracy.  metric: "rmse", "rmsmens" or a callable
     ``(model, [Trajectory]) -> float``."""
 
-    def __init__(self, system, trajs, metric, rng, horizon=1, linear_fit="host", linear_kstep="host"):
+    def __init__(self, system, trajs, metric, rng, horizon=1, linear_fit="host", linear_kstep="host",
+                 sindy_kstep="host"):
         """linear_fit: how ``evaluate_batch`` fits ARX / Koopman models -- "host": each by its own ``train()``;
         "device": all of a batch by one ``sysid.linear_fit.fit_linear_models`` call (one Gram pass on the device,
         equal configurations fitted once).
         linear_kstep: how the string metrics score linear models wider than 64 states -- "host": the loop over
         ``pred_batch``; "device": one ``ampc_kstep_errors_linear`` call per batch (``model_errors``).
+        sindy_kstep: how the string metrics score SINDy models -- "host": the loop over ``pred_batch``; "device":
+        one ``ampc_kstep_errors_sindy`` call per batch.
         ``last_kstep`` holds the ``KstepReport`` of the last ``evaluate_batch`` (``host_fallbacks``)."""
         if linear_fit not in ("host", "device"):
             raise ValueError("linear_fit must be 'host' or 'device'")
         if linear_kstep not in ("host", "device"):
             raise ValueError("linear_kstep must be 'host' or 'device'")
+        if sindy_kstep not in ("host", "device"):
+            raise ValueError("sindy_kstep must be 'host' or 'device'")
         self.linear_fit = linear_fit
         self.linear_kstep = linear_kstep
+        self.sindy_kstep = sindy_kstep
         self.last_kstep = None
         self.system = system
         self.trajs = trajs
@@ -45,10 +52,12 @@ class ModelEvaluator(ABC):
         if isinstance(metric, str):
             if metric == "rmse":
                 self.metric = lambda model, trajs: get_model_rmse(model, trajs, horizon=self.horizon,
-                                                                  linear_kstep=self.linear_kstep)
+                                                                  linear_kstep=self.linear_kstep,
+                                                                  sindy_kstep=self.sindy_kstep)
             elif metric == "rmsmens":
                 self.metric = lambda model, trajs: get_model_rmsmens(model, trajs, horiz=self.horizon,
-                                                                     linear_kstep=self.linear_kstep)
+                                                                     linear_kstep=self.linear_kstep,
+                                                                     sindy_kstep=self.sindy_kstep)
             else:
                 raise ValueError("metric must be one of %s or a callable, not %r" % (", ".join(METRICS), metric))
             self.metric_name = metric
@@ -86,5 +95,6 @@ class ModelEvaluator(ABC):
         if self.metric_name is not None:
             self.last_kstep = KstepReport()
             return model_errors(models, test_trajs, [self.horizon], self.metric_name,
-                                linear_kstep=self.linear_kstep, report=self.last_kstep)[:, 0]
+                                linear_kstep=self.linear_kstep, report=self.last_kstep,
+                                sindy_kstep=self.sindy_kstep)[:, 0]
         return np.array([float(self.metric(m, test_trajs)) for m in models])

@@ -12,6 +12,11 @@ models (``MLP``; ``ARX`` / ``Koopman`` of at most 64 states) are grouped by shap
 error sums of every horizon (csrc/kstep_kernels.hpp).  Every other model -- SINDy, wide linear models, any
 foreign ``Model`` -- takes the host fallback, the reference's own algorithm over ``model.pred_batch``.
 
+``sindy_kstep="device"`` (opt-in; the default ``"host"`` is the path above, bit for bit) scores ``SINDy`` models on
+the GPU: they are grouped by ``(precision, device, obs_dim, ctrl_dim)`` (``sindy_kstep_key``) and each group is ONE
+``ampc_kstep_errors_sindy`` call, whatever mix of feature libraries, coefficients and time modes it holds
+(csrc/kstep_sindy_kernels.hpp).  The state is the observation; the device step is ``pred_batch``'s own.
+
 ``linear_kstep="device"`` (opt-in; the default ``"host"`` is the path above, bit for bit) scores trained
 ``_LinearModel``s of 65..256 states on the GPU too: they are grouped by ``(precision, device, ctrl_dim)``
 (``wide_linear_key``) and each group is ONE ``ampc_kstep_errors_linear`` call, whatever mix of state dimensions it
@@ -46,18 +51,25 @@ _WIDE_MAX_LINEAR_STATES = 256           # ampc_set_linear / ampc_kstep_errors_li
 _WIDE_MAX_CTRLS = 16
 _LDS_BYTES = 160 * 1024
 LINEAR_KSTEP = ("host", "device")
+SINDY_KSTEP = ("host", "device")
+_SINDY_MAX_TAB = 160                    # kSindyMaxTab (csrc/sindy_kernels.hpp)
+_SINDY_STAGE_BYTES = 48 * 1024          # kSindyStageBytes
+_SINDY_ROWS, _SINDY_CHUNK, _SINDY_ERR_STRIDE = 64, 8, 65      # csrc/kstep_sindy_kernels.hpp
 
 
 class KstepReport:
     """What one ``model_errors`` call did: ``device_models`` scored by ``ampc_kstep_errors``, ``wide_models`` by
-    ``ampc_kstep_errors_linear`` in ``wide_calls`` calls, ``host_fallbacks`` by the host loop over ``pred_batch``."""
+    ``ampc_kstep_errors_linear`` in ``wide_calls`` calls, ``sindy_models`` by ``ampc_kstep_errors_sindy`` in
+    ``sindy_calls`` calls, ``host_fallbacks`` by the host loop over ``pred_batch``."""
 
     def __init__(self):
         self.device_models = self.wide_models = self.wide_calls = self.host_fallbacks = 0
+        self.sindy_models = self.sindy_calls = 0
 
     def __repr__(self):
-        return "KstepReport(device_models=%d, wide_models=%d, wide_calls=%d, host_fallbacks=%d)" % (
-            self.device_models, self.wide_models, self.wide_calls, self.host_fallbacks)
+        return ("KstepReport(device_models=%d, wide_models=%d, wide_calls=%d, sindy_models=%d, sindy_calls=%d, "
+                "host_fallbacks=%d)" % (self.device_models, self.wide_models, self.wide_calls, self.sindy_models,
+                                        self.sindy_calls, self.host_fallbacks))
 
 
 last_report = KstepReport()
@@ -275,6 +287,88 @@ def kstep_sums_linear(models, trajs, kmax, delta=False):
     return S, D
 
 
+# ---- SINDy models: the one-launch entry ------------------------------------------------------------------
+def sindy_program_sizes(model):
+    """(n_feat, n_trig, n_pow, n_mon, n_pool, n_tab) of the feature program ``ampc_set_sindy`` builds from the
+    model's library: the distinct sin / cos arguments and powers, one table entry per monomial and a constant 1;
+    ``n_tab == 0`` (and no table arrays) when the table would exceed ``kSindyMaxTab``: direct evaluation."""
+    kind, a0, a1, par, pair_var, _ = model.library
+    trig, pows, n_mon = set(), set(), 0
+    for k, a, b, p in zip(kind.tolist(), a0.tolist(), a1.tolist(), par.tolist()):
+        if 1 <= k <= 4:
+            trig.add((a if k <= 2 else b, p))
+        elif k == 5:
+            pows.add((a, p))
+        elif k == 6:
+            n_mon += 1
+    n_tab = 2 * len(trig) + len(pows) + n_mon + 1
+    if n_tab > _SINDY_MAX_TAB:
+        return len(kind), 0, 0, 0, len(pair_var), 0
+    return len(kind), len(trig), len(pows), n_mon, len(pair_var), n_tab
+
+
+def _sindy_lds_bytes(model, nx, nu, delta):
+    """kstep_sindy_lds_bytes (csrc/kstep_sindy_kernels.hpp) with sindy_stage_bytes (csrc/host_common.hpp)."""
+    esz = 8 if model.precision == "f64" else 4
+    n_feat, n_trig, n_pow, n_mon, n_pool, n_tab = sindy_program_sizes(model)
+    stage = 0
+    if n_tab > 0:
+        ints = 2 * n_feat + n_trig + n_pow + 2 * n_mon + 2 * n_pool
+        elems = n_feat * nx + n_trig + n_pow + (ints * 4 + esz - 1) // esz + 2
+        stage = elems * esz + 2 * esz if elems * esz <= _SINDY_STAGE_BYTES else 0
+    err = (2 if delta else 1) * _SINDY_CHUNK * _SINDY_ERR_STRIDE * 8
+    return (2 * nx + nu + n_tab) * _SINDY_ROWS * esz + err + stage
+
+
+def sindy_kstep_key(model, obs_dim=None, delta=False):
+    """Key of the SINDy models that share one ``ampc_kstep_errors_sindy`` call -- ("sindy", precision, device,
+    obs_dim, ctrl_dim): libraries, coefficients and time modes may differ -- or None: not a ``SINDy`` with the
+    class's own ``pred_batch`` and device staging, a system the entry does not take (``obs_dim`` is not the model's,
+    more than 64 states or 16 controls, a coefficient matrix of another shape), or per-thread columns that do not
+    fit LDS.  Needs no GPU."""
+    from ..sysid.sindy import SINDy
+    cls = type(model)
+    if not isinstance(model, SINDy) or cls.pred_batch is not SINDy.pred_batch:
+        return None
+    if cls._dev is not SINDy._dev or cls.stage_into is not SINDy.stage_into:
+        return None
+    s = model.system
+    no = s.obs_dim if obs_dim is None else int(obs_dim)
+    if no != s.obs_dim or not (1 <= no <= 64) or not (1 <= s.ctrl_dim <= _WIDE_MAX_CTRLS):
+        return None
+    n_feat = len(model.library[0])
+    if not (1 <= n_feat <= 4096) or np.shape(model.coefficients) != (no, n_feat):
+        return None
+    if model.precision not in ("f64", "f32"):
+        return None
+    if _sindy_lds_bytes(model, no, s.ctrl_dim, delta) > _LDS_BYTES:
+        return None
+    return ("sindy", model.precision, int(model.device), no, s.ctrl_dim)
+
+
+def kstep_sums_sindy(models, trajs, kmax, delta=False):
+    """(S [n_models][kmax], D or None) of SINDy models of ONE ``sindy_kstep_key``: one ``ampc_kstep_errors_sindy``
+    call."""
+    import ctypes
+    obs_dim = _obs_dim(trajs, models[0])
+    lens, obs, ctrls = _concat(trajs)
+    n = len(models)
+    handles = [m._dev() for m in models]
+    hp = (ctypes.c_void_p * n)(*[h._h.value for h in handles])
+    inv_std = None
+    if delta:
+        _, std = _increment_stats(trajs)
+        with np.errstate(divide="ignore"):
+            inv_std = np.ascontiguousarray(1.0 / std)
+    S = np.empty((n, kmax))
+    D = np.empty((n, kmax)) if delta else None
+    lib = handles[0].lib
+    _lib.check(lib.ampc_kstep_errors_sindy(hp, n, len(trajs), _lib.iptr(lens), obs_dim, _lib.dptr(obs),
+                                           _lib.dptr(ctrls), int(kmax), _lib.dptr(inv_std), _lib.dptr(S),
+                                           _lib.dptr(D)))
+    return S, D
+
+
 def _concat(trajs):
     lens = np.array([len(t) for t in trajs], dtype=np.int32)
     obs = np.ascontiguousarray(np.concatenate([np.asarray(t.obs, dtype=np.float64) for t in trajs]))
@@ -314,18 +408,21 @@ def row_counts(trajs, kmax):
     return np.array([np.maximum(lens - h, 0).sum() for h in range(1, kmax + 1)], dtype=np.float64)
 
 
-def model_errors(models, trajs, horizons, metric="rmse", linear_kstep="host", report=None):
+def model_errors(models, trajs, horizons, metric="rmse", linear_kstep="host", report=None, sindy_kstep="host"):
     """RMSE or RMSMENS of every model at every horizon: ndarray [len(models), len(horizons)] in input order
     (the data of a ``KstepPredAccGraph`` curve).  Device models are grouped by shape, one ``ampc_kstep_errors``
     call per group covering every horizon; the others take the host fallback (module docstring) -- except, with
     ``linear_kstep="device"``, the wide linear models: one ``ampc_kstep_errors_linear`` call per
-    ``wide_linear_key``.  ``report``: a ``KstepReport`` to fill (one is made otherwise; either way it becomes
+    ``wide_linear_key``, and, with ``sindy_kstep="device"``, the SINDy models: one ``ampc_kstep_errors_sindy`` call
+    per ``sindy_kstep_key``.  ``report``: a ``KstepReport`` to fill (one is made otherwise; either way it becomes
     ``model_metrics.last_report``)."""
     global last_report
     if metric not in METRICS:
         raise ValueError("metric must be one of %s, not %r" % (", ".join(METRICS), metric))
     if linear_kstep not in LINEAR_KSTEP:
         raise ValueError("linear_kstep must be 'host' or 'device'")
+    if sindy_kstep not in SINDY_KSTEP:
+        raise ValueError("sindy_kstep must be 'host' or 'device'")
     report = KstepReport() if report is None else report
     last_report = report
     models = list(models)
@@ -339,7 +436,7 @@ def model_errors(models, trajs, horizons, metric="rmse", linear_kstep="host", re
         for m in models:
             _check_rmsmens_model(m, obs_dim)
     delta = metric == "rmsmens"
-    groups, wide = {}, {}
+    groups, wide, sindy = {}, {}, {}
     for i, m in enumerate(models):
         key = device_shape_key(m) if trajs else None
         if key is not None:
@@ -349,15 +446,20 @@ def model_errors(models, trajs, horizons, metric="rmse", linear_kstep="host", re
             key = wide_linear_key(m, obs_dim, delta)
         if key is not None:
             wide.setdefault(key, []).append(i)
+            continue
+        if sindy_kstep == "device" and trajs:
+            key = sindy_kstep_key(m, obs_dim, delta)
+        if key is not None:
+            sindy.setdefault(key, []).append(i)
         else:
             host = host_rmse if metric == "rmse" else host_rmsmens
             out[i] = [host(m, trajs, h) for h in horizons]
             report.host_fallbacks += 1
-    if groups or wide:
+    if groups or wide or sindy:
         kmax = max(horizons)
         N = row_counts(trajs, kmax)
         hidx = np.array(horizons) - 1
-        for sums, grp in ((kstep_sums, groups), (kstep_sums_linear, wide)):
+        for sums, grp in ((kstep_sums, groups), (kstep_sums_linear, wide), (kstep_sums_sindy, sindy)):
             for idx in grp.values():
                 S, D = sums([models[i] for i in idx], trajs, kmax, delta=delta)
                 with np.errstate(divide="ignore", invalid="ignore"):
@@ -366,17 +468,22 @@ def model_errors(models, trajs, horizons, metric="rmse", linear_kstep="host", re
                 if grp is wide:
                     report.wide_models += len(idx)
                     report.wide_calls += 1
+                elif grp is sindy:
+                    report.sindy_models += len(idx)
+                    report.sindy_calls += 1
                 else:
                     report.device_models += len(idx)
     return out
 
 
-def get_model_rmse(model, trajs, horizon=1, linear_kstep="host"):
+def get_model_rmse(model, trajs, horizon=1, linear_kstep="host", sindy_kstep="host"):
     """Unnormalised RMSE at a fixed horizon (model_metrics.py:12-43); see the module docstring."""
-    return float(model_errors([model], trajs, [horizon], "rmse", linear_kstep=linear_kstep)[0, 0])
+    return float(model_errors([model], trajs, [horizon], "rmse", linear_kstep=linear_kstep,
+                              sindy_kstep=sindy_kstep)[0, 0])
 
 
-def get_model_rmsmens(model, trajs, horiz=1, linear_kstep="host"):
+def get_model_rmsmens(model, trajs, horiz=1, linear_kstep="host", sindy_kstep="host"):
     """Root mean squared model error, normalised step-wise (model_metrics.py:45-111); see the module
     docstring for the deviations from the reference."""
-    return float(model_errors([model], trajs, [horiz], "rmsmens", linear_kstep=linear_kstep)[0, 0])
+    return float(model_errors([model], trajs, [horiz], "rmsmens", linear_kstep=linear_kstep,
+                              sindy_kstep=sindy_kstep)[0, 0])

@@ -42,7 +42,7 @@ int ampc_version(void);   /* 100 * major + minor; 104: + ampc_mppi_run_legacy; 1
                            * 106: + ampc_ilqr_solve_queue_var, ampc_ilqr_closed_loop_var, ampc_set_indicator_costs,
                            *      ampc_mppi_plan_set_models, ampc_ilqr_plan_set_models; 107: + ampc_set_mlp_dev, ampc_ilqr_plan_set_constants;
                            * 108: + ampc_kstep_errors; 109: + ampc_lqr_*; 110: + ampc_linfit_fit;
-                           * 111: + ampc_kstep_errors_linear */
+                           * 111: + ampc_kstep_errors_linear; 112: + ampc_kstep_errors_sindy */
 int ampc_device_count(void);
 
 /* ---- handle ------------------------------------------------------------------------------ */
@@ -503,6 +503,18 @@ int ampc_kstep_errors_linear(ampc_handle* const* models, int n_models, int n_tra
                              const int* arx_history, const int* n_basis, const int* lift_kinds,
                              const double* lift_params, const double* const* init_rows, int kmax,
                              const double* inv_std, double* sq_err, double* sq_delta_err);
+
+/* ... of SINDy models (handles staged with ampc_set_sindy), any mix of feature libraries, coefficients and time
+ * modes in ONE launch (csrc/kstep_sindy_kernels.hpp): one thread per start point, 64-row tiles, grid (tiles, models).
+ * The models share precision, device, state dim and ctrl_dim; the state is the observation (obs_dim == state dim, no
+ * initial-state rows); data and outputs as ampc_kstep_errors.  Refused: handles without a SINDy model, mixed
+ * precision / device / state dim / ctrl_dim, obs_dim != state dim, and a model whose per-thread LDS columns
+ * ((2 nx + nu + table entries) x 64 rows) do not fit LDS with the error block.  A diverging model yields non-finite
+ * sums for itself only.  Deterministic: a model's sums do not depend on the other models of the call or on their
+ * order (fixed 64-row tiles, fixed-order f64 sums).  Synchronises. */
+int ampc_kstep_errors_sindy(ampc_handle* const* models, int n_models, int n_traj, const int* traj_len, int obs_dim,
+                            const double* obs, const double* ctrls, int kmax, const double* inv_std, double* sq_err,
+                            double* sq_delta_err);
 
 /* ---- least-squares model fits (f64 only) ---------------------------------------------------- */
 /* Fits ARX models (sysid/arx.py:62-116) and Koopman models of method "lstsq" (sysid/koopman.py:141-154) of ONE data
