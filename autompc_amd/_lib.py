@@ -117,6 +117,8 @@ SIGNATURES = {
     "ampc_lqr_closed_loop_scored": (c_int, [c_void_p, c_void_p, _dp, _dp, c_int, c_int, _ip, _dp, _dp, _dp, _dp]),
     "ampc_linfit_fit": (c_int, [c_int, c_int, _ip, c_int, c_int, _dp, _dp, c_int, _ip, c_int, _ip, _ip, _dp, _dp, _ip,
                                 _dp]),
+    "ampc_sindy_fit": (c_int, [c_int, c_int, _ip, c_int, c_int, _dp, _dp, _dp, c_int, _ip, _ip, _ip, _ip, _ip, _dp, _ip,
+                               _ip, c_int, _ip, _ip, _dp, c_double, c_int, _dp, _ip, _dp, _dp, _ip]),
 }
 
 
@@ -917,3 +919,49 @@ def linfit_fit(traj_len, obs, ctrls, arx_histories=(), koopman_bases=(), device=
     check(lib.ampc_linfit_fit(int(device), len(lens), iptr(lens), no, nu, dptr(obs), dptr(ctrls), n_arx, iptr(hist),
                               n_koop, iptr(nb), iptr(kinds), dptr(params), dptr(coeffs), iptr(status), dptr(pivot)))
     return [coeffs[off[i]:off[i + 1]].reshape(shapes[i]) for i in range(len(shapes))], status, pivot
+
+
+def sindy_fit(traj_len, obs, ctrls, designs, configs, ycont=None, alpha=0.05, max_iter=20, device=0):
+    """ampc_sindy_fit: sequentially-thresholded least-squares fits of SINDy configurations of one data set.
+    obs [R][nx], ctrls [R][nu]: the trajectories concatenated, traj_len their lengths; ycont: None or [R][nx], the
+    continuous-mode targets by data row.  designs: feature libraries, the ``(kind, a0, a1, par, pair_var, pair_exp)``
+    tuples of ``sysid.sindy.build_library``; configs: ``(design index, continuous, threshold)`` triples.  Returns
+    (coeffs, status, min_pivot, min_margin, iterations): a list of [nx][n_features] matrices and four
+    per-configuration arrays (status 0 fitted, 1 pivot rule, 2 threshold tie)."""
+    lib = load()
+    if lib.ampc_device_count() <= 0:
+        raise AmpcError("no HIP device visible: the MI355X path cannot run here "
+                        "(there is no CPU fallback by design)")
+    obs, ctrls = as_f64(obs), as_f64(ctrls)
+    nx, nu = obs.shape[1], ctrls.shape[1]
+    lens = np.ascontiguousarray(traj_len, dtype=np.int32)
+    if int(lens.sum()) != obs.shape[0] or obs.shape[0] != ctrls.shape[0]:
+        raise ValueError("traj_len does not add up to the rows of obs / ctrls")
+    if ycont is not None:
+        ycont = as_f64(ycont)
+        if ycont.shape != obs.shape:
+            raise ValueError("ycont must have the shape of obs")
+    i32 = lambda parts: np.ascontiguousarray(np.concatenate([np.asarray(p, dtype=np.int32).ravel() for p in parts]
+                                                            + [np.zeros(1, dtype=np.int32)]))
+    feat_off = np.concatenate([[0], np.cumsum([len(d[0]) for d in designs])]).astype(np.int32)
+    pair_off = np.concatenate([[0], np.cumsum([len(d[4]) for d in designs])]).astype(np.int32)
+    kind, a0, a1 = (i32([d[k] for d in designs]) for k in (0, 1, 2))
+    pvar, pexp = (i32([d[k] for d in designs]) for k in (4, 5))
+    par = as_f64(np.concatenate([np.asarray(d[3], dtype=np.float64).ravel() for d in designs] + [np.zeros(1)]))
+    cd = np.ascontiguousarray([c[0] for c in configs] + [0], dtype=np.int32)
+    cc = np.ascontiguousarray([1 if c[1] else 0 for c in configs] + [0], dtype=np.int32)
+    ct = as_f64([float(c[2]) for c in configs] + [0.0])
+    C = len(configs)
+    if C and (cd[:C].min() < 0 or cd[:C].max() >= len(designs)):
+        raise ValueError("a configuration names no design")
+    shapes = [(nx, int(feat_off[cd[i] + 1] - feat_off[cd[i]])) for i in range(C)]
+    off = np.concatenate([[0], np.cumsum([r * c for r, c in shapes])]).astype(np.int64)
+    coeffs = np.empty(int(off[-1]))
+    status = np.zeros(C, dtype=np.int32)
+    pivot, margin = np.empty(C), np.empty(C)
+    iters = np.zeros(C, dtype=np.int32)
+    check(lib.ampc_sindy_fit(int(device), len(lens), iptr(lens), nx, nu, dptr(obs), dptr(ctrls), dptr(ycont),
+                             len(designs), iptr(feat_off), iptr(pair_off), iptr(kind), iptr(a0), iptr(a1), dptr(par),
+                             iptr(pvar), iptr(pexp), C, iptr(cd), iptr(cc), dptr(ct), float(alpha), int(max_iter),
+                             dptr(coeffs), iptr(status), dptr(pivot), dptr(margin), iptr(iters)))
+    return [coeffs[off[i]:off[i + 1]].reshape(shapes[i]) for i in range(C)], status, pivot, margin, iters

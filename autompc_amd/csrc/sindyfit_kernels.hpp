@@ -1,0 +1,325 @@
+// sindyfit_kernels.hpp -- sequentially-thresholded least-squares (STLSQ) fits of SINDy models in f64 (what
+// sysid/sindy.py SINDy.train does on the host), many configurations per call.  The frame is linfit_kernels.hpp's.
+//
+// sindyfit_gram_kernel + sindyfit_gram_reduce_kernel: G = Theta' [Theta | Y_discrete | Y_continuous] of EVERY design
+// (feature library) of the call in one launch: the design is a grid dimension.  A design row is one data row t of a
+// trajectory that has a successor.  Its feature columns are the library's functions of [obs[t], ctrls[t]] (the seven
+// kinds of sindy_kernels.hpp, evaluated by sindy_feature / sindy_ipow as the prediction kernels do), its target
+// columns the next observation (discrete) and / or row t of an uploaded [R][nx] array (continuous: np.gradient of the
+// observations or the caller's xdot); only the target sets a configuration of the design asks for are formed.  Columns
+// are formed ON THE FLY by a per-column rule (SindyfitCol), sixteen rows at a time into LDS: the wide design matrix
+// never exists in HBM.  Accumulation on v_mfma_f64_16x16x4_f64, one accumulator per 16 x 16 tile; of Theta'Theta only
+// the tiles on and above the diagonal are computed (the reduction mirrors them).
+//
+// Determinism (linfit_kernels.hpp's contract).  Rows are split over workgroups by ROW INDEX only (kSindyfitSplitRows
+// consecutive data rows each); rows without a successor are dropped by a SELECT.  An entry's partial sum is one MFMA
+// accumulator's k-ordered chain over the split's rows, the partials are summed over splits in order by
+// sindyfit_gram_reduce_kernel.  No atomics: G[a][b] of two given columns has the same bits whatever other columns or
+// designs the call holds, and from run to run.
+//
+// sindyfit_solve_kernel: one workgroup per (configuration, target).  A configuration is (design, time mode,
+// threshold); alpha and max_iter belong to the call.  With keep = all features, every iteration gathers
+// G[keep, keep] + alpha I and G[keep, target], scales to unit diagonal (D = diag(G + alpha I)^-1/2), factors by the
+// right-looking blocked Cholesky of linfit_solve_kernel (panel in LDS, trailing matrix in global memory, the
+// right-hand side carried as an extra row), back-substitutes, and drops the kept features with |coef| < threshold;
+// it stops when nothing is dropped, nothing is kept or max_iter solves were made.  The result is where(keep, coef, 0)
+// of the last solve, as SINDy.train leaves it.
+// Per pair: bad = 1 when, in any solve, a diagonal entry or pivot is not positive and finite, a coefficient is not
+// finite, or the smallest squared pivot is below n_kept * 2^-26; the smallest squared pivot; the smallest threshold
+// margin | |coef| - threshold | / threshold over all solves and kept features; the number of solves.  The host folds
+// the pairs of a configuration in target order (status 1: bad, 2: margin below 2^-20).
+#ifndef AMPC_SINDYFIT_KERNELS_HPP
+#define AMPC_SINDYFIT_KERNELS_HPP
+#include <hip/hip_runtime.h>
+
+#include "sindy_kernels.hpp"
+
+namespace ampc {
+
+// the frame's constants, equal to linfit_kernels.hpp's (that header defines kernels, so it is not included here)
+constexpr int kSindyfitThreads = 256;
+constexpr int kSindyfitSplitRows = 512;   // data rows per workgroup of the Gram pass (a constant: see Determinism)
+constexpr int kSindyfitChunk = 16;        // design rows formed in LDS at a time
+constexpr int kSindyfitAcc = 8;           // tiles (accumulators) per wave
+constexpr int kSindyfitNb = 8, kSindyfitPs = kSindyfitNb + 1;   // Cholesky panel width, LDS row stride of the panel
+constexpr int kSindyfitMaxFeat = 272;     // features per design (kLinfitMaxFeat)
+typedef double sindyfit_d4 __attribute__((ext_vector_type(4)));
+constexpr int kSindyfitMaxState = 64, kSindyfitMaxCtrl = 16;
+// columns of a design: features + both target sets, padded to a tile; two per thread
+constexpr int kSindyfitMaxCols = (kSindyfitMaxFeat + 2 * kSindyfitMaxState + 15) / 16 * 16;
+constexpr int kSindyfitColsPerThread = (kSindyfitMaxCols + kSindyfitThreads - 1) / kSindyfitThreads;
+
+enum { SFC_NEXT_OBS = 7, SFC_YCONT = 8, SFC_ZERO = 9 };   // column kinds behind the library's SF_* kinds
+
+// How one column of [Theta | Y] is formed from a data row.
+struct SindyfitCol {
+  int kind;     // SF_ID .. SF_MONO: a library feature; SFC_NEXT_OBS: obs[t + 1][a0]; SFC_YCONT: ycont[t][a0]; SFC_ZERO
+  int a0, a1;   // variables (index into [obs | ctrls]); SF_MONO: first (variable, exponent) pair and their number
+  int pad;
+  double par;   // frequency / exponent
+};
+
+// One design.  Read field by field through a global pointer (uniform loads), as LinfitSolveDesc.
+struct SindyfitDesign {
+  const SindyfitCol* cols;    // [wp]
+  const int* pool;            // [n_pair][2] (variable, exponent >= 1) of the monomial features
+  const int* tiles;           // [n_tiles]: ti | tj << 16
+  double* part;               // [splits][nfp][wp]
+  double* G;                  // [nfp][wp]
+  int nf, w, wp, nfp, n_tiles, lds_stride;
+};
+
+struct SindyfitGramArgs {
+  const double* obs;          // [R][nx]
+  const double* ctrls;        // [R][nu]
+  const double* ycont;        // [R][nx] or nullptr (no design has continuous targets then)
+  const int* row_start;       // [R]: first row of the row's trajectory; -1: the row has no successor (no design row)
+  const SindyfitDesign* designs;
+  int R, nx, nu, splits;
+};
+
+__device__ inline double sindyfit_var(const SindyfitGramArgs& a, int g, int i) {
+  return i < a.nx ? a.obs[(size_t)g * a.nx + i] : a.ctrls[(size_t)g * a.nu + (i - a.nx)];
+}
+
+__device__ inline double sindyfit_value(const SindyfitGramArgs& a, const SindyfitCol c, const int* __restrict__ pool,
+                                        int g) {
+  if (c.kind == SFC_ZERO) return 0.0;
+  if (c.kind == SFC_NEXT_OBS) return a.obs[(size_t)(g + 1) * a.nx + c.a0];
+  if (c.kind == SFC_YCONT) return a.ycont[(size_t)g * a.nx + c.a0];
+  if (c.kind == SF_MONO) {
+    double val = 1.0;
+    for (int j = 0; j < c.a1; ++j)
+      val *= sindy_ipow<double>(sindyfit_var(a, g, pool[2 * (c.a0 + j)]), pool[2 * (c.a0 + j) + 1]);
+    return val;
+  }
+  return sindy_feature<double>(c.kind, sindyfit_var(a, g, c.a0), sindyfit_var(a, g, c.a1), c.par);
+}
+
+// grid (splits, tile groups, designs): workgroup (s, q, d) accumulates tiles 32 q .. 32 q + 31 of design d over data
+// rows kSindyfitSplitRows s ..; dynamic LDS: kSindyfitChunk * (largest lds_stride of the call) doubles.
+__global__ __launch_bounds__(kSindyfitThreads) void sindyfit_gram_kernel(const SindyfitGramArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double sindyfit_lds[];
+  const SindyfitDesign* d = a.designs + blockIdx.z;
+  const int n_tiles = d->n_tiles;
+  if ((int)blockIdx.y * 4 * kSindyfitAcc >= n_tiles) return;      // (uniform: a narrower design has fewer groups)
+  const int wp = d->wp, nfp = d->nfp, stride = d->lds_stride;
+  const SindyfitCol* __restrict__ cols = d->cols;
+  const int* __restrict__ pool = d->pool;
+  const int* __restrict__ tiles = d->tiles;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  int ti[kSindyfitAcc], tj[kSindyfitAcc];
+  sindyfit_d4 acc[kSindyfitAcc];
+#pragma unroll
+  for (int q = 0; q < kSindyfitAcc; ++q) {
+    const int id = ((int)blockIdx.y * 4 + wave) * kSindyfitAcc + q;
+    const int w = id < n_tiles ? tiles[id] : -1;
+    ti[q] = w < 0 ? -1 : (w & 0xffff);
+    tj[q] = w < 0 ? -1 : (w >> 16);
+    acc[q] = sindyfit_d4{0.0, 0.0, 0.0, 0.0};
+  }
+  SindyfitCol col[kSindyfitColsPerThread];
+#pragma unroll
+  for (int m = 0; m < kSindyfitColsPerThread; ++m) {
+    const int c = tid + m * kSindyfitThreads;
+    col[m] = c < wp ? cols[c] : SindyfitCol{SFC_ZERO, 0, 0, 0, 0.0};
+  }
+  const int row0 = (int)blockIdx.x * kSindyfitSplitRows;
+  const int rend = row0 + kSindyfitSplitRows < a.R ? row0 + kSindyfitSplitRows : a.R;
+  for (int c0 = row0; c0 < rend; c0 += kSindyfitChunk) {
+#pragma unroll
+    for (int m = 0; m < kSindyfitColsPerThread; ++m) {
+      const int c = tid + m * kSindyfitThreads;
+      if (c >= wp) continue;
+      for (int r = 0; r < kSindyfitChunk; ++r) {
+        const int g = c0 + r;
+        const int start = g < rend ? a.row_start[g] : -1;
+        // a row without a successor is dropped by a SELECT (its values are never formed)
+        sindyfit_lds[r * stride + c] = start < 0 ? 0.0 : sindyfit_value(a, col[m], pool, g);
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int ks = 0; ks < kSindyfitChunk / 4; ++ks) {
+      const double* rowp = sindyfit_lds + (4 * ks + (lane >> 4)) * stride + (lane & 15);
+#pragma unroll
+      for (int q = 0; q < kSindyfitAcc; ++q)
+        if (ti[q] >= 0)
+          acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(rowp[16 * ti[q]], rowp[16 * tj[q]], acc[q], 0, 0, 0);
+    }
+    __syncthreads();
+  }
+  double* part = d->part + (size_t)blockIdx.x * nfp * wp;
+#pragma unroll
+  for (int q = 0; q < kSindyfitAcc; ++q) {
+    if (ti[q] < 0) continue;
+#pragma unroll
+    for (int r = 0; r < 4; ++r)       // f64 16x16x4 result map: column lane & 15, row (lane >> 4) + 4 r
+      part[(size_t)(16 * ti[q] + (lane >> 4) + 4 * r) * wp + 16 * tj[q] + (lane & 15)] = acc[q][r];
+  }
+}
+
+// grid (blocks, designs): G[a][b] = sum over splits, in split order, of the partial tile entries; an entry below the
+// tile diagonal of the symmetric part is read from its mirror.  Entries with a >= nf or b >= w are not written.
+__global__ void sindyfit_gram_reduce_kernel(const SindyfitDesign* __restrict__ designs, int splits) {
+  const SindyfitDesign* d = designs + blockIdx.y;
+  const int nf = d->nf, w = d->w, wp = d->wp, nfp = d->nfp;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nf * w) return;
+  const double* __restrict__ part = d->part;
+  const int ra = i / w, cb = i - ra * w;
+  int sr = ra, sc = cb;
+  if (cb < nf && (cb >> 4) < (ra >> 4)) { sr = cb; sc = ra; }
+  double s = 0.0;
+  for (int k = 0; k < splits; ++k) s += part[((size_t)k * nfp + sr) * wp + sc];
+  d->G[(size_t)ra * wp + cb] = s;
+}
+
+// One (configuration, target) pair.  Read field by field through a global pointer (uniform loads).
+struct SindyfitSolveDesc {
+  int n, tcol, id, pad;       // features, the target's column of G, output slot (pair index)
+  const double* g;            // the design's Gram [.][ldg]
+  long long ldg;
+  long long ws;               // workspace offset (doubles): [n + 1][n]
+  long long out;              // coefficient offset (doubles): [n]
+  double threshold;
+};
+
+__global__ __launch_bounds__(kSindyfitThreads) void sindyfit_solve_kernel(
+    const SindyfitSolveDesc* __restrict__ descs, const int* __restrict__ order, double* ws, double* __restrict__ coef,
+    int* __restrict__ bad, double* __restrict__ min_pivot, double* __restrict__ min_margin, int* __restrict__ iters,
+    const double alpha, const int max_iter) {
+  __shared__ double P[(kSindyfitMaxFeat + 1) * kSindyfitPs];
+  __shared__ double dsc[kSindyfitMaxFeat];      // D
+  __shared__ double linv[kSindyfitMaxFeat];     // 1 / L[j][j]
+  __shared__ double cf[kSindyfitMaxFeat];       // coefficients of the last solve, by feature
+  __shared__ int kl[kSindyfitMaxFeat];          // kept features, in order
+  __shared__ int keep[kSindyfitMaxFeat];
+  __shared__ double s_min, s_solve_min, s_margin;
+  __shared__ int s_bad, s_nk, s_drop, s_iters;
+  constexpr int T = kSindyfitThreads, PS = kSindyfitPs;
+  const SindyfitSolveDesc* d = descs + order[blockIdx.x];
+  const int nf = d->n, tcol = d->tcol, id = d->id;
+  const double* __restrict__ G = d->g;
+  const size_t ldg = (size_t)d->ldg;
+  double* M = ws + d->ws;
+  double* out = coef + d->out;
+  const double thr = d->threshold;
+  const int t = threadIdx.x;
+  for (int i = t; i < nf; i += T) { keep[i] = 1; cf[i] = 0.0; }
+  if (t == 0) { s_bad = 0; s_min = __builtin_inf(); s_margin = __builtin_inf(); s_iters = 0; }
+  __syncthreads();
+  for (int it = 0; it < max_iter; ++it) {
+    if (t == 0) {
+      int nk = 0;
+      for (int i = 0; i < nf; ++i)
+        if (keep[i]) kl[nk++] = i;
+      s_nk = nk; s_drop = 0; s_solve_min = __builtin_inf();
+    }
+    __syncthreads();
+    const int n = s_nk, rows = n + 1;
+    if (n == 0) break;
+    for (int i = t; i < n; i += T) {
+      const double g = G[kl[i] * ldg + kl[i]] + alpha;
+      if (!(g > 0.0) || !isfinite(g)) { s_bad = 1; s_min = g; }
+      dsc[i] = 1.0 / sqrt(g);
+    }
+    __syncthreads();
+    if (s_bad) break;
+    for (int e = t; e < rows * n; e += T) {
+      const int r = e / n, c = e - r * n;
+      M[e] = r < n ? (G[kl[r] * ldg + kl[c]] + (r == c ? alpha : 0.0)) * dsc[r] * dsc[c]
+                   : G[kl[c] * ldg + tcol] * dsc[c];
+    }
+    __syncthreads();
+    for (int j0 = 0; j0 < n; j0 += kSindyfitNb) {
+      const int nbw = n - j0 < kSindyfitNb ? n - j0 : kSindyfitNb, pr = rows - j0;
+      for (int e = t; e < pr * nbw; e += T) {
+        const int r = e / nbw, c = e - r * nbw;
+        P[r * PS + c] = M[(size_t)(j0 + r) * n + j0 + c];
+      }
+      __syncthreads();
+      for (int jj = 0; jj < nbw; ++jj) {
+        if (t == 0) {
+          const double piv = P[jj * PS + jj];
+          if (!(piv > 0.0) || !isfinite(piv)) { s_bad = 1; s_min = piv; }
+          else {
+            if (piv < s_solve_min) s_solve_min = piv;
+            const double l = sqrt(piv);
+            P[jj * PS + jj] = l;
+            linv[j0 + jj] = 1.0 / l;
+          }
+        }
+        __syncthreads();
+        if (s_bad) break;
+        const double l = P[jj * PS + jj];
+        for (int r = jj + 1 + t; r < pr; r += T) P[r * PS + jj] /= l;
+        __syncthreads();
+        const int cw = nbw - jj - 1;
+        for (int e = t; e < (pr - jj - 1) * cw; e += T) {
+          const int r = jj + 1 + e / cw, c = jj + 1 + e % cw;
+          if (r >= c) P[r * PS + c] = fma(-P[r * PS + jj], P[c * PS + jj], P[r * PS + c]);
+        }
+        __syncthreads();
+      }
+      if (s_bad) break;
+      for (int e = t; e < pr * nbw; e += T) {
+        const int r = e / nbw, c = e - r * nbw;
+        M[(size_t)(j0 + r) * n + j0 + c] = P[r * PS + c];
+      }
+      const int c1 = j0 + nbw, w = n - c1, h = rows - c1;
+      for (int e = t; e < h * w; e += T) {
+        const int r = c1 + e / w, c = c1 + e % w;
+        if (r < c) continue;
+        double v = M[(size_t)r * n + c];
+        for (int q = 0; q < nbw; ++q) v = fma(-P[(r - j0) * PS + q], P[(c - j0) * PS + q], v);
+        M[(size_t)r * n + c] = v;
+      }
+      __syncthreads();
+    }
+    if (s_bad) break;
+    // row n holds y = L^-1 (D g_t); back substitution L' z = y by columns, z_j = y_j / L[j][j]
+    double* y = M + (size_t)n * n;
+    for (int j = n - 1; j > 0; --j) {
+      const double yj = y[j] * linv[j];
+      for (int i = t; i < j; i += T) y[i] = fma(-M[(size_t)j * n + i], yj, y[i]);
+      __syncthreads();
+    }
+    for (int i = t; i < nf; i += T) cf[i] = 0.0;
+    __syncthreads();
+    if (t == 0) {
+      if (s_solve_min < s_min) s_min = s_solve_min;
+      if (s_solve_min < (double)n * 0x1p-26) s_bad = 1;
+      s_iters = it + 1;
+    }
+    // the kept features' coefficients, their threshold margins, and who is dropped (one thread per feature writes
+    // its own entries; the minimum is folded by thread 0 in feature order)
+    for (int c = t; c < n; c += T) {
+      const double v = y[c] * linv[c] * dsc[c];
+      cf[kl[c]] = v;
+      if (!isfinite(v)) s_bad = 1;
+      dsc[c] = thr > 0.0 ? fabs(fabs(v) - thr) / thr : __builtin_inf();     // (dsc is free again: the margins)
+      if (fabs(v) < thr) { keep[kl[c]] = 0; s_drop = 1; }
+    }
+    __syncthreads();
+    if (t == 0)
+      for (int c = 0; c < n; ++c)
+        if (dsc[c] < s_margin) s_margin = dsc[c];
+    __syncthreads();
+    const bool stop = s_bad || !s_drop;
+    __syncthreads();                    // (thread 0 resets s_drop at the top of the next iteration)
+    if (stop) break;
+  }
+  __syncthreads();
+  for (int i = t; i < nf; i += T) out[i] = s_bad ? __builtin_nan("") : (keep[i] ? cf[i] : 0.0);
+  if (t == 0) {
+    bad[id] = s_bad;
+    min_pivot[id] = s_min;
+    min_margin[id] = s_margin;
+    iters[id] = s_iters;
+  }
+}
+
+}  // namespace ampc
+#endif

@@ -5,7 +5,8 @@ autompc/evaluation/evaluator.py, holdout_evaluator.py).
 ``evaluator.evaluate_batch(factory, cfgs)`` is the batched form the tuner uses: every model is built with
 ``skip_train_model=True``, the MLPs are fitted together by one ``sysid.mlp_fit.fit_mlps`` call (lockstep,
 each model exactly as its own ``train()``), the others are trained one by one -- or, with ``linear_fit="device"``,
-the ARX / Koopman models by one ``sysid.linear_fit.fit_linear_models`` call -- and all are scored by
+the ARX / Koopman models by one ``sysid.linear_fit.fit_linear_models`` call, with ``sindy_fit="device"`` the SINDy
+models by one ``sysid.sindy_fit.fit_sindy_models`` call -- and all are scored by
 ``model_errors`` (one k-step kernel call per model shape; with ``linear_kstep="device"`` the ARX / Koopman models
 wider than 64 states too, all of them in one ``ampc_kstep_errors_linear`` call, instead of the host loop; with
 ``sindy_kstep="device"`` the SINDy models in one ``ampc_kstep_errors_sindy`` call).
@@ -26,7 +27,7 @@ class ModelEvaluator(ABC):
     ``(model, [Trajectory]) -> float``."""
 
     def __init__(self, system, trajs, metric, rng, horizon=1, linear_fit="host", linear_kstep="host",
-                 sindy_kstep="host"):
+                 sindy_kstep="host", sindy_fit="host"):
         """linear_fit: how ``evaluate_batch`` fits ARX / Koopman models -- "host": each by its own ``train()``;
         "device": all of a batch by one ``sysid.linear_fit.fit_linear_models`` call (one Gram pass on the device,
         equal configurations fitted once).
@@ -34,6 +35,9 @@ class ModelEvaluator(ABC):
         ``pred_batch``; "device": one ``ampc_kstep_errors_linear`` call per batch (``model_errors``).
         sindy_kstep: how the string metrics score SINDy models -- "host": the loop over ``pred_batch``; "device":
         one ``ampc_kstep_errors_sindy`` call per batch.
+        sindy_fit: how ``evaluate_batch`` fits SINDy models -- "host": each by its own ``train()``; "device": all of
+        a batch by one ``sysid.sindy_fit.fit_sindy_models`` call (one Gram launch, equal configurations fitted once);
+        ``last_sindy_fit`` holds its ``SindyFitReport``.
         ``last_kstep`` holds the ``KstepReport`` of the last ``evaluate_batch`` (``host_fallbacks``)."""
         if linear_fit not in ("host", "device"):
             raise ValueError("linear_fit must be 'host' or 'device'")
@@ -41,7 +45,11 @@ class ModelEvaluator(ABC):
             raise ValueError("linear_kstep must be 'host' or 'device'")
         if sindy_kstep not in ("host", "device"):
             raise ValueError("sindy_kstep must be 'host' or 'device'")
+        if sindy_fit not in ("host", "device"):
+            raise ValueError("sindy_fit must be 'host' or 'device'")
         self.linear_fit = linear_fit
+        self.sindy_fit = sindy_fit
+        self.last_sindy_fit = None
         self.linear_kstep = linear_kstep
         self.sindy_kstep = sindy_kstep
         self.last_kstep = None
@@ -90,6 +98,13 @@ class ModelEvaluator(ABC):
             if linear:
                 self.last_linear_fit = fit_linear_models(linear, train_trajs)
             others = [m for m in others if not isinstance(m, (ARX, Koopman))]
+        if self.sindy_fit == "device":
+            from ..sysid.sindy import SINDy
+            from ..sysid.sindy_fit import fit_sindy_models
+            sindys = [m for m in others if isinstance(m, SINDy)]
+            if sindys:
+                self.last_sindy_fit = fit_sindy_models(sindys, train_trajs)
+            others = [m for m in others if not isinstance(m, SINDy)]
         for m in others:
             m.train(train_trajs, silent=True)
         if self.metric_name is not None:

@@ -45,7 +45,7 @@ class BatchPipelineTuner:
 
     def __init__(self, system, evaluator, batch_size=64, sampler=None, truedyn_noise="device",
                  eval_kwargs=None, keep_trajs=False, balance=None, models=None, model_factory=None,
-                 trajs=None, as_configs=False, linear_fit="host"):
+                 trajs=None, as_configs=False, linear_fit="host", sindy_fit="host"):
         """truedyn_noise: the noise mode of the controllers scored against the true dynamics
         (MPPI(noise=...): "device" Philox, or "numpy" / "numpy_device" = the reference's global
         legacy stream).  eval_kwargs: extra keyword arguments for every ``evaluator.evaluate`` call
@@ -64,6 +64,9 @@ class BatchPipelineTuner:
         linear_fit: "host" fits every ARX / Koopman configuration by its own ``train()``; "device" fits all fresh
         ones of a shard by one ``sysid.linear_fit.fit_linear_models`` call (one Gram pass on the device);
         ``linear_host_fits`` counts the models that call handed back to ``train()``.
+
+        sindy_fit: the same for SINDy configurations ("device": one ``sysid.sindy_fit.fit_sindy_models`` call per
+        shard); ``sindy_host_fits`` counts the ``train()`` calls it made.
 
         as_configs: report ``cfgs`` / ``inc_cfg`` as pipeline configurations with the reference's key names
         (`_ctrlr:horizon`, `_cost:<obs>_Q`, `_model:lr`, ...; tuning/configs.py) instead of candidate dicts;
@@ -99,6 +102,10 @@ class BatchPipelineTuner:
             raise ValueError("linear_fit must be 'host' or 'device'")
         self.linear_fit = linear_fit
         self.linear_host_fits = 0
+        if sindy_fit not in ("host", "device"):
+            raise ValueError("sindy_fit must be 'host' or 'device'")
+        self.sindy_fit = sindy_fit
+        self.sindy_host_fits = 0
         self.batch_size = int(batch_size)
         if self.batch_size < 1:
             raise ValueError("batch_size must be >= 1")
@@ -189,6 +196,13 @@ class BatchPipelineTuner:
                 if linear:
                     self.linear_host_fits += fit_linear_models(linear, self.trajs).host_fits
                 others = [m for m in others if not isinstance(m, (ARX, Koopman))]
+            if self.sindy_fit == "device":
+                from ..sysid.sindy import SINDy
+                from ..sysid.sindy_fit import fit_sindy_models
+                sindys = [m for m in others if isinstance(m, SINDy)]
+                if sindys:
+                    self.sindy_host_fits += fit_sindy_models(sindys, self.trajs).host_fits
+                others = [m for m in others if not isinstance(m, SINDy)]
             for m in others:
                 m.train(self.trajs, silent=True)
             self._fitted.update(fresh)

@@ -42,7 +42,8 @@ int ampc_version(void);   /* 100 * major + minor; 104: + ampc_mppi_run_legacy; 1
                            * 106: + ampc_ilqr_solve_queue_var, ampc_ilqr_closed_loop_var, ampc_set_indicator_costs,
                            *      ampc_mppi_plan_set_models, ampc_ilqr_plan_set_models; 107: + ampc_set_mlp_dev, ampc_ilqr_plan_set_constants;
                            * 108: + ampc_kstep_errors; 109: + ampc_lqr_*; 110: + ampc_linfit_fit;
-                           * 111: + ampc_kstep_errors_linear; 112: + ampc_kstep_errors_sindy */
+                           * 111: + ampc_kstep_errors_linear; 112: + ampc_kstep_errors_sindy;
+                           * 113: + ampc_sindy_fit */
 int ampc_device_count(void);
 
 /* ---- handle ------------------------------------------------------------------------------ */
@@ -535,6 +536,35 @@ int ampc_linfit_fit(int device, int n_traj, const int* traj_len, int obs_dim, in
                     const double* ctrls, int n_arx, const int* arx_history, int n_koopman,
                     const int* koopman_n_basis, const int* koopman_kinds, const double* koopman_params,
                     double* coeffs, int* status, double* min_pivot);
+
+/* Sequentially-thresholded least-squares (STLSQ) fits of SINDy configurations of ONE data set in one call: what
+ * sysid/sindy.py SINDy.train does per model (ridge normal equations on the kept features, features with
+ * |coefficient| < threshold dropped, at most max_iter solves per target).  Data as ampc_linfit_fit (obs_dim 1..64,
+ * ctrl_dim 1..16); a design row is row t of a trajectory with a successor, its variables [obs[t], ctrls[t]].
+ * ycont: NULL or [sum len][obs_dim], the continuous-mode targets by data row (row t's derivative; rows without a
+ * successor are not read as targets); the discrete target of row t is obs[t + 1].
+ * Designs (distinct feature libraries): design d owns features feat_off[d] .. feat_off[d + 1] of kind / a0 / a1 / par
+ * (the arrays of ampc_set_sindy: kinds 0 identity, 1 sin, 2 cos, 3 x sin(f y), 4 x cos(f y), 5 power, 6 monomial; at
+ * most 272 features) and pairs pair_off[d] .. pair_off[d + 1] of pair_var / pair_exp; a monomial's a0 counts from
+ * its own design's first pair.  feat_off / pair_off hold n_designs + 1 entries and start at 0.
+ * Configurations: cfg_design, cfg_continuous (0: discrete targets, 1: ycont), cfg_threshold [n_configs]; alpha (the
+ * ridge term) and max_iter (>= 1) hold for the call.  All Grams Theta'[Theta | Y] are formed by one launch, each
+ * (configuration, target) is then solved by one workgroup on sub-matrices of its design's Gram.
+ * Outputs per configuration, in order: coeffs packed [obs_dim][n_features of its design]; status: 0 fitted, 1 not
+ * fitted here (in some solve of some target a diagonal entry or pivot of the unit-diagonal matrix was not positive
+ * and finite, a coefficient was not finite, or the smallest squared pivot was below n_kept * 2^-26), 2 threshold tie
+ * (some kept coefficient of some solve had | |coef| - threshold | / threshold < 2^-20: keep / drop could go either
+ * way at rounding level; fit that model on the host); min_pivot: smallest squared pivot of all its solves;
+ * min_margin: smallest such threshold margin; iterations: the largest number of solves any of its targets took.
+ * Refused: sizes over the limits, max_iter < 1, a continuous configuration with ycont == NULL.  Deterministic: a
+ * configuration's result does not depend on the other configurations or designs of the call or on their order.
+ * Synchronises. */
+int ampc_sindy_fit(int device, int n_traj, const int* traj_len, int obs_dim, int ctrl_dim, const double* obs,
+                   const double* ctrls, const double* ycont, int n_designs, const int* feat_off, const int* pair_off,
+                   const int* kind, const int* a0, const int* a1, const double* par, const int* pair_var,
+                   const int* pair_exp, int n_configs, const int* cfg_design, const int* cfg_continuous,
+                   const double* cfg_threshold, double alpha, int max_iter, double* coeffs, int* status,
+                   double* min_pivot, double* min_margin, int* iterations);
 
 /* ---- finite-horizon LQR (f64 only) ---------------------------------------------------------- */
 /* A plan of n_problems LQR controllers (reference: autompc/control/lqr.py:139-192 FiniteHorizonLQR) that keeps
