@@ -119,6 +119,8 @@ SIGNATURES = {
                                 _dp]),
     "ampc_sindy_fit": (c_int, [c_int, c_int, _ip, c_int, c_int, _dp, _dp, _dp, c_int, _ip, _ip, _ip, _ip, _ip, _dp, _ip,
                                _ip, c_int, _ip, _ip, _dp, c_double, c_int, _dp, _ip, _dp, _dp, _ip]),
+    "ampc_lasso_fit": (c_int, [c_int, c_int, _ip, c_int, c_int, _dp, _dp, c_int, _ip, _ip, _dp, c_int, _ip, _dp,
+                               c_double, c_double, _dp, _ip, _dp, _ip]),
 }
 
 
@@ -965,3 +967,41 @@ def sindy_fit(traj_len, obs, ctrls, designs, configs, ycont=None, alpha=0.05, ma
                              iptr(pvar), iptr(pexp), C, iptr(cd), iptr(cc), dptr(ct), float(alpha), int(max_iter),
                              dptr(coeffs), iptr(status), dptr(pivot), dptr(margin), iptr(iters)))
     return [coeffs[off[i]:off[i + 1]].reshape(shapes[i]) for i in range(C)], status, pivot, margin, iters
+
+
+def lasso_fit(traj_len, obs, ctrls, bases, configs, tie=None, ratio_tie=None, device=0):
+    """ampc_lasso_fit: lasso fits of Koopman configurations of one data set by coordinate descent on the Gram.
+    obs [R][no], ctrls [R][nu]: the trajectories concatenated, traj_len their lengths.  bases: (kinds, params) pairs;
+    configs: (basis index, lasso_alpha) pairs.  tie / ratio_tie: the margins below which a stopping decision is a tie
+    (None: ``sysid.lasso_fit.TIE`` / ``RATIO_TIE``).  Returns (coeffs, status, min_margin, sweeps): a list of
+    [n][n + nu] matrices and three per-configuration arrays (status 0 fitted, 1 not fitted here, 2 tie; min_margin
+    [.][2]: gap margin, sweep-test margin; sweeps: the largest over the targets)."""
+    from .sysid.lasso_fit import RATIO_TIE, TIE
+    lib = load()
+    if lib.ampc_device_count() <= 0:
+        raise AmpcError("no HIP device visible: the MI355X path cannot run here "
+                        "(there is no CPU fallback by design)")
+    obs, ctrls = as_f64(obs), as_f64(ctrls)
+    no, nu = obs.shape[1], ctrls.shape[1]
+    lens = np.ascontiguousarray(traj_len, dtype=np.int32)
+    if int(lens.sum()) != obs.shape[0] or obs.shape[0] != ctrls.shape[0]:
+        raise ValueError("traj_len does not add up to the rows of obs / ctrls")
+    nb = np.array([len(k) for k, _ in bases] + [0], dtype=np.int32)
+    kinds = np.array([int(v) for k, _ in bases for v in k] + [0], dtype=np.int32)
+    params = np.array([float(v) for _, p in bases for v in p] + [0.0])
+    C = len(configs)
+    cb = np.ascontiguousarray([int(c[0]) for c in configs] + [0], dtype=np.int32)
+    ca = as_f64([float(c[1]) for c in configs] + [0.0])
+    if C and (cb[:C].min() < 0 or cb[:C].max() >= len(bases)):
+        raise ValueError("a configuration names no basis")
+    shapes = [(int(nb[cb[i]]) * no, int(nb[cb[i]]) * no + nu) for i in range(C)]
+    off = np.concatenate([[0], np.cumsum([r * c for r, c in shapes])]).astype(np.int64)
+    coeffs = np.empty(int(off[-1]))
+    status = np.zeros(C, dtype=np.int32)
+    margin = np.empty((C, 2))
+    sweeps = np.zeros(C, dtype=np.int32)
+    check(lib.ampc_lasso_fit(int(device), len(lens), iptr(lens), no, nu, dptr(obs), dptr(ctrls), len(bases), iptr(nb),
+                             iptr(kinds), dptr(params), C, iptr(cb), dptr(ca), float(TIE if tie is None else tie),
+                             float(RATIO_TIE if ratio_tie is None else ratio_tie), dptr(coeffs), iptr(status),
+                             dptr(margin), iptr(sweeps)))
+    return [coeffs[off[i]:off[i + 1]].reshape(shapes[i]) for i in range(C)], status, margin, sweeps

@@ -25,7 +25,7 @@ extern template int ilqr_launch_iter<double>(ampc_ilqr_plan*, int);
 extern template int ilqr_launch_iter<float>(ampc_ilqr_plan*, int);
 
 extern "C" const char* ampc_last_error(void) { return g_err.c_str(); }
-extern "C" int ampc_version(void) { return 113; }   // 1.13: ampc_sindy_fit; 1.12: ampc_kstep_errors_sindy; 1.11: ampc_kstep_errors_linear; 1.10: ampc_linfit_fit; 1.09: ampc_lqr_*; 1.08: ampc_kstep_errors; 1.07: round 6 (ampc_set_mlp_dev, ampc_ilqr_plan_set_constants); 1.06: round 5 (ampc_ilqr_*_var); 1.04: round 3 (ampc_set_sindy monomial pair list; ampc_mppi_run_legacy)
+extern "C" int ampc_version(void) { return 114; }   // 1.14: ampc_lasso_fit; 1.13: ampc_sindy_fit; 1.12: ampc_kstep_errors_sindy; 1.11: ampc_kstep_errors_linear; 1.10: ampc_linfit_fit; 1.09: ampc_lqr_*; 1.08: ampc_kstep_errors; 1.07: round 6 (ampc_set_mlp_dev, ampc_ilqr_plan_set_constants); 1.06: round 5 (ampc_ilqr_*_var); 1.04: round 3 (ampc_set_sindy monomial pair list; ampc_mppi_run_legacy)
 extern "C" int ampc_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;

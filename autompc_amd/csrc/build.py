@@ -1,8 +1,8 @@
 """Build libautompc_hip.so for gfx950 with hipcc (cross-compiles without a GPU).
 
-Twenty-two translation units compiled in parallel and linked into one shared library: api.cpp +
-api_{model,mppi,ilqr,lqr,linfit,sindyfit}.cpp (the C ABI and host logic by family), launch_{mlp,mppi,ilqr,kstep,kstep_linear,kstep_sindy}.cpp
-once per precision (-DAMPC_T=double|float), launch_lqr.cpp, launch_linfit.cpp and launch_sindyfit.cpp (f64 only).
+Twenty-four translation units compiled in parallel and linked into one shared library: api.cpp +
+api_{model,mppi,ilqr,lqr,linfit,sindyfit,lasso}.cpp (the C ABI and host logic by family), launch_{mlp,mppi,ilqr,kstep,kstep_linear,kstep_sindy}.cpp
+once per precision (-DAMPC_T=double|float), launch_lqr.cpp, launch_linfit.cpp, launch_sindyfit.cpp and launch_lasso.cpp (f64 only).
 """
 import concurrent.futures
 import os
@@ -29,7 +29,9 @@ UNITS = [("api", "api.cpp", []), ("api_model", "api_model.cpp", []), ("api_mppi"
     ("api_linfit", "api_linfit.cpp", []),
     ("linfit_double", "launch_linfit.cpp", ["-DAMPC_T=double", "-DAMPC_T_IS_F64=1"]),
     ("api_sindyfit", "api_sindyfit.cpp", []),
-    ("sindyfit_double", "launch_sindyfit.cpp", ["-DAMPC_T=double", "-DAMPC_T_IS_F64=1"])]
+    ("sindyfit_double", "launch_sindyfit.cpp", ["-DAMPC_T=double", "-DAMPC_T_IS_F64=1"]),
+    ("api_lasso", "api_lasso.cpp", []),
+    ("lasso_double", "launch_lasso.cpp", ["-DAMPC_T=double", "-DAMPC_T_IS_F64=1"])]
 SOURCES = sorted({u[1] for u in UNITS})
 
 

@@ -23,11 +23,10 @@ void linfit_pack_desc(void* dst, int n, int nt, int tcol, int id, const double* 
 // fall on two disjoint halves of the banks
 static int linfit_stride(int wp) { return (wp / 16) % 2 ? wp : wp + 16; }
 
-// Gram of one design: partial tiles, then the ordered sum.  part holds splits * nfp * wp doubles, G nfp * wp.
-int linfit_launch_gram(hipStream_t st, int R, int no, int nu, const void* obs, const void* ctrls,
-                       const void* row_start, const void* cols, const void* prog, const void* tiles, int n_tiles,
-                       int nf, int nt, void* part, void* G) {
-  const int wp = (nf + nt + 15) / 16 * 16, nfp = (nf + 15) / 16 * 16;
+// Partial tiles of one design's Gram: part holds splits * nfp * wp doubles (tile rows up to nfp / 16).
+int linfit_launch_gram_part(hipStream_t st, int R, int no, int nu, const void* obs, const void* ctrls,
+                            const void* row_start, const void* cols, const void* prog, const void* tiles, int n_tiles,
+                            int wp, int nfp, void* part) {
   const int splits = (R + kLinfitSplitRows - 1) / kLinfitSplitRows;
   LinfitGramArgs a{};
   a.obs = (const double*)obs; a.ctrls = (const double*)ctrls; a.row_start = (const int*)row_start;
@@ -40,6 +39,17 @@ int linfit_launch_gram(hipStream_t st, int R, int no, int nu, const void* obs, c
   const int groups = (n_tiles + 4 * kLinfitAcc - 1) / (4 * kLinfitAcc);
   hipLaunchKernelGGL(linfit_gram_kernel, dim3(splits, groups), dim3(kLinfitThreads), lds, st, a);
   HIP_OK(hipGetLastError());
+  return 0;
+}
+
+// Gram of one design: partial tiles, then the ordered sum.  part holds splits * nfp * wp doubles, G nfp * wp.
+int linfit_launch_gram(hipStream_t st, int R, int no, int nu, const void* obs, const void* ctrls,
+                       const void* row_start, const void* cols, const void* prog, const void* tiles, int n_tiles,
+                       int nf, int nt, void* part, void* G) {
+  const int wp = (nf + nt + 15) / 16 * 16, nfp = (nf + 15) / 16 * 16;
+  const int splits = (R + kLinfitSplitRows - 1) / kLinfitSplitRows;
+  if (int rc = linfit_launch_gram_part(st, R, no, nu, obs, ctrls, row_start, cols, prog, tiles, n_tiles, wp, nfp, part))
+    return rc;
   const int w = nf + nt;
   hipLaunchKernelGGL(linfit_gram_reduce_kernel, dim3((nf * w + 255) / 256), dim3(256), 0, st, (const double*)part,
                      (double*)G, splits, nf, w, nfp, wp);

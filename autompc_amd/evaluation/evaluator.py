@@ -27,7 +27,7 @@ class ModelEvaluator(ABC):
     ``(model, [Trajectory]) -> float``."""
 
     def __init__(self, system, trajs, metric, rng, horizon=1, linear_fit="host", linear_kstep="host",
-                 sindy_kstep="host", sindy_fit="host"):
+                 sindy_kstep="host", sindy_fit="host", lasso_fit="host"):
         """linear_fit: how ``evaluate_batch`` fits ARX / Koopman models -- "host": each by its own ``train()``;
         "device": all of a batch by one ``sysid.linear_fit.fit_linear_models`` call (one Gram pass on the device,
         equal configurations fitted once).
@@ -38,6 +38,8 @@ class ModelEvaluator(ABC):
         sindy_fit: how ``evaluate_batch`` fits SINDy models -- "host": each by its own ``train()``; "device": all of
         a batch by one ``sysid.sindy_fit.fit_sindy_models`` call (one Gram launch, equal configurations fitted once);
         ``last_sindy_fit`` holds its ``SindyFitReport``.
+        lasso_fit: with ``linear_fit="device"``, how that call fits Koopman models of method "lasso" -- "host": each
+        by its own ``train()``; "device": by ``ampc_lasso_fit`` (``fit_linear_models(..., lasso="device")``).
         ``last_kstep`` holds the ``KstepReport`` of the last ``evaluate_batch`` (``host_fallbacks``)."""
         if linear_fit not in ("host", "device"):
             raise ValueError("linear_fit must be 'host' or 'device'")
@@ -47,7 +49,10 @@ class ModelEvaluator(ABC):
             raise ValueError("sindy_kstep must be 'host' or 'device'")
         if sindy_fit not in ("host", "device"):
             raise ValueError("sindy_fit must be 'host' or 'device'")
+        if lasso_fit not in ("host", "device"):
+            raise ValueError("lasso_fit must be 'host' or 'device'")
         self.linear_fit = linear_fit
+        self.lasso_fit = lasso_fit
         self.sindy_fit = sindy_fit
         self.last_sindy_fit = None
         self.linear_kstep = linear_kstep
@@ -96,7 +101,7 @@ class ModelEvaluator(ABC):
             from ..sysid.linear_fit import fit_linear_models
             linear = [m for m in others if isinstance(m, (ARX, Koopman))]
             if linear:
-                self.last_linear_fit = fit_linear_models(linear, train_trajs)
+                self.last_linear_fit = fit_linear_models(linear, train_trajs, lasso=self.lasso_fit)
             others = [m for m in others if not isinstance(m, (ARX, Koopman))]
         if self.sindy_fit == "device":
             from ..sysid.sindy import SINDy

@@ -20,6 +20,14 @@ pseudo-inverse cutoff makes of singular values at rounding level), and models ov
 16 controls).  Every model ends up exactly as after its own ``train(trajs)``: ARX through ``_set_coeffs``, Koopman
 through ``_set_matrices``.
 
+Lasso.  With ``lasso="device"`` Koopman models of ``method="lasso"`` take a Gram route of their own
+(``sysid/lasso_fit.py``, ``ampc_lasso_fit``: sklearn's cyclic coordinate descent run on the centred Gram of
+``[1 | F | Y]``, one Gram per distinct basis whatever the alphas).  Duplicate basis functions are allowed there
+(coordinate descent is well defined on them); product terms and over-size models still go to ``train()``, and so do
+configurations that come back with status 1 (centring lost half the digits of a column, or a non-finite value) or
+status 2 (a stopping decision too close to call).  The default ``lasso="host"`` leaves every lasso model to
+``train()``, as before.
+
 ``gram_fit_host`` is the same algorithm in numpy (what the CPU tests run and the GPU tests compare against first).
 """
 import numpy as np
@@ -167,7 +175,7 @@ def gram_fit_host(traj_len, obs, ctrls, arx_histories=(), koopman_bases=(), orde
 
 class LinearFitReport(list):
     """One entry per model, in order: ``{"where": "device" | "host", "reason": None | str, "pivot": float |
-    None}``.  ``host_fits``: the ``train()`` calls that were made (equal configurations share one)."""
+    None}``; models that took the lasso route also carry ``"sweeps"`` and ``"margin"``.  ``host_fits``: the ``train()`` calls that were made (equal configurations share one)."""
     host_fits = 0
     device_fits = 0
 
@@ -178,18 +186,19 @@ def _config_key(m):
     return ("koopman", m.method, m.lasso_alpha, tuple(m.basis), m.product_terms)
 
 
-def _host_reason(m):
-    """Why a model cannot take the Gram route (None: it can)."""
+def _host_reason(m, lasso="host"):
+    """Why a model cannot take a Gram route (None: it can)."""
     no, nu = m.system.obs_dim, m.system.ctrl_dim
     if nu > MAX_CTRL or no > MAX_STATE:
         return "size"
     if isinstance(m, ARX):
         return "size" if m.state_dim > MAX_STATE else None
-    if m.method != "lstsq":
+    on_lasso_route = lasso == "device" and m.method == "lasso" and m.lasso_alpha is not None
+    if m.method != "lstsq" and not on_lasso_route:
         return "method"
     if m.product_terms:
         return "product_terms"
-    if len(set(m.basis)) != len(m.basis):
+    if len(set(m.basis)) != len(m.basis) and not on_lasso_route:
         return "duplicate basis"
     if len(m.basis) * no > MAX_STATE or any(k == 1 and not 0 <= p <= MAX_POWER for k, p in m.basis):
         return "size"
@@ -203,13 +212,17 @@ def _copy_fit(src, dst):
         dst._set_matrices(src.A, src.B)
 
 
-def fit_linear_models(models, trajs, device=0, backend="device"):
+def fit_linear_models(models, trajs, device=0, backend="device", lasso="host"):
     """Fit untrained ``ARX`` / ``Koopman`` models of one system to `trajs`; every model ends up as after its own
     ``train(trajs)``.  Equal configurations are fitted once.  Models the Gram route declines (module docstring)
     are fitted by ``train()``.  backend="numpy" runs ``gram_fit_host`` in place of the device call (the check of
-    the algorithm on a host without a GPU; there is no automatic fallback).  Returns a ``LinearFitReport``."""
+    the algorithm on a host without a GPU; there is no automatic fallback).  lasso="device": Koopman models of
+    method "lasso" are fitted by ``ampc_lasso_fit`` (backend="numpy": ``lasso_fit_host``), their report entries gain
+    ``"sweeps"`` and ``"margin"``; lasso="host" (default): by ``train()``.  Returns a ``LinearFitReport``."""
     if backend not in ("device", "numpy"):
         raise ValueError("backend must be 'device' or 'numpy'")
+    if lasso not in ("host", "device"):
+        raise ValueError("lasso must be 'host' or 'device'")
     models = list(models)
     for m in models:
         if not isinstance(m, (ARX, Koopman)):
@@ -220,14 +233,41 @@ def fit_linear_models(models, trajs, device=0, backend="device"):
     groups = {}                                            # configuration -> indices of its models
     for i, m in enumerate(models):
         groups.setdefault(_config_key(m), []).append(i)
-    dev_keys, host = [], {}                                # host: configuration -> reason
+    dev_keys, lasso_keys, host = [], [], {}                # host: configuration -> reason
     for key, members in groups.items():
-        reason = _host_reason(models[members[0]])
-        if reason is None:
-            dev_keys.append(key)
-        else:
+        reason = _host_reason(models[members[0]], lasso)
+        if reason is not None:
             host[key] = reason
+        elif key[0] == "koopman" and key[1] == "lasso":
+            lasso_keys.append(key)
+        else:
+            dev_keys.append(key)
     pivots = {}
+    if lasso_keys:
+        from .lasso_fit import lasso_fit_host
+        lens, obs, ctrls = concat_trajs(trajs)
+        basis_of, bases, configs = {}, [], []
+        for key in lasso_keys:
+            if key[3] not in basis_of:
+                basis_of[key[3]] = len(bases)
+                bases.append(models[groups[key][0]].device_lift())
+            configs.append((basis_of[key[3]], float(key[2])))
+        if backend == "device":
+            out = _lib.lasso_fit(lens, obs, ctrls, bases, configs, device=device)
+        else:
+            out = lasso_fit_host(lens, obs, ctrls, bases, configs)
+        for key, c, s, mg, sw in zip(lasso_keys, *out):
+            stats = {"sweeps": int(sw), "margin": float(np.min(mg))}
+            for i in groups[key]:
+                report[i].update(stats)
+            if s != 0:
+                host[key] = "status %d" % s
+                continue
+            n = c.shape[0]
+            for i in groups[key]:
+                models[i]._set_matrices(c[:n, :n], c[:n, n:])
+                report[i].update(where="device")
+            report.device_fits += 1
     if dev_keys:
         lens, obs, ctrls = concat_trajs(trajs)
         arx = [k for k in dev_keys if k[0] == "arx"]

@@ -43,7 +43,7 @@ int ampc_version(void);   /* 100 * major + minor; 104: + ampc_mppi_run_legacy; 1
                            *      ampc_mppi_plan_set_models, ampc_ilqr_plan_set_models; 107: + ampc_set_mlp_dev, ampc_ilqr_plan_set_constants;
                            * 108: + ampc_kstep_errors; 109: + ampc_lqr_*; 110: + ampc_linfit_fit;
                            * 111: + ampc_kstep_errors_linear; 112: + ampc_kstep_errors_sindy;
-                           * 113: + ampc_sindy_fit */
+                           * 113: + ampc_sindy_fit; 114: + ampc_lasso_fit */
 int ampc_device_count(void);
 
 /* ---- handle ------------------------------------------------------------------------------ */
@@ -565,6 +565,33 @@ int ampc_sindy_fit(int device, int n_traj, const int* traj_len, int obs_dim, int
                    const int* pair_exp, int n_configs, const int* cfg_design, const int* cfg_continuous,
                    const double* cfg_threshold, double alpha, int max_iter, double* coeffs, int* status,
                    double* min_pivot, double* min_margin, int* iterations);
+
+/* Lasso fits of Koopman models (sysid/koopman.py:150-156: sklearn's Lasso(alpha).fit with its defaults -- intercept
+ * fitted and dropped, max_iter 1000, tol 1e-4, cyclic coordinate descent) of ONE data set in one call, by the same
+ * descent run on the Gram.  Data as ampc_linfit_fit (obs_dim 1..256, ctrl_dim 1..16).  Bases: basis_n[n_bases] and the
+ * concatenated basis_kinds / basis_params (kinds of ampc_linfit_fit; n_basis * obs_dim <= 256; duplicate functions
+ * are allowed); configurations: cfg_basis, cfg_alpha [n_configs] (alpha finite, >= 0).  Per basis that a
+ * configuration names, one Gram pass (the MFMA pass of ampc_linfit_fit) over the design [1 | F | Y], F = [lift(obs[t]),
+ * ctrls[t]], Y = lift(obs[t + 1]); with m rows, mu = sum F / m, ybar = sum Y / m:
+ *   G = F'F - m mu mu',  Q = F'Y - m mu ybar',  yy_t = Y_t'Y_t - m ybar_t^2,  a = alpha m,  tol_t = 1e-4 yy_t.
+ * One wave per (configuration, target) then runs, from w = 0 and H = G w = 0, sweeps it = 0..999 over the features in
+ * order: skip i if G_ii == 0; tmp = Q_it - H_i + w_i G_ii; w_new = sign(tmp) max(|tmp| - a, 0) / G_ii; if w_new != w_i:
+ * H += (w_new - w_i) G[:, i]; d_w_max = max |w_new - w_i|, w_max = max |w_new|.  After a sweep with w_max == 0 or
+ * d_w_max / w_max < 1e-4 or it == 999 the duality gap: dn = max |Q_t - H|, R2 = yy_t - 2 w.Q_t + w.H, Ry = yy_t - w.Q_t;
+ * dn > a: c = a / dn, gap = (R2 + R2 c^2) / 2, else c = 1, gap = R2; gap += a |w|_1 - c Ry; stop when gap < tol_t.  A
+ * target that reaches sweep 1000 keeps its w; a sweep that moves nothing and does not stop counts as 1000.
+ * Outputs per configuration, in order: coeffs packed [n][n + ctrl_dim] = [A | B]; status: 0 fitted, 1 not fitted here
+ * (a value is not finite, or the centring took half the digits of a column: G_ii < 2^-26 (F'F)_ii or
+ * yy_t < 2^-26 Y_t'Y_t with the raw value non-zero; an all-zero column is skipped and keeps coefficient 0), 2 a stopping
+ * decision too close to call (|gap - tol_t| <= tie tol_t at some gap check, or |d_w_max / w_max - 1e-4| <= ratio_tie 1e-4
+ * at some sweep: fit that model on the host); min_margin [n_configs][2]: the smallest such gap margin and sweep-test
+ * margin; sweeps: the largest sweep count of its targets.  Refused: sizes over the limits, alpha < 0 or not finite.
+ * Deterministic (fixed-order sums, no atomics): a configuration's result does not depend on the other configurations
+ * or bases of the call or on their order.  Synchronises. */
+int ampc_lasso_fit(int device, int n_traj, const int* traj_len, int obs_dim, int ctrl_dim, const double* obs,
+                   const double* ctrls, int n_bases, const int* basis_n, const int* basis_kinds,
+                   const double* basis_params, int n_configs, const int* cfg_basis, const double* cfg_alpha,
+                   double tie, double ratio_tie, double* coeffs, int* status, double* min_margin, int* sweeps);
 
 /* ---- finite-horizon LQR (f64 only) ---------------------------------------------------------- */
 /* A plan of n_problems LQR controllers (reference: autompc/control/lqr.py:139-192 FiniteHorizonLQR) that keeps
