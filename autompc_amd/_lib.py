@@ -894,20 +894,25 @@ class LqrPlan:
         return scores, obs, ctl
 
 
-def linfit_fit(traj_len, obs, ctrls, arx_histories=(), koopman_bases=(), device=0):
-    """ampc_linfit_fit: least-squares fits of ARX histories and Koopman bases ((kinds, params) pairs) of one data set.
-    obs [R][no], ctrls [R][nu]: the trajectories concatenated, traj_len their lengths.  Returns (coeffs, status,
-    min_pivot): a list of coefficient matrices -- ARX [no][1 + k (no + nu)], Koopman [n][n + nu] -- ARX configurations
-    first, and the two per-configuration arrays."""
+def _fit_data(traj_len, obs, ctrls):
+    """The library and the data set of a fit call, coerced and checked: (lib, lens, obs, ctrls, obs_dim, ctrl_dim)."""
     lib = load()
     if lib.ampc_device_count() <= 0:
         raise AmpcError("no HIP device visible: the MI355X path cannot run here "
                         "(there is no CPU fallback by design)")
     obs, ctrls = as_f64(obs), as_f64(ctrls)
-    no, nu = obs.shape[1], ctrls.shape[1]
     lens = np.ascontiguousarray(traj_len, dtype=np.int32)
     if int(lens.sum()) != obs.shape[0] or obs.shape[0] != ctrls.shape[0]:
         raise ValueError("traj_len does not add up to the rows of obs / ctrls")
+    return lib, lens, obs, ctrls, obs.shape[1], ctrls.shape[1]
+
+
+def linfit_fit(traj_len, obs, ctrls, arx_histories=(), koopman_bases=(), device=0):
+    """ampc_linfit_fit: least-squares fits of ARX histories and Koopman bases ((kinds, params) pairs) of one data set.
+    obs [R][no], ctrls [R][nu]: the trajectories concatenated, traj_len their lengths.  Returns (coeffs, status,
+    min_pivot): a list of coefficient matrices -- ARX [no][1 + k (no + nu)], Koopman [n][n + nu] -- ARX configurations
+    first, and the two per-configuration arrays."""
+    lib, lens, obs, ctrls, no, nu = _fit_data(traj_len, obs, ctrls)
     hist = np.ascontiguousarray(list(arx_histories) + [0], dtype=np.int32)
     n_arx, n_koop = len(hist) - 1, len(koopman_bases)
     nb = np.array([len(k) for k, _ in koopman_bases] + [0], dtype=np.int32)
@@ -930,15 +935,7 @@ def sindy_fit(traj_len, obs, ctrls, designs, configs, ycont=None, alpha=0.05, ma
     tuples of ``sysid.sindy.build_library``; configs: ``(design index, continuous, threshold)`` triples.  Returns
     (coeffs, status, min_pivot, min_margin, iterations): a list of [nx][n_features] matrices and four
     per-configuration arrays (status 0 fitted, 1 pivot rule, 2 threshold tie)."""
-    lib = load()
-    if lib.ampc_device_count() <= 0:
-        raise AmpcError("no HIP device visible: the MI355X path cannot run here "
-                        "(there is no CPU fallback by design)")
-    obs, ctrls = as_f64(obs), as_f64(ctrls)
-    nx, nu = obs.shape[1], ctrls.shape[1]
-    lens = np.ascontiguousarray(traj_len, dtype=np.int32)
-    if int(lens.sum()) != obs.shape[0] or obs.shape[0] != ctrls.shape[0]:
-        raise ValueError("traj_len does not add up to the rows of obs / ctrls")
+    lib, lens, obs, ctrls, nx, nu = _fit_data(traj_len, obs, ctrls)
     if ycont is not None:
         ycont = as_f64(ycont)
         if ycont.shape != obs.shape:
@@ -977,15 +974,7 @@ def lasso_fit(traj_len, obs, ctrls, bases, configs, tie=None, ratio_tie=None, de
     [n][n + nu] matrices and three per-configuration arrays (status 0 fitted, 1 not fitted here, 2 tie; min_margin
     [.][2]: gap margin, sweep-test margin; sweeps: the largest over the targets)."""
     from .sysid.lasso_fit import RATIO_TIE, TIE
-    lib = load()
-    if lib.ampc_device_count() <= 0:
-        raise AmpcError("no HIP device visible: the MI355X path cannot run here "
-                        "(there is no CPU fallback by design)")
-    obs, ctrls = as_f64(obs), as_f64(ctrls)
-    no, nu = obs.shape[1], ctrls.shape[1]
-    lens = np.ascontiguousarray(traj_len, dtype=np.int32)
-    if int(lens.sum()) != obs.shape[0] or obs.shape[0] != ctrls.shape[0]:
-        raise ValueError("traj_len does not add up to the rows of obs / ctrls")
+    lib, lens, obs, ctrls, no, nu = _fit_data(traj_len, obs, ctrls)
     nb = np.array([len(k) for k, _ in bases] + [0], dtype=np.int32)
     kinds = np.array([int(v) for k, _ in bases for v in k] + [0], dtype=np.int32)
     params = np.array([float(v) for _, p in bases for v in p] + [0.0])

@@ -3,11 +3,8 @@
 // design [1 | F | Y] (linfit_gram_kernel), centred through the constant column, then one wave per (configuration,
 // target) runs the cyclic coordinate descent on it.  f64 only; kernels in lasso_kernels.hpp, launchers in
 // launch_lasso.cpp.
-#include "host_common.hpp"
+#include "fit_host.hpp"
 
-size_t linfit_col_bytes();
-int linfit_split_rows();
-void linfit_pack_col(void* dst, int src, int lag, int j, int fn);
 int linfit_launch_gram_part(hipStream_t st, int R, int no, int nu, const void* obs, const void* ctrls,
                             const void* row_start, const void* cols, const void* prog, const void* tiles, int n_tiles,
                             int wp, int nfp, void* part);
@@ -20,24 +17,14 @@ void lasso_pack_pair(void* dst, const double* G, const double* q, const double* 
 int lasso_launch_centre(hipStream_t st, const void* designs, int n_designs, int max_entries);
 int lasso_launch_cd(hipStream_t st, int n_pairs, const void* pairs, void* status, void* margins, void* sweeps);
 
-static constexpr int kLassoMaxState = 256, kLassoMaxCtrl = 16;
-
 namespace {
 struct Design {
   int nf = 0, nt = 0, wp = 0, ldp = 0;
   bool used = false;
-  std::vector<char> cols;
+  LinfitCols cols{linfit_col_bytes(), linfit_pack_col};
   std::vector<double> prog;
   std::vector<int> tiles;
   long long part_off = 0, g_off = 0, q_off = 0, yy_off = 0;      // doubles
-  void add_col(int src, int lag, int j, int fn) {
-    cols.resize(cols.size() + linfit_col_bytes());
-    linfit_pack_col(cols.data() + cols.size() - linfit_col_bytes(), src, lag, j, fn);
-  }
-};
-struct StreamGuard {
-  hipStream_t s = nullptr;
-  ~StreamGuard() { if (s) (void)hipStreamDestroy(s); }
 };
 }  // namespace
 
@@ -49,26 +36,14 @@ extern "C" int ampc_lasso_fit(int device, int n_traj, const int* traj_len, int o
   REQUIRE(traj_len && obs && ctrls && coeffs && status && min_margin && sweeps, "ampc_lasso_fit: NULL argument");
   REQUIRE(basis_n && basis_kinds && basis_params && cfg_basis && cfg_alpha, "ampc_lasso_fit: NULL basis or configuration");
   REQUIRE(n_traj >= 1, "ampc_lasso_fit: n_traj < 1");
-  REQUIRE(obs_dim >= 1 && obs_dim <= kLassoMaxState, "ampc_lasso_fit: obs_dim must be in 1..256");
-  REQUIRE(ctrl_dim >= 1 && ctrl_dim <= kLassoMaxCtrl, "ampc_lasso_fit: ctrl_dim must be in 1..16");
+  REQUIRE(obs_dim >= 1 && obs_dim <= kFitMaxState, "ampc_lasso_fit: obs_dim must be in 1..256");
+  REQUIRE(ctrl_dim >= 1 && ctrl_dim <= kFitMaxCtrl, "ampc_lasso_fit: ctrl_dim must be in 1..16");
   REQUIRE(n_bases >= 1 && n_configs >= 1, "ampc_lasso_fit: no basis or no configuration");
   REQUIRE(tie >= 0.0 && ratio_tie >= 0.0, "ampc_lasso_fit: tie margins must be >= 0");
   const int no = obs_dim, nu = ctrl_dim;
-  long long R = 0;
-  for (int i = 0; i < n_traj; ++i) {
-    REQUIRE(traj_len[i] >= 1, "ampc_lasso_fit: trajectory length < 1");
-    R += traj_len[i];
-  }
-  REQUIRE(R < (1LL << 30), "ampc_lasso_fit: too many rows");
-  // first row of every row's trajectory; -1 for a trajectory's last row (it predicts nothing)
-  std::vector<int> row_start((size_t)R);
-  long long design_rows = 0;
-  for (long long g = 0, i = 0; i < n_traj; ++i) {
-    const long long s = g;
-    for (int t = 0; t < traj_len[i]; ++t, ++g) row_start[g] = t + 1 < traj_len[i] ? (int)s : -1;
-    design_rows += traj_len[i] - 1;
-  }
-  REQUIRE(design_rows >= 1, "ampc_lasso_fit: no trajectory has two rows");
+  FitData data;
+  if (int rc = data.index("ampc_lasso_fit", n_traj, traj_len)) return rc;
+  const long long R = data.R, design_rows = data.design_rows;
 
   std::vector<Design> designs(n_bases);
   for (int c = 0; c < n_configs; ++c) {
@@ -76,37 +51,23 @@ extern "C" int ampc_lasso_fit(int device, int n_traj, const int* traj_len, int o
     REQUIRE(cfg_alpha[c] >= 0.0 && std::isfinite(cfg_alpha[c]), "ampc_lasso_fit: alpha must be finite and >= 0");
     designs[cfg_basis[c]].used = true;
   }
-  const int splits = (int)((R + linfit_split_rows() - 1) / linfit_split_rows());
+  const int splits = data.splits;
   long long part_total = 0, g_total = 0, q_total = 0, yy_total = 0;
   int max_entries = 0;
   for (int b = 0, pos = 0; b < n_bases; ++b) {
     Design& d = designs[b];
     const int nb = basis_n[b];
-    REQUIRE(nb >= 1 && (long long)nb * no <= kLassoMaxState,
-            "ampc_lasso_fit: a Koopman lift (n_basis * obs_dim) must have 1..256 states");
-    for (int k = 0; k < nb; ++k, ++pos) {
-      const int kind = basis_kinds[pos];
-      const double par = basis_params[pos];
-      REQUIRE(kind >= 0 && kind <= 3, "ampc_lasso_fit: basis kind must be 0 identity, 1 power, 2 sin, 3 cos");
-      REQUIRE(kind != 1 || (par >= 0 && par <= 64 && par == std::floor(par)),
-              "ampc_lasso_fit: powers must be integers in 0..64");
-      d.prog.push_back(kind);
-      d.prog.push_back(par);
-    }
+    if (int rc = koopman_basis_program("ampc_lasso_fit", nb, basis_kinds + pos, basis_params + pos, no, d.prog))
+      return rc;
+    pos += nb;
     if (!d.used) continue;
     const int n = nb * no;
     d.nf = n + nu;
     d.nt = n;
-    d.add_col(0, 0, 0, -1);                                        // the constant column
-    for (int f = 0; f < nb; ++f)
-      for (int j = 0; j < no; ++j) d.add_col(1, 0, j, d.prog[2 * f] == 0.0 ? -1 : f);
-    for (int j = 0; j < nu; ++j) d.add_col(2, 0, j, -1);
-    for (int f = 0; f < nb; ++f)
-      for (int j = 0; j < no; ++j) d.add_col(1, -1, j, d.prog[2 * f] == 0.0 ? -1 : f);
-    const int w = 1 + d.nf + d.nt;
-    d.wp = (w + 15) / 16 * 16;
+    d.cols.add(0, 0, 0, -1);                                       // the constant column
+    koopman_columns(d.cols, d.prog, no, nu);
+    d.wp = d.cols.pad16(0, -2, 0, -1);
     d.ldp = (d.nf + 63) / 64 * 64;
-    for (int c = w; c < d.wp; ++c) d.add_col(0, -2, 0, -1);        // padding columns: zero
     // tile rows of [1 | F] against every column on and right of the diagonal; of Y the diagonal tiles
     const int frows = (1 + d.nf + 15) / 16;
     for (int ti = 0; ti < d.wp / 16; ++ti)
@@ -130,39 +91,27 @@ extern "C" int ampc_lasso_fit(int device, int n_traj, const int* traj_len, int o
   const int P = (int)cfg_pair[n_configs];
   const long long out = cfg_out[n_configs];
 
-  REQUIRE(ampc_device_count() > 0, "ampc_lasso_fit: no HIP device");
-  HIP_OK(hipSetDevice(device));
-  StreamGuard sg;
-  HIP_OK(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
-  hipStream_t st = sg.s;
-  ScopedBuf d_obs, d_ctl, d_rs, d_part, d_g, d_q, d_yy, d_bad, d_designs, d_pairs, d_coef, d_status, d_mar, d_it;
+  if (int rc = data.stage("ampc_lasso_fit", device, no, nu, obs, ctrls, nullptr)) return rc;
+  hipStream_t st = data.sg.s;
+  ScopedBuf d_part, d_g, d_q, d_yy, d_bad, d_designs, d_pairs, d_coef, d_status, d_mar, d_it;
   std::vector<ScopedBuf> d_cols(n_bases), d_prog(n_bases), d_tiles(n_bases);
-  HIP_OK(d_obs.reserve((size_t)R * no * 8));
-  HIP_OK(d_ctl.reserve((size_t)R * nu * 8));
-  HIP_OK(d_rs.reserve((size_t)R * 4));
   HIP_OK(d_part.reserve((size_t)part_total * 8));
   HIP_OK(d_g.reserve((size_t)g_total * 8));
   HIP_OK(d_q.reserve((size_t)q_total * 8));
   HIP_OK(d_yy.reserve((size_t)yy_total * 8));
   HIP_OK(d_bad.reserve((size_t)n_bases * 4));
   HIP_OK(hipMemsetAsync(d_bad.p, 0, (size_t)n_bases * 4, st));
-  HIP_OK(hipMemcpyAsync(d_obs.p, obs, (size_t)R * no * 8, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_ctl.p, ctrls, (size_t)R * nu * 8, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_rs.p, row_start.data(), (size_t)R * 4, hipMemcpyHostToDevice, st));
   const size_t gsz = lasso_design_bytes();
   std::vector<char> dtab;
   std::vector<int> design_slot(n_bases, -1);
   for (int b = 0; b < n_bases; ++b) {
     const Design& d = designs[b];
     if (!d.used) continue;
-    HIP_OK(d_cols[b].reserve(d.cols.size()));
-    HIP_OK(d_prog[b].reserve(d.prog.size() * 8));
-    HIP_OK(d_tiles[b].reserve(d.tiles.size() * 4));
-    HIP_OK(hipMemcpyAsync(d_cols[b].p, d.cols.data(), d.cols.size(), hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_prog[b].p, d.prog.data(), d.prog.size() * 8, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_tiles[b].p, d.tiles.data(), d.tiles.size() * 4, hipMemcpyHostToDevice, st));
-    if (int rc = linfit_launch_gram_part(st, (int)R, no, nu, d_obs.p, d_ctl.p, d_rs.p, d_cols[b].p, d_prog[b].p,
-                                         d_tiles[b].p, (int)d.tiles.size(), d.wp, d.wp,
+    if (int rc = fit_upload(d_cols[b], d.cols.bytes, st)) return rc;
+    if (int rc = fit_upload(d_prog[b], d.prog, st)) return rc;
+    if (int rc = fit_upload(d_tiles[b], d.tiles, st)) return rc;
+    if (int rc = linfit_launch_gram_part(st, (int)R, no, nu, data.d_obs.p, data.d_ctrls.p, data.d_row_start.p,
+                                         d_cols[b].p, d_prog[b].p, d_tiles[b].p, (int)d.tiles.size(), d.wp, d.wp,
                                          (double*)d_part.p + d.part_off))
       return rc;
     design_slot[b] = (int)(dtab.size() / gsz);
@@ -171,8 +120,7 @@ extern "C" int ampc_lasso_fit(int device, int n_traj, const int* traj_len, int o
                       (double*)d_g.p + d.g_off, (double*)d_q.p + d.q_off, (double*)d_yy.p + d.yy_off,
                       (int*)d_bad.p + b, d.nf, d.nt, d.wp, d.ldp, splits, (double)design_rows);
   }
-  HIP_OK(d_designs.reserve(dtab.size()));
-  HIP_OK(hipMemcpyAsync(d_designs.p, dtab.data(), dtab.size(), hipMemcpyHostToDevice, st));
+  if (int rc = fit_upload(d_designs, dtab, st)) return rc;
   if (int rc = lasso_launch_centre(st, d_designs.p, (int)(dtab.size() / gsz), max_entries)) return rc;
 
   const size_t psz = lasso_pair_bytes();
@@ -189,11 +137,10 @@ extern "C" int ampc_lasso_fit(int device, int n_traj, const int* traj_len, int o
                       cfg_alpha[c] * (double)design_rows, d.nf, d.ldp, id);
     }
   }
-  HIP_OK(d_pairs.reserve(pairs.size()));
+  if (int rc = fit_upload(d_pairs, pairs, st)) return rc;
   HIP_OK(d_status.reserve((size_t)P * 4));
   HIP_OK(d_mar.reserve((size_t)P * 16));
   HIP_OK(d_it.reserve((size_t)P * 4));
-  HIP_OK(hipMemcpyAsync(d_pairs.p, pairs.data(), pairs.size(), hipMemcpyHostToDevice, st));
   if (int rc = lasso_launch_cd(st, P, d_pairs.p, d_status.p, d_mar.p, d_it.p)) return rc;
   std::vector<int> bad(P), its(P);
   std::vector<double> mar((size_t)2 * P);

@@ -3,15 +3,11 @@
 // (distinct feature libraries) -- a configuration's every iteration and target only needs a sub-matrix of its
 // design's Gram Theta'[Theta | Y] -- then one solve workgroup per (configuration, target).
 // f64 only; kernels in sindyfit_kernels.hpp, launchers in launch_sindyfit.cpp.
-#include "host_common.hpp"
-
-#include <numeric>
+#include "fit_host.hpp"
 
 size_t sindyfit_col_bytes();
 size_t sindyfit_design_bytes();
 size_t sindyfit_desc_bytes();
-int sindyfit_split_rows();
-int sindyfit_max_feat();
 int sindyfit_max_state();
 int sindyfit_max_ctrl();
 int sindyfit_zero_kind();
@@ -33,17 +29,9 @@ struct Design {
   int nf = 0, w = 0, wp = 0, nfp = 0;
   bool disc = false, cont = false;
   int tcol_disc = 0, tcol_cont = 0;
-  std::vector<char> cols;
+  FitCols<int, int, int, double> cols{sindyfit_col_bytes(), sindyfit_pack_col};     // (kind, a0, a1, par)
   std::vector<int> pool, tiles;
   long long g_off = 0, part_off = 0;      // doubles
-  void add_col(int kind, int a0, int a1, double par) {
-    cols.resize(cols.size() + sindyfit_col_bytes());
-    sindyfit_pack_col(cols.data() + cols.size() - sindyfit_col_bytes(), kind, a0, a1, par);
-  }
-};
-struct StreamGuard {
-  hipStream_t s = nullptr;
-  ~StreamGuard() { if (s) (void)hipStreamDestroy(s); }
 };
 }  // namespace
 
@@ -65,21 +53,9 @@ extern "C" int ampc_sindy_fit(int device, int n_traj, const int* traj_len, int o
   REQUIRE(max_iter >= 1, "ampc_sindy_fit: max_iter < 1");
   REQUIRE(alpha >= 0.0 && std::isfinite(alpha), "ampc_sindy_fit: alpha must be finite and >= 0");
   const int nx = obs_dim, nu = ctrl_dim, nv = nx + nu;
-  long long R = 0;
-  for (int i = 0; i < n_traj; ++i) {
-    REQUIRE(traj_len[i] >= 1, "ampc_sindy_fit: trajectory length < 1");
-    R += traj_len[i];
-  }
-  REQUIRE(R < (1LL << 30), "ampc_sindy_fit: too many rows");
-  // first row of every row's trajectory; -1 for a trajectory's last row (it predicts nothing)
-  std::vector<int> row_start((size_t)R);
-  long long design_rows = 0;
-  for (long long g = 0, i = 0; i < n_traj; ++i) {
-    const long long s = g;
-    for (int t = 0; t < traj_len[i]; ++t, ++g) row_start[g] = t + 1 < traj_len[i] ? (int)s : -1;
-    design_rows += traj_len[i] - 1;
-  }
-  REQUIRE(design_rows >= 1, "ampc_sindy_fit: no trajectory has two rows");
+  FitData data;
+  if (int rc = data.index("ampc_sindy_fit", n_traj, traj_len)) return rc;
+  const long long R = data.R;
 
   std::vector<Design> designs(n_designs);
   for (int c = 0; c < n_configs; ++c) {
@@ -91,13 +67,13 @@ extern "C" int ampc_sindy_fit(int device, int n_traj, const int* traj_len, int o
   }
   REQUIRE(feat_off[0] == 0 && pair_off[0] == 0, "ampc_sindy_fit: offsets must start at 0");
   int max_tiles = 0, max_wp = 0, max_entries = 0;
-  const int splits = (int)((R + sindyfit_split_rows() - 1) / sindyfit_split_rows());
+  const int splits = data.splits;
   long long g_total = 0, part_total = 0;
   for (int di = 0; di < n_designs; ++di) {
     Design& d = designs[di];
     const int f0 = feat_off[di], p0 = pair_off[di], np = pair_off[di + 1] - p0;
     d.nf = feat_off[di + 1] - f0;
-    REQUIRE(d.nf >= 1 && d.nf <= sindyfit_max_feat(), "ampc_sindy_fit: a design must have 1..272 features");
+    REQUIRE(d.nf >= 1 && d.nf <= kFitMaxFeat, "ampc_sindy_fit: a design must have 1..272 features");
     REQUIRE(np >= 0, "ampc_sindy_fit: pair offsets must not decrease");
     for (int j = 0; j < np; ++j) {
       REQUIRE(pair_var[p0 + j] >= 0 && pair_var[p0 + j] < nv, "ampc_sindy_fit: monomial variable out of range");
@@ -113,22 +89,19 @@ extern "C" int ampc_sindy_fit(int device, int n_traj, const int* traj_len, int o
       else
         REQUIRE(a0[k] >= 0 && a0[k] < nv && a1[k] >= 0 && a1[k] < nv, "ampc_sindy_fit: feature variable out of range");
       REQUIRE(std::isfinite(par[k]), "ampc_sindy_fit: feature parameter not finite");
-      d.add_col(kind[k], a0[k], a1[k], par[k]);
+      d.cols.add(kind[k], a0[k], a1[k], par[k]);
     }
     d.tcol_disc = d.nf;
     d.tcol_cont = d.nf + (d.disc ? nx : 0);
     if (d.disc)
-      for (int j = 0; j < nx; ++j) d.add_col(sindyfit_next_obs_kind(), j, 0, 0.0);
+      for (int j = 0; j < nx; ++j) d.cols.add(sindyfit_next_obs_kind(), j, 0, 0.0);
     if (d.cont)
-      for (int j = 0; j < nx; ++j) d.add_col(sindyfit_ycont_kind(), j, 0, 0.0);
-    d.w = d.nf + nx * ((d.disc ? 1 : 0) + (d.cont ? 1 : 0));
-    d.wp = (d.w + 15) / 16 * 16;
+      for (int j = 0; j < nx; ++j) d.cols.add(sindyfit_ycont_kind(), j, 0, 0.0);
+    d.w = d.cols.n;
+    d.wp = d.cols.pad16(sindyfit_zero_kind(), 0, 0, 0.0);
     d.nfp = (d.nf + 15) / 16 * 16;
-    for (int c = d.w; c < d.wp; ++c) d.add_col(sindyfit_zero_kind(), 0, 0, 0.0);
     if (d.pool.empty()) d.pool.assign(2, 0);
-    // symmetric part: tiles on and above the diagonal; the target columns follow in the same tile rows
-    for (int ti = 0; ti < d.nfp / 16; ++ti)
-      for (int tj = ti; tj < d.wp / 16; ++tj) d.tiles.push_back(ti | (tj << 16));
+    d.tiles = upper_tiles(d.nfp, d.wp);
     max_tiles = std::max(max_tiles, (int)d.tiles.size());
     max_wp = std::max(max_wp, d.wp);
     max_entries = std::max(max_entries, d.nf * d.w);
@@ -152,43 +125,25 @@ extern "C" int ampc_sindy_fit(int device, int n_traj, const int* traj_len, int o
   const int P = (int)cfg_pair[n_configs];
   REQUIRE(ws <= (1LL << 31), "ampc_sindy_fit: the solve workspace would exceed 16 GiB (too many configurations)");
 
-  REQUIRE(ampc_device_count() > 0, "ampc_sindy_fit: no HIP device");
-  HIP_OK(hipSetDevice(device));
-  StreamGuard sg;
-  HIP_OK(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
-  hipStream_t st = sg.s;
-  ScopedBuf d_obs, d_ctl, d_yc, d_rs, d_part, d_g, d_designs, d_descs, d_order, d_ws, d_coef, d_bad, d_piv, d_mar,
-      d_it;
+  if (int rc = data.stage("ampc_sindy_fit", device, nx, nu, obs, ctrls, ycont)) return rc;
+  hipStream_t st = data.sg.s;
+  ScopedBuf d_part, d_g, d_designs, d_descs, d_order, d_ws, d_coef, d_bad, d_piv, d_mar, d_it;
   std::vector<ScopedBuf> d_cols(n_designs), d_pool(n_designs), d_tiles(n_designs);
-  HIP_OK(d_obs.reserve((size_t)R * nx * 8));
-  HIP_OK(d_ctl.reserve((size_t)R * nu * 8));
-  HIP_OK(d_rs.reserve((size_t)R * 4));
   HIP_OK(d_part.reserve((size_t)part_total * 8));
   HIP_OK(d_g.reserve((size_t)g_total * 8));
-  HIP_OK(hipMemcpyAsync(d_obs.p, obs, (size_t)R * nx * 8, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_ctl.p, ctrls, (size_t)R * nu * 8, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_rs.p, row_start.data(), (size_t)R * 4, hipMemcpyHostToDevice, st));
-  if (ycont) {
-    HIP_OK(d_yc.reserve((size_t)R * nx * 8));
-    HIP_OK(hipMemcpyAsync(d_yc.p, ycont, (size_t)R * nx * 8, hipMemcpyHostToDevice, st));
-  }
   const size_t gsz = sindyfit_design_bytes();
   std::vector<char> dtab((size_t)n_designs * gsz);
   for (int i = 0; i < n_designs; ++i) {
     const Design& d = designs[i];
-    HIP_OK(d_cols[i].reserve(d.cols.size()));
-    HIP_OK(d_pool[i].reserve(d.pool.size() * 4));
-    HIP_OK(d_tiles[i].reserve(d.tiles.size() * 4));
-    HIP_OK(hipMemcpyAsync(d_cols[i].p, d.cols.data(), d.cols.size(), hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_pool[i].p, d.pool.data(), d.pool.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_tiles[i].p, d.tiles.data(), d.tiles.size() * 4, hipMemcpyHostToDevice, st));
+    if (int rc = fit_upload(d_cols[i], d.cols.bytes, st)) return rc;
+    if (int rc = fit_upload(d_pool[i], d.pool, st)) return rc;
+    if (int rc = fit_upload(d_tiles[i], d.tiles, st)) return rc;
     sindyfit_pack_design(dtab.data() + (size_t)i * gsz, d_cols[i].p, d_pool[i].p, d_tiles[i].p,
                          (double*)d_part.p + d.part_off, (double*)d_g.p + d.g_off, d.nf, d.w, (int)d.tiles.size());
   }
-  HIP_OK(d_designs.reserve(dtab.size()));
-  HIP_OK(hipMemcpyAsync(d_designs.p, dtab.data(), dtab.size(), hipMemcpyHostToDevice, st));
-  if (int rc = sindyfit_launch_gram(st, (int)R, nx, nu, d_obs.p, d_ctl.p, ycont ? d_yc.p : nullptr, d_rs.p,
-                                    d_designs.p, n_designs, max_tiles, max_wp, max_entries))
+  if (int rc = fit_upload(d_designs, dtab, st)) return rc;
+  if (int rc = sindyfit_launch_gram(st, (int)R, nx, nu, data.d_obs.p, data.d_ctrls.p, data.d_ycont.p,
+                                    data.d_row_start.p, d_designs.p, n_designs, max_tiles, max_wp, max_entries))
     return rc;
 
   std::vector<char> descs((size_t)P * dsz);
@@ -210,16 +165,14 @@ extern "C" int ampc_sindy_fit(int device, int n_traj, const int* traj_len, int o
   std::iota(order.begin(), order.end(), 0);
   std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return pair_nf[a] > pair_nf[b]; });
   const long long out = cfg_out[n_configs];
-  HIP_OK(d_descs.reserve(descs.size()));
-  HIP_OK(d_order.reserve((size_t)P * 4));
+  if (int rc = fit_upload(d_descs, descs, st)) return rc;
+  if (int rc = fit_upload(d_order, order, st)) return rc;
   HIP_OK(d_ws.reserve((size_t)ws * 8));
   HIP_OK(d_coef.reserve((size_t)out * 8));
   HIP_OK(d_bad.reserve((size_t)P * 4));
   HIP_OK(d_piv.reserve((size_t)P * 8));
   HIP_OK(d_mar.reserve((size_t)P * 8));
   HIP_OK(d_it.reserve((size_t)P * 4));
-  HIP_OK(hipMemcpyAsync(d_descs.p, descs.data(), descs.size(), hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_order.p, order.data(), (size_t)P * 4, hipMemcpyHostToDevice, st));
   if (int rc = sindyfit_launch_solve(st, P, d_descs.p, d_order.p, d_ws.p, d_coef.p, d_bad.p, d_piv.p, d_mar.p, d_it.p,
                                      alpha, max_iter))
     return rc;

@@ -1,9 +1,10 @@
 // lasso_kernels.hpp -- lasso fits of Koopman models in f64 (reference: autompc/sysid/koopman.py:150-156, sklearn's
 // Lasso with its defaults), many (basis, alpha) configurations per call: cyclic coordinate descent on the Gram.
 //
-// The Gram of the design [1 | F | Y] comes from linfit_gram_kernel (linfit_kernels.hpp; its tile list here holds the
-// tile rows of [1 | F] against all columns and the diagonal tiles of Y).  lasso_centre_kernel sums the partial tiles
-// over the row splits in order and centres through the constant column: with m rows, mu = sum F / m, ybar = sum Y / m,
+// The Gram of the design [1 | F | Y] comes from linfit_gram_kernel (linfit_kernels.hpp, gram_frame.hpp; its tile list
+// here holds the tile rows of [1 | F] against all columns and the diagonal tiles of Y).  lasso_centre_kernel sums the
+// partial tiles over the row splits in order (gram_split_sum) and centres through the constant column: with m rows,
+// mu = sum F / m, ybar = sum Y / m,
 //   G = F'F - m mu mu'      Q = F'Y - m mu ybar'      yy_t = Y_t'Y_t - m ybar_t^2
 // G is stored [nf][ldp] (ldp = nf rounded up to 64, padding zero) and symmetric to the bit (each pair is summed once),
 // Q transposed [nt][ldp].  bad[design] is set when the centring took half the digits of a column's sum of squares
@@ -17,6 +18,8 @@
 #ifndef AMPC_LASSO_KERNELS_HPP
 #define AMPC_LASSO_KERNELS_HPP
 #include <hip/hip_runtime.h>
+
+#include "gram_frame.hpp"
 
 namespace ampc {
 
@@ -35,12 +38,10 @@ struct LassoDesign {
   double m;               // design rows
 };
 
-// sum over the row splits, in order, of entry (a, b) of the partial Gram; a tile below the diagonal is its mirror
+// entry (a, b) of the raw Gram: the ordered sum of its partial tiles (of Y only the diagonal tiles exist, and only
+// they are asked for)
 __device__ inline double lasso_raw(const LassoDesign& d, int a, int b) {
-  if ((b >> 4) < (a >> 4)) { const int t = a; a = b; b = t; }
-  double s = 0.0;
-  for (int k = 0; k < d.splits; ++k) s += d.part[((size_t)k * d.wp + a) * d.wp + b];
-  return s;
+  return gram_split_sum(d.part, d.splits, d.wp, d.wp, a, b, true);
 }
 
 // grid (blocks over (nf + nt) * ldp + nt entries, designs)

@@ -1,28 +1,20 @@
 // sindyfit_kernels.hpp -- sequentially-thresholded least-squares (STLSQ) fits of SINDy models in f64 (what
-// sysid/sindy.py SINDy.train does on the host), many configurations per call.  The frame is linfit_kernels.hpp's.
+// sysid/sindy.py SINDy.train does on the host), many configurations per call.
 //
 // sindyfit_gram_kernel + sindyfit_gram_reduce_kernel: G = Theta' [Theta | Y_discrete | Y_continuous] of EVERY design
-// (feature library) of the call in one launch: the design is a grid dimension.  A design row is one data row t of a
-// trajectory that has a successor.  Its feature columns are the library's functions of [obs[t], ctrls[t]] (the seven
-// kinds of sindy_kernels.hpp, evaluated by sindy_feature / sindy_ipow as the prediction kernels do), its target
-// columns the next observation (discrete) and / or row t of an uploaded [R][nx] array (continuous: np.gradient of the
-// observations or the caller's xdot); only the target sets a configuration of the design asks for are formed.  Columns
-// are formed ON THE FLY by a per-column rule (SindyfitCol), sixteen rows at a time into LDS: the wide design matrix
-// never exists in HBM.  Accumulation on v_mfma_f64_16x16x4_f64, one accumulator per 16 x 16 tile; of Theta'Theta only
-// the tiles on and above the diagonal are computed (the reduction mirrors them).
-//
-// Determinism (linfit_kernels.hpp's contract).  Rows are split over workgroups by ROW INDEX only (kSindyfitSplitRows
-// consecutive data rows each); rows without a successor are dropped by a SELECT.  An entry's partial sum is one MFMA
-// accumulator's k-ordered chain over the split's rows, the partials are summed over splits in order by
-// sindyfit_gram_reduce_kernel.  No atomics: G[a][b] of two given columns has the same bits whatever other columns or
-// designs the call holds, and from run to run.
+// (feature library) of the call in one launch of the shared Gram pass (gram_frame.hpp: row splits, MFMA tiles, ordered
+// sum; its determinism contract holds here): the design is a grid dimension.  A design's feature columns are the
+// library's functions of [obs[t], ctrls[t]] (the seven kinds of sindy_kernels.hpp, evaluated by sindy_feature /
+// sindy_ipow as the prediction kernels do), its target columns the next observation (discrete) and / or row t of an
+// uploaded [R][nx] array (continuous: np.gradient of the observations or the caller's xdot); only the target sets a
+// configuration of the design asks for are formed.  The per-column rule is SindyfitCol; of Theta'Theta only the tiles
+// on and above the diagonal are computed (the reduction mirrors them).
 //
 // sindyfit_solve_kernel: one workgroup per (configuration, target).  A configuration is (design, time mode,
 // threshold); alpha and max_iter belong to the call.  With keep = all features, every iteration gathers
-// G[keep, keep] + alpha I and G[keep, target], scales to unit diagonal (D = diag(G + alpha I)^-1/2), factors by the
-// right-looking blocked Cholesky of linfit_solve_kernel (panel in LDS, trailing matrix in global memory, the
-// right-hand side carried as an extra row), back-substitutes, and drops the kept features with |coef| < threshold;
-// it stops when nothing is dropped, nothing is kept or max_iter solves were made.  The result is where(keep, coef, 0)
+// G[keep, keep] + alpha I and G[keep, target], scales to unit diagonal (D = diag(G + alpha I)^-1/2), factors by
+// fit_cholesky (gram_frame.hpp; the right-hand side carried as an extra row), back-substitutes, and drops the kept
+// features with |coef| < threshold; it stops when nothing is dropped, nothing is kept or max_iter solves were made.  The result is where(keep, coef, 0)
 // of the last solve, as SINDy.train leaves it.
 // Per pair: bad = 1 when, in any solve, a diagonal entry or pivot is not positive and finite, a coefficient is not
 // finite, or the smallest squared pivot is below n_kept * 2^-26; the smallest squared pivot; the smallest threshold
@@ -32,22 +24,15 @@
 #define AMPC_SINDYFIT_KERNELS_HPP
 #include <hip/hip_runtime.h>
 
+#include "gram_frame.hpp"
 #include "sindy_kernels.hpp"
 
 namespace ampc {
 
-// the frame's constants, equal to linfit_kernels.hpp's (that header defines kernels, so it is not included here)
-constexpr int kSindyfitThreads = 256;
-constexpr int kSindyfitSplitRows = 512;   // data rows per workgroup of the Gram pass (a constant: see Determinism)
-constexpr int kSindyfitChunk = 16;        // design rows formed in LDS at a time
-constexpr int kSindyfitAcc = 8;           // tiles (accumulators) per wave
-constexpr int kSindyfitNb = 8, kSindyfitPs = kSindyfitNb + 1;   // Cholesky panel width, LDS row stride of the panel
-constexpr int kSindyfitMaxFeat = 272;     // features per design (kLinfitMaxFeat)
-typedef double sindyfit_d4 __attribute__((ext_vector_type(4)));
 constexpr int kSindyfitMaxState = 64, kSindyfitMaxCtrl = 16;
 // columns of a design: features + both target sets, padded to a tile; two per thread
-constexpr int kSindyfitMaxCols = (kSindyfitMaxFeat + 2 * kSindyfitMaxState + 15) / 16 * 16;
-constexpr int kSindyfitColsPerThread = (kSindyfitMaxCols + kSindyfitThreads - 1) / kSindyfitThreads;
+constexpr int kSindyfitMaxCols = (kFitMaxFeat + 2 * kSindyfitMaxState + 15) / 16 * 16;
+constexpr int kSindyfitColsPerThread = (kSindyfitMaxCols + kFitThreads - 1) / kFitThreads;
 
 enum { SFC_NEXT_OBS = 7, SFC_YCONT = 8, SFC_ZERO = 9 };   // column kinds behind the library's SF_* kinds
 
@@ -57,6 +42,7 @@ struct SindyfitCol {
   int a0, a1;   // variables (index into [obs | ctrls]); SF_MONO: first (variable, exponent) pair and their number
   int pad;
   double par;   // frequency / exponent
+  __host__ __device__ static SindyfitCol zero() { return SindyfitCol{SFC_ZERO, 0, 0, 0, 0.0}; }     // a padding column
 };
 
 // One design.  Read field by field through a global pointer (uniform loads), as LinfitSolveDesc.
@@ -96,72 +82,23 @@ __device__ inline double sindyfit_value(const SindyfitGramArgs& a, const Sindyfi
   return sindy_feature<double>(c.kind, sindyfit_var(a, g, c.a0), sindyfit_var(a, g, c.a1), c.par);
 }
 
-// grid (splits, tile groups, designs): workgroup (s, q, d) accumulates tiles 32 q .. 32 q + 31 of design d over data
-// rows kSindyfitSplitRows s ..; dynamic LDS: kSindyfitChunk * (largest lds_stride of the call) doubles.
-__global__ __launch_bounds__(kSindyfitThreads) void sindyfit_gram_kernel(const SindyfitGramArgs a) {
+// grid (splits, tile groups, designs); dynamic LDS: kFitChunk * (largest lds_stride of the call) doubles.
+__global__ __launch_bounds__(kFitThreads) void sindyfit_gram_kernel(const SindyfitGramArgs a) {
   extern __shared__ __attribute__((aligned(16))) double sindyfit_lds[];
   const SindyfitDesign* d = a.designs + blockIdx.z;
   const int n_tiles = d->n_tiles;
-  if ((int)blockIdx.y * 4 * kSindyfitAcc >= n_tiles) return;      // (uniform: a narrower design has fewer groups)
+  if ((int)blockIdx.y * 4 * kFitAcc >= n_tiles) return;      // (uniform: a narrower design has fewer groups)
   const int wp = d->wp, nfp = d->nfp, stride = d->lds_stride;
   const SindyfitCol* __restrict__ cols = d->cols;
   const int* __restrict__ pool = d->pool;
   const int* __restrict__ tiles = d->tiles;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  int ti[kSindyfitAcc], tj[kSindyfitAcc];
-  sindyfit_d4 acc[kSindyfitAcc];
-#pragma unroll
-  for (int q = 0; q < kSindyfitAcc; ++q) {
-    const int id = ((int)blockIdx.y * 4 + wave) * kSindyfitAcc + q;
-    const int w = id < n_tiles ? tiles[id] : -1;
-    ti[q] = w < 0 ? -1 : (w & 0xffff);
-    tj[q] = w < 0 ? -1 : (w >> 16);
-    acc[q] = sindyfit_d4{0.0, 0.0, 0.0, 0.0};
-  }
-  SindyfitCol col[kSindyfitColsPerThread];
-#pragma unroll
-  for (int m = 0; m < kSindyfitColsPerThread; ++m) {
-    const int c = tid + m * kSindyfitThreads;
-    col[m] = c < wp ? cols[c] : SindyfitCol{SFC_ZERO, 0, 0, 0, 0.0};
-  }
-  const int row0 = (int)blockIdx.x * kSindyfitSplitRows;
-  const int rend = row0 + kSindyfitSplitRows < a.R ? row0 + kSindyfitSplitRows : a.R;
-  for (int c0 = row0; c0 < rend; c0 += kSindyfitChunk) {
-#pragma unroll
-    for (int m = 0; m < kSindyfitColsPerThread; ++m) {
-      const int c = tid + m * kSindyfitThreads;
-      if (c >= wp) continue;
-      for (int r = 0; r < kSindyfitChunk; ++r) {
-        const int g = c0 + r;
-        const int start = g < rend ? a.row_start[g] : -1;
-        // a row without a successor is dropped by a SELECT (its values are never formed)
-        sindyfit_lds[r * stride + c] = start < 0 ? 0.0 : sindyfit_value(a, col[m], pool, g);
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int ks = 0; ks < kSindyfitChunk / 4; ++ks) {
-      const double* rowp = sindyfit_lds + (4 * ks + (lane >> 4)) * stride + (lane & 15);
-#pragma unroll
-      for (int q = 0; q < kSindyfitAcc; ++q)
-        if (ti[q] >= 0)
-          acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(rowp[16 * ti[q]], rowp[16 * tj[q]], acc[q], 0, 0, 0);
-    }
-    __syncthreads();
-  }
-  double* part = d->part + (size_t)blockIdx.x * nfp * wp;
-#pragma unroll
-  for (int q = 0; q < kSindyfitAcc; ++q) {
-    if (ti[q] < 0) continue;
-#pragma unroll
-    for (int r = 0; r < 4; ++r)       // f64 16x16x4 result map: column lane & 15, row (lane >> 4) + 4 r
-      part[(size_t)(16 * ti[q] + (lane >> 4) + 4 * r) * wp + 16 * tj[q] + (lane & 15)] = acc[q][r];
-  }
+  gram_tiles<kSindyfitColsPerThread>(
+      sindyfit_lds, cols, tiles, n_tiles, wp, nfp, stride, d->part, a.R, a.row_start,
+      [&a, pool](const SindyfitCol c, int g, int) { return sindyfit_value(a, c, pool, g); });
 }
 
-// grid (blocks, designs): G[a][b] = sum over splits, in split order, of the partial tile entries; an entry below the
-// tile diagonal of the symmetric part is read from its mirror.  Entries with a >= nf or b >= w are not written.
+// grid (blocks, designs): G[a][b] = the ordered sum of the partial tile entries.  Entries with a >= nf or b >= w are
+// not written.
 __global__ void sindyfit_gram_reduce_kernel(const SindyfitDesign* __restrict__ designs, int splits) {
   const SindyfitDesign* d = designs + blockIdx.y;
   const int nf = d->nf, w = d->w, wp = d->wp, nfp = d->nfp;
@@ -169,11 +106,7 @@ __global__ void sindyfit_gram_reduce_kernel(const SindyfitDesign* __restrict__ d
   if (i >= nf * w) return;
   const double* __restrict__ part = d->part;
   const int ra = i / w, cb = i - ra * w;
-  int sr = ra, sc = cb;
-  if (cb < nf && (cb >> 4) < (ra >> 4)) { sr = cb; sc = ra; }
-  double s = 0.0;
-  for (int k = 0; k < splits; ++k) s += part[((size_t)k * nfp + sr) * wp + sc];
-  d->G[(size_t)ra * wp + cb] = s;
+  d->G[(size_t)ra * wp + cb] = gram_split_sum(part, splits, nfp, wp, ra, cb, cb < nf);
 }
 
 // One (configuration, target) pair.  Read field by field through a global pointer (uniform loads).
@@ -186,19 +119,19 @@ struct SindyfitSolveDesc {
   double threshold;
 };
 
-__global__ __launch_bounds__(kSindyfitThreads) void sindyfit_solve_kernel(
+__global__ __launch_bounds__(kFitThreads) void sindyfit_solve_kernel(
     const SindyfitSolveDesc* __restrict__ descs, const int* __restrict__ order, double* ws, double* __restrict__ coef,
     int* __restrict__ bad, double* __restrict__ min_pivot, double* __restrict__ min_margin, int* __restrict__ iters,
     const double alpha, const int max_iter) {
-  __shared__ double P[(kSindyfitMaxFeat + 1) * kSindyfitPs];
-  __shared__ double dsc[kSindyfitMaxFeat];      // D
-  __shared__ double linv[kSindyfitMaxFeat];     // 1 / L[j][j]
-  __shared__ double cf[kSindyfitMaxFeat];       // coefficients of the last solve, by feature
-  __shared__ int kl[kSindyfitMaxFeat];          // kept features, in order
-  __shared__ int keep[kSindyfitMaxFeat];
+  __shared__ double P[(kFitMaxFeat + 1) * kFitPs];
+  __shared__ double dsc[kFitMaxFeat];      // D
+  __shared__ double linv[kFitMaxFeat];     // 1 / L[j][j]
+  __shared__ double cf[kFitMaxFeat];       // coefficients of the last solve, by feature
+  __shared__ int kl[kFitMaxFeat];          // kept features, in order
+  __shared__ int keep[kFitMaxFeat];
   __shared__ double s_min, s_solve_min, s_margin;
   __shared__ int s_bad, s_nk, s_drop, s_iters;
-  constexpr int T = kSindyfitThreads, PS = kSindyfitPs;
+  constexpr int T = kFitThreads;
   const SindyfitSolveDesc* d = descs + order[blockIdx.x];
   const int nf = d->n, tcol = d->tcol, id = d->id;
   const double* __restrict__ G = d->g;
@@ -233,51 +166,7 @@ __global__ __launch_bounds__(kSindyfitThreads) void sindyfit_solve_kernel(
                    : G[kl[c] * ldg + tcol] * dsc[c];
     }
     __syncthreads();
-    for (int j0 = 0; j0 < n; j0 += kSindyfitNb) {
-      const int nbw = n - j0 < kSindyfitNb ? n - j0 : kSindyfitNb, pr = rows - j0;
-      for (int e = t; e < pr * nbw; e += T) {
-        const int r = e / nbw, c = e - r * nbw;
-        P[r * PS + c] = M[(size_t)(j0 + r) * n + j0 + c];
-      }
-      __syncthreads();
-      for (int jj = 0; jj < nbw; ++jj) {
-        if (t == 0) {
-          const double piv = P[jj * PS + jj];
-          if (!(piv > 0.0) || !isfinite(piv)) { s_bad = 1; s_min = piv; }
-          else {
-            if (piv < s_solve_min) s_solve_min = piv;
-            const double l = sqrt(piv);
-            P[jj * PS + jj] = l;
-            linv[j0 + jj] = 1.0 / l;
-          }
-        }
-        __syncthreads();
-        if (s_bad) break;
-        const double l = P[jj * PS + jj];
-        for (int r = jj + 1 + t; r < pr; r += T) P[r * PS + jj] /= l;
-        __syncthreads();
-        const int cw = nbw - jj - 1;
-        for (int e = t; e < (pr - jj - 1) * cw; e += T) {
-          const int r = jj + 1 + e / cw, c = jj + 1 + e % cw;
-          if (r >= c) P[r * PS + c] = fma(-P[r * PS + jj], P[c * PS + jj], P[r * PS + c]);
-        }
-        __syncthreads();
-      }
-      if (s_bad) break;
-      for (int e = t; e < pr * nbw; e += T) {
-        const int r = e / nbw, c = e - r * nbw;
-        M[(size_t)(j0 + r) * n + j0 + c] = P[r * PS + c];
-      }
-      const int c1 = j0 + nbw, w = n - c1, h = rows - c1;
-      for (int e = t; e < h * w; e += T) {
-        const int r = c1 + e / w, c = c1 + e % w;
-        if (r < c) continue;
-        double v = M[(size_t)r * n + c];
-        for (int q = 0; q < nbw; ++q) v = fma(-P[(r - j0) * PS + q], P[(c - j0) * PS + q], v);
-        M[(size_t)r * n + c] = v;
-      }
-      __syncthreads();
-    }
+    fit_cholesky(M, rows, n, P, linv, s_bad, s_min, s_solve_min);
     if (s_bad) break;
     // row n holds y = L^-1 (D g_t); back substitution L' z = y by columns, z_j = y_j / L[j][j]
     double* y = M + (size_t)n * n;
