@@ -121,6 +121,8 @@ SIGNATURES = {
                                _ip, c_int, _ip, _ip, _dp, c_double, c_int, _dp, _ip, _dp, _dp, _ip]),
     "ampc_lasso_fit": (c_int, [c_int, c_int, _ip, c_int, c_int, _dp, _dp, c_int, _ip, _ip, _dp, c_int, _ip, _dp,
                                c_double, c_double, _dp, _ip, _dp, _ip]),
+    "ampc_stable_fit": (c_int, [c_int, c_int, _ip, c_int, c_int, _dp, _dp, c_int, _ip, _ip, _dp, c_double, _dp, _ip,
+                                _dp, _ip, _ip, _dp]),
 }
 
 
@@ -994,3 +996,27 @@ def lasso_fit(traj_len, obs, ctrls, bases, configs, tie=None, ratio_tie=None, de
                              float(RATIO_TIE if ratio_tie is None else ratio_tie), dptr(coeffs), iptr(status),
                              dptr(margin), iptr(sweeps)))
     return [coeffs[off[i]:off[i + 1]].reshape(shapes[i]) for i in range(C)], status, margin, sweeps
+
+
+def stable_fit(traj_len, obs, ctrls, bases, tie=None, device=0):
+    """ampc_stable_fit: stable fits of Koopman configurations of one data set, the projected fast-gradient method of
+    ``sysid/stable_fit.py`` on the Gram.  obs [R][no], ctrls [R][nu]: the trajectories concatenated, traj_len their
+    lengths.  bases: (kinds, params) pairs, one configuration each (lifted states <= 64).  tie: the margin below which
+    a line-search decision is a tie (None: ``sysid.stable_fit.TIE``).  Returns (coeffs, status, error, iterations,
+    trials, min_margin): a list of [n][n + nu] matrices ``[A | B]`` and five per-basis arrays (status 0 fitted, 1 not
+    fitted here, 2 tie)."""
+    from .sysid.stable_fit import TIE
+    lib, lens, obs, ctrls, no, nu = _fit_data(traj_len, obs, ctrls)
+    C = len(bases)
+    nb = np.array([len(k) for k, _ in bases] + [0], dtype=np.int32)
+    kinds = np.array([int(v) for k, _ in bases for v in k] + [0], dtype=np.int32)
+    params = np.array([float(v) for _, p in bases for v in p] + [0.0])
+    shapes = [(int(nb[i]) * no, int(nb[i]) * no + nu) for i in range(C)]
+    off = np.concatenate([[0], np.cumsum([r * c for r, c in shapes])]).astype(np.int64)
+    coeffs = np.empty(int(off[-1]))
+    status, iters, trials = (np.zeros(C, dtype=np.int32) for _ in range(3))
+    error, margin = np.empty(C), np.empty(C)
+    check(lib.ampc_stable_fit(int(device), len(lens), iptr(lens), no, nu, dptr(obs), dptr(ctrls), C, iptr(nb),
+                              iptr(kinds), dptr(params), float(TIE if tie is None else tie), dptr(coeffs),
+                              iptr(status), dptr(error), iptr(iters), iptr(trials), dptr(margin)))
+    return [coeffs[off[i]:off[i + 1]].reshape(shapes[i]) for i in range(C)], status, error, iters, trials, margin

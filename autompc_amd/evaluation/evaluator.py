@@ -27,7 +27,7 @@ class ModelEvaluator(ABC):
     ``(model, [Trajectory]) -> float``."""
 
     def __init__(self, system, trajs, metric, rng, horizon=1, linear_fit="host", linear_kstep="host",
-                 sindy_kstep="host", sindy_fit="host", lasso_fit="host"):
+                 sindy_kstep="host", sindy_fit="host", lasso_fit="host", stable_fit="host"):
         """linear_fit: how ``evaluate_batch`` fits ARX / Koopman models -- "host": each by its own ``train()``;
         "device": all of a batch by one ``sysid.linear_fit.fit_linear_models`` call (one Gram pass on the device,
         equal configurations fitted once).
@@ -40,6 +40,9 @@ class ModelEvaluator(ABC):
         ``last_sindy_fit`` holds its ``SindyFitReport``.
         lasso_fit: with ``linear_fit="device"``, how that call fits Koopman models of method "lasso" -- "host": each
         by its own ``train()``; "device": by ``ampc_lasso_fit`` (``fit_linear_models(..., lasso="device")``).
+        stable_fit: with ``linear_fit="device"``, how that call fits Koopman models of method "stable" -- "host": each
+        by its own ``train()``, which refuses the method; "device": by ``ampc_stable_fit``, what it declines by
+        ``sysid.stable_fit.stabilize_host`` (``fit_linear_models(..., stable="device")``).
         ``last_kstep`` holds the ``KstepReport`` of the last ``evaluate_batch`` (``host_fallbacks``)."""
         if linear_fit not in ("host", "device"):
             raise ValueError("linear_fit must be 'host' or 'device'")
@@ -51,8 +54,11 @@ class ModelEvaluator(ABC):
             raise ValueError("sindy_fit must be 'host' or 'device'")
         if lasso_fit not in ("host", "device"):
             raise ValueError("lasso_fit must be 'host' or 'device'")
+        if stable_fit not in ("host", "device"):
+            raise ValueError("stable_fit must be 'host' or 'device'")
         self.linear_fit = linear_fit
         self.lasso_fit = lasso_fit
+        self.stable_fit = stable_fit
         self.sindy_fit = sindy_fit
         self.last_sindy_fit = None
         self.linear_kstep = linear_kstep
@@ -101,7 +107,8 @@ class ModelEvaluator(ABC):
             from ..sysid.linear_fit import fit_linear_models
             linear = [m for m in others if isinstance(m, (ARX, Koopman))]
             if linear:
-                self.last_linear_fit = fit_linear_models(linear, train_trajs, lasso=self.lasso_fit)
+                self.last_linear_fit = fit_linear_models(linear, train_trajs, lasso=self.lasso_fit,
+                                                             stable=self.stable_fit)
             others = [m for m in others if not isinstance(m, (ARX, Koopman))]
         if self.sindy_fit == "device":
             from ..sysid.sindy import SINDy

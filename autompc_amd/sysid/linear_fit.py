@@ -28,6 +28,15 @@ configurations that come back with status 1 (centring lost half the digits of a 
 status 2 (a stopping decision too close to call).  The default ``lasso="host"`` leaves every lasso model to
 ``train()``, as before.
 
+Stable.  With ``stable="device"`` Koopman models of ``method="stable"`` take the Gram route of
+``sysid/stable_fit.py`` (``ampc_stable_fit``: the reference's projected fast-gradient method run on the Gram of
+``[F | Y]``, one configuration per distinct basis).  Models with product terms are refused as by ``train()``; models
+over that route's limits (64 lifted states, 16 controls) and configurations that come back with status 1 (a Cholesky
+pivot under the rule above -- duplicate basis functions end here --, an ill-conditioned polar factor, a non-finite
+value) or status 2 (a line-search decision too close to call) are fitted by ``stable_fit.stabilize_host``, the
+reference's routine restated on the data.  The default ``stable="host"`` leaves every stable model to ``train()``,
+which refuses the method, as before.
+
 ``gram_fit_host`` is the same algorithm in numpy (what the CPU tests run and the GPU tests compare against first).
 """
 import numpy as np
@@ -175,7 +184,8 @@ def gram_fit_host(traj_len, obs, ctrls, arx_histories=(), koopman_bases=(), orde
 
 class LinearFitReport(list):
     """One entry per model, in order: ``{"where": "device" | "host", "reason": None | str, "pivot": float |
-    None}``; models that took the lasso route also carry ``"sweeps"`` and ``"margin"``.  ``host_fits``: the ``train()`` calls that were made (equal configurations share one)."""
+    None}``; models that took the lasso route also carry ``"sweeps"`` and ``"margin"``, models of the stable route
+    ``"iterations"``, ``"trials"``, ``"margin"`` and ``"error"``.  ``host_fits``: the ``train()`` calls that were made (equal configurations share one)."""
     host_fits = 0
     device_fits = 0
 
@@ -186,13 +196,20 @@ def _config_key(m):
     return ("koopman", m.method, m.lasso_alpha, tuple(m.basis), m.product_terms)
 
 
-def _host_reason(m, lasso="host"):
+def _host_reason(m, lasso="host", stable="host"):
     """Why a model cannot take a Gram route (None: it can)."""
     no, nu = m.system.obs_dim, m.system.ctrl_dim
     if nu > MAX_CTRL or no > MAX_STATE:
         return "size"
     if isinstance(m, ARX):
         return "size" if m.state_dim > MAX_STATE else None
+    if stable == "device" and m.method == "stable":
+        from .stable_fit import MAX_N                      # here, not at the top: stable_fit imports this module
+        if m.product_terms:
+            return "product_terms"
+        if len(m.basis) * no > MAX_N or any(k == 1 and not 0 <= p <= MAX_POWER for k, p in m.basis):
+            return "size"
+        return None
     on_lasso_route = lasso == "device" and m.method == "lasso" and m.lasso_alpha is not None
     if m.method != "lstsq" and not on_lasso_route:
         return "method"
@@ -212,17 +229,32 @@ def _copy_fit(src, dst):
         dst._set_matrices(src.A, src.B)
 
 
-def fit_linear_models(models, trajs, device=0, backend="device", lasso="host"):
+def _stable_host_fit(m, trajs):
+    """A stable Koopman model fitted by the data-form restatement of the reference's routine."""
+    from .stable_fit import koopman_rows, stabilize_host
+    lens, obs, ctrls = concat_trajs(trajs)
+    stats = {}
+    A, B, error = stabilize_host(*koopman_rows(lens, obs, ctrls, m.device_lift()), stats=stats)
+    m._set_matrices(A, B)
+    return dict(stats, error=error)
+
+
+def fit_linear_models(models, trajs, device=0, backend="device", lasso="host", stable="host"):
     """Fit untrained ``ARX`` / ``Koopman`` models of one system to `trajs`; every model ends up as after its own
     ``train(trajs)``.  Equal configurations are fitted once.  Models the Gram route declines (module docstring)
     are fitted by ``train()``.  backend="numpy" runs ``gram_fit_host`` in place of the device call (the check of
     the algorithm on a host without a GPU; there is no automatic fallback).  lasso="device": Koopman models of
     method "lasso" are fitted by ``ampc_lasso_fit`` (backend="numpy": ``lasso_fit_host``), their report entries gain
-    ``"sweeps"`` and ``"margin"``; lasso="host" (default): by ``train()``.  Returns a ``LinearFitReport``."""
+    ``"sweeps"`` and ``"margin"``; lasso="host" (default): by ``train()``.  stable="device": Koopman models of method
+    "stable" (without product terms) are fitted by ``ampc_stable_fit`` (backend="numpy": ``stable_fit_host``), those it
+    declines by ``stabilize_host``; their report entries gain ``"iterations"``, ``"trials"``, ``"margin"`` and
+    ``"error"``; stable="host" (default): by ``train()``, which refuses the method.  Returns a ``LinearFitReport``."""
     if backend not in ("device", "numpy"):
         raise ValueError("backend must be 'device' or 'numpy'")
     if lasso not in ("host", "device"):
         raise ValueError("lasso must be 'host' or 'device'")
+    if stable not in ("host", "device"):
+        raise ValueError("stable must be 'host' or 'device'")
     models = list(models)
     for m in models:
         if not isinstance(m, (ARX, Koopman)):
@@ -233,11 +265,17 @@ def fit_linear_models(models, trajs, device=0, backend="device", lasso="host"):
     groups = {}                                            # configuration -> indices of its models
     for i, m in enumerate(models):
         groups.setdefault(_config_key(m), []).append(i)
-    dev_keys, lasso_keys, host = [], [], {}                # host: configuration -> reason
+    dev_keys, lasso_keys, stable_keys, host = [], [], [], {}       # host: configuration -> reason
+    stable_host = {}                                       # stable configurations for stabilize_host -> reason
     for key, members in groups.items():
-        reason = _host_reason(models[members[0]], lasso)
-        if reason is not None:
+        reason = _host_reason(models[members[0]], lasso, stable)
+        on_stable_route = stable == "device" and key[0] == "koopman" and key[1] == "stable"
+        if on_stable_route and reason == "size":
+            stable_host[key] = reason
+        elif reason is not None:
             host[key] = reason
+        elif on_stable_route:
+            stable_keys.append(key)
         elif key[0] == "koopman" and key[1] == "lasso":
             lasso_keys.append(key)
         else:
@@ -268,6 +306,32 @@ def fit_linear_models(models, trajs, device=0, backend="device", lasso="host"):
                 models[i]._set_matrices(c[:n, :n], c[:n, n:])
                 report[i].update(where="device")
             report.device_fits += 1
+    if stable_keys:
+        from .stable_fit import stable_fit_host
+        lens, obs, ctrls = concat_trajs(trajs)
+        bases = [models[groups[key][0]].device_lift() for key in stable_keys]
+        if backend == "device":
+            out = _lib.stable_fit(lens, obs, ctrls, bases, device=device)
+        else:
+            out = stable_fit_host(lens, obs, ctrls, bases)
+        for key, c, s, err, it, tr, mg in zip(stable_keys, *out):
+            if s != 0:
+                stable_host[key] = "status %d" % s
+                continue
+            stats = {"iterations": int(it), "trials": int(tr), "margin": float(mg), "error": float(err)}
+            n = c.shape[0]
+            for i in groups[key]:
+                models[i]._set_matrices(c[:n, :n], c[:n, n:])
+                report[i].update(stats, where="device")
+            report.device_fits += 1
+    for key, reason in stable_host.items():
+        first = models[groups[key][0]]
+        stats = _stable_host_fit(first, trajs)
+        report.host_fits += 1
+        for i in groups[key]:
+            if models[i] is not first:
+                _copy_fit(first, models[i])
+            report[i].update(stats, where="host", reason=reason)
     if dev_keys:
         lens, obs, ctrls = concat_trajs(trajs)
         arx = [k for k in dev_keys if k[0] == "arx"]

@@ -45,7 +45,8 @@ class BatchPipelineTuner:
 
     def __init__(self, system, evaluator, batch_size=64, sampler=None, truedyn_noise="device",
                  eval_kwargs=None, keep_trajs=False, balance=None, models=None, model_factory=None,
-                 trajs=None, as_configs=False, linear_fit="host", sindy_fit="host", lasso_fit="host"):
+                 trajs=None, as_configs=False, linear_fit="host", sindy_fit="host", lasso_fit="host",
+                 stable_fit="host"):
         """truedyn_noise: the noise mode of the controllers scored against the true dynamics
         (MPPI(noise=...): "device" Philox, or "numpy" / "numpy_device" = the reference's global
         legacy stream).  eval_kwargs: extra keyword arguments for every ``evaluator.evaluate`` call
@@ -67,6 +68,10 @@ class BatchPipelineTuner:
 
         lasso_fit: with ``linear_fit="device"``, "device" lets that call fit Koopman configurations of method "lasso"
         by ``ampc_lasso_fit`` (``fit_linear_models(..., lasso="device")``) instead of handing them to ``train()``.
+
+        stable_fit: with ``linear_fit="device"``, "device" lets that call fit Koopman configurations of method
+        "stable" by ``ampc_stable_fit`` (``fit_linear_models(..., stable="device")``; what it declines is fitted by
+        ``sysid.stable_fit.stabilize_host``) instead of handing them to ``train()``, which refuses the method.
 
         sindy_fit: the same for SINDy configurations ("device": one ``sysid.sindy_fit.fit_sindy_models`` call per
         shard); ``sindy_host_fits`` counts the ``train()`` calls it made.
@@ -105,8 +110,11 @@ class BatchPipelineTuner:
             raise ValueError("linear_fit must be 'host' or 'device'")
         if lasso_fit not in ("host", "device"):
             raise ValueError("lasso_fit must be 'host' or 'device'")
+        if stable_fit not in ("host", "device"):
+            raise ValueError("stable_fit must be 'host' or 'device'")
         self.linear_fit = linear_fit
         self.lasso_fit = lasso_fit
+        self.stable_fit = stable_fit
         self.linear_host_fits = 0
         if sindy_fit not in ("host", "device"):
             raise ValueError("sindy_fit must be 'host' or 'device'")
@@ -200,7 +208,8 @@ class BatchPipelineTuner:
                 from ..sysid.linear_fit import fit_linear_models
                 linear = [m for m in others if isinstance(m, (ARX, Koopman))]
                 if linear:
-                    self.linear_host_fits += fit_linear_models(linear, self.trajs, lasso=self.lasso_fit).host_fits
+                    self.linear_host_fits += fit_linear_models(linear, self.trajs, lasso=self.lasso_fit,
+                                                               stable=self.stable_fit).host_fits
                 others = [m for m in others if not isinstance(m, (ARX, Koopman))]
             if self.sindy_fit == "device":
                 from ..sysid.sindy import SINDy

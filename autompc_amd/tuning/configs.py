@@ -198,12 +198,16 @@ def sample_arx_config(rng):
     return {"history": int(rng.integers(1, 11))}
 
 
-def sample_koopman_config(rng):
+def sample_koopman_config(rng, methods=("lstsq", "lasso")):
     """One draw from KoopmanFactory's space (koopman.py:46-77): method, lasso_alpha log-uniform 1e-10..1e2 (method
     lasso), poly_basis / poly_degree 2..8, trig_basis / trig_freq 1..8, product_terms "false"; the conditional keys
-    appear only under their parent's value.  The method is drawn from {lstsq, lasso} only: the reference's third
-    choice, "stable", is a training-time optimisation this project's ``Koopman.train`` refuses."""
-    cfg = {"method": str(rng.choice(["lstsq", "lasso"]))}
+    appear only under their parent's value.  The method is drawn from `methods`, by default {lstsq, lasso}: the
+    reference's third choice, "stable", is fitted by ``fit_linear_models(..., stable="device")`` (``Koopman.train``
+    itself refuses it); ``methods=("lstsq", "lasso", "stable")`` draws from the reference's full space."""
+    for m in methods:
+        if m not in ("lstsq", "lasso", "stable"):
+            raise ValueError("methods must be drawn from lstsq, lasso and stable")
+    cfg = {"method": str(rng.choice(list(methods)))}
     if cfg["method"] == "lasso":
         cfg["lasso_alpha"] = float(10 ** rng.uniform(-10, 2))
     cfg["poly_basis"] = str(rng.choice(["true", "false"]))
@@ -216,11 +220,14 @@ def sample_koopman_config(rng):
     return cfg
 
 
-def sample_lqr_pipeline_configs(system, n, rng, model=None):
+def sample_lqr_pipeline_configs(system, n, rng, model=None, koopman_methods=None):
     """`n` (ARX | Koopman) x LQR x QuadCost configurations with the reference's key names: finite_horizon uniform
     over {"true", "false"}, ``_ctrlr:horizon`` (1..1000) only when "true" (lqr.py:214-224), cost gains as
-    sample_pipeline_configs; model None (no `_model:` keys), "arx" or "koopman" (that factory's sub-space)."""
-    draw = {None: None, "arx": sample_arx_config, "koopman": sample_koopman_config}
+    sample_pipeline_configs; model None (no `_model:` keys), "arx" or "koopman" (that factory's sub-space;
+    koopman_methods: the ``methods`` of ``sample_koopman_config``, None for its default)."""
+    koopman = sample_koopman_config if koopman_methods is None else (
+        lambda r: sample_koopman_config(r, methods=koopman_methods))
+    draw = {None: None, "arx": sample_arx_config, "koopman": koopman}
     if model not in draw:
         raise ValueError("model must be None, 'arx' or 'koopman'")
     out = []

@@ -43,7 +43,7 @@ int ampc_version(void);   /* 100 * major + minor; 104: + ampc_mppi_run_legacy; 1
                            *      ampc_mppi_plan_set_models, ampc_ilqr_plan_set_models; 107: + ampc_set_mlp_dev, ampc_ilqr_plan_set_constants;
                            * 108: + ampc_kstep_errors; 109: + ampc_lqr_*; 110: + ampc_linfit_fit;
                            * 111: + ampc_kstep_errors_linear; 112: + ampc_kstep_errors_sindy;
-                           * 113: + ampc_sindy_fit; 114: + ampc_lasso_fit */
+                           * 113: + ampc_sindy_fit; 114: + ampc_lasso_fit; + ampc_stable_fit (no bump: callers detect it by its symbol) */
 int ampc_device_count(void);
 
 /* ---- handle ------------------------------------------------------------------------------ */
@@ -592,6 +592,27 @@ int ampc_lasso_fit(int device, int n_traj, const int* traj_len, int obs_dim, int
                    const double* ctrls, int n_bases, const int* basis_n, const int* basis_kinds,
                    const double* basis_params, int n_configs, const int* cfg_basis, const double* cfg_alpha,
                    double tie, double ratio_tie, double* coeffs, int* status, double* min_margin, int* sweeps);
+
+/* Stable fits of Koopman configurations (f64), one per basis, of one data set in one call (reference:
+ * autompc/sysid/stable_koopman.py:47-167 stabilize_discrete with its default initialisation): A = S^-1 U B S with S
+ * positive definite, U orthogonal, B symmetric with eigenvalues in [0, 1] -- Schur stable by construction -- fitted by
+ * the projected fast-gradient method, run on the Gram of the design [F | Y] (F = [lift(obs[t]), ctrls[t]], Y =
+ * lift(obs[t + 1]); one shared Gram pass per basis, the least-squares start by the scaled Cholesky of ampc_linfit_fit),
+ * one workgroup per basis: a line-search trial costs O(n^3) whatever the number of rows.  Data and bases as
+ * ampc_lasso_fit; lifted states n = basis_n * obs_dim <= 64, ctrl_dim <= 16.
+ *   tie: a line-search decision |e_next - e| <= tie e (or the convergence test that close to its threshold) is a tie;
+ *   coeffs: per basis [n][n + ctrl_dim] = [A | B], bases in order;
+ *   status [n_bases]: 0 fitted; 1 not fitted here (a Cholesky pivot under ampc_linfit_fit's rule, a polar factor of a
+ *   matrix whose Gram has min eig <= 2^-40 max eig, an eigen-iteration at its 30-sweep cap, a non-finite value: coeffs
+ *   NaN); 2 a decision was a tie (coeffs are the fit that followed);
+ *   error [n_bases]: the final |Y - A Xs - B Xu|_F; iterations, trials [n_bases]: outer iterations and line-search
+ *   trials run; min_margin [n_bases]: the smallest relative distance of a decision from its threshold.
+ * Refused: sizes over the limits, no trajectory with two rows.  Deterministic (fixed-order sums, no atomics): a basis's
+ * result does not depend on the other bases of the call or on their order.  Synchronises. */
+int ampc_stable_fit(int device, int n_traj, const int* traj_len, int obs_dim, int ctrl_dim, const double* obs,
+                    const double* ctrls, int n_bases, const int* basis_n, const int* basis_kinds,
+                    const double* basis_params, double tie, double* coeffs, int* status, double* error,
+                    int* iterations, int* trials, double* min_margin);
 
 /* ---- finite-horizon LQR (f64 only) ---------------------------------------------------------- */
 /* A plan of n_problems LQR controllers (reference: autompc/control/lqr.py:139-192 FiniteHorizonLQR) that keeps
