@@ -7,6 +7,11 @@ restatement's recorded error against the reference and the case's recorded round
 differ from numpy's in the last bits and its eigensolver is Jacobi where numpy's is LAPACK's: equally valid, and
 perturbing at the level of one rounding, which roundoff_response measures.  Iteration and trial counts are integers
 and must equal the reference's.
+
+The size sweep (stablefit_cases.SWEEP: every lifted size around the multiples of 16 at 1 and 16 controls, and a
+ragged-rows case) adds, per case, the kernel's error against the residual of the matrices it returned, formed from the
+data in extended precision, within TIE.  Every fitted sweep case ran the full 29 iterations in the reference: the two
+early exits of the iteration (a second line-search failure in a row, the convergence test) stay unreached.
 """
 import warnings
 
@@ -21,7 +26,9 @@ from autompc_amd.sysid import stable_fit as SF
 from autompc_amd.tuning import BatchPipelineTuner, LqrCandidateEvaluator, sample_lqr_pipeline_configs
 from autompc_amd.tuning.configs import DictConfiguration
 
-from stablefit_cases import CASES, FITTED, basis, data, gold, new_model, reference, rel_err, tolerance, trajs
+from stablefit_cases import (CASES, DECLINED, FITTED, MIXED, MIXED_BASES, SWEEP_FITTED, SWEEP_TIED, basis, data,
+                             declined_data, gold, make_data, new_model, perturbation, reference, rel_err, residual,
+                             tolerance, trajs, two_valued_data, without_lone_rows)
 
 pytestmark = pytest.mark.gpu
 
@@ -63,7 +70,122 @@ def test_a_basis_gives_the_same_bits_alone_in_a_batch_permuted_and_repeated():
             assert np.array_equal(batch[0][k], other[0][j])
             for f in (1, 4, 5):                             # status, trials, min_margin
                 assert np.array_equal(batch[f][k], other[f][j])
+    # the 3-state basis comes within 4.7e-11 of a line-search decision, on the host form as here: a tie (status 2) since
+    # TIE is 1.3e-10 (the size sweep's error-form differences); the two larger ones are fitted
+    host = SF.stable_fit_host(lens, obs, ctrls, bases)
+    assert list(batch[1]) == [2, 0, 0] == list(host[1]) and np.all(np.isfinite(batch[0][0]))
+    assert 3.5e-12 < batch[5][0] <= SF.TIE and abs(batch[5][0] - host[5][0]) <= 1e-3 * host[5][0]
+
+
+@pytest.mark.parametrize("name", SWEEP_FITTED)
+def test_sweep_device_fit_matches_the_reference_and_its_own_residual(name):
+    """One device call per size of stablefit_cases.SWEEP (and its ragged-rows case): status, counts, the matrices
+    against the reference and against stable_fit_host, and the kernel's error against the residual of the matrices it
+    returned, formed from the data in extended precision.  That last difference is the one TIE (100 x the recorded
+    error-form error) is the project's margin for; the residual is Lipschitz in the coefficients, so the bound holds
+    for the exact algorithm."""
+    g = gold(name)
+    lens, obs, ctrls = data(name)
+    b = basis(name)
+    coeffs, status, error, its, trials, margin = _lib.stable_fit(lens, obs, ctrls, [b])
+    assert status[0] == 0
+    assert (int(its[0]), int(trials[0])) == (int(g["iterations"]), int(g["trials"]))
+    tol = tolerance(name)
+    err = rel_err(coeffs[0], reference(name))
+    herr = rel_err(coeffs[0], SF.stable_fit_host(lens, obs, ctrls, [b])[0][0])
+    res = residual(coeffs[0], lens, obs, ctrls, b)
+    rerr = abs(error[0] - res) / res
+    print(name, "device against the reference", err, "against stable_fit_host", herr, "tolerance", tol,
+          "error against the residual", rerr, "TIE", SF.TIE)
+    assert err <= tol and herr <= tol
+    n = coeffs[0].shape[0]
+    assert np.max(np.abs(np.linalg.eigvals(coeffs[0][:, :n]))) <= 1.0 + 1e-9
+    assert rerr <= SF.TIE
+
+
+@pytest.mark.parametrize("name", SWEEP_TIED)
+def test_sweep_one_lifted_state_ties_on_the_device(name):
+    lens, obs, ctrls = data(name)
+    coeffs, status, error, its, trials, margin = _lib.stable_fit(lens, obs, ctrls, [basis(name)])
+    host = SF.stable_fit_host(lens, obs, ctrls, [basis(name)])
+    assert status[0] == 2 == host[1][0] == int(gold(name)["status"])
+    assert np.all(np.isfinite(coeffs[0])) and np.isfinite(error[0])
+
+
+def test_the_kernel_declines_a_singular_polar_factor():
+    """stablefit_cases.DECLINED: the Cholesky accepts, the first polar factor inside stable_fgm_kernel does not."""
+    lens, obs, ctrls = declined_data()
+    coeffs, status, error, its, trials, margin = _lib.stable_fit(lens, obs, ctrls, [([0], [1.0])])
+    assert status[0] == 1 and its[0] == 0 and trials[0] == 0
+    assert coeffs[0].shape == (4, 6) and np.all(np.isnan(coeffs[0])) and np.isnan(error[0]) and margin[0] == np.inf
+
+
+def test_a_declined_basis_leaves_its_neighbours_in_the_launch_alone():
+    """Identity, identity + x^2, identity again on stablefit_cases.two_valued_data: x^2 of the 0 / 1 observation
+    duplicates it, the middle basis is declined (status 1, by the Cholesky or by the polar factor) and the two good
+    ones give the bits they give alone."""
+    lens, obs, ctrls = two_valued_data()
+    good, bad = ([0], [1.0]), ([0, 1], [1.0, 2.0])
+    coeffs, status, error, its, trials, margin = _lib.stable_fit(lens, obs, ctrls, [good, bad, good])
+    alone = _lib.stable_fit(lens, obs, ctrls, [good])
+    assert list(status) == [0, 1, 0] and alone[1][0] == 0
+    assert coeffs[1].shape == (8, 10) and np.all(np.isnan(coeffs[1])) and np.isnan(error[1])
+    assert its[1] == 0 and trials[1] == 0 and margin[1] == np.inf
+    for k in (0, 2):
+        assert np.array_equal(coeffs[k], alone[0][0]) and np.all(np.isfinite(coeffs[k]))
+        for f, other in zip((error, its, trials, margin), alone[2:]):
+            assert np.array_equal(f[k], other[0])
+    assert its[0] > 0 and trials[0] > 0
+
+
+@pytest.fixture(scope="module")
+def mixed():
+    """stablefit_cases.MIXED: the data, stable_fit_host's fits of the three bases and their round-off responses."""
+    lens, obs, ctrls = make_data(MIXED)
+    host = SF.stable_fit_host(lens, obs, ctrls, MIXED_BASES)
+    pert = SF.stable_fit_host(lens, obs, ctrls, MIXED_BASES, perturb=perturbation(MIXED["seed"]))
+    assert np.all(host[1] == 0) and np.all(pert[1] == 0)
+    assert np.array_equal(host[3], pert[3]) and np.array_equal(host[4], pert[4])
+    return (lens, obs, ctrls), host, [rel_err(p, c) for p, c in zip(pert[0], host[0])]
+
+
+def test_a_large_basis_gives_the_same_bits_alone_in_a_batch_permuted_and_repeated(mixed):
+    """n = 21, 42 and 63 lifted states at 16 controls in one launch: three workgroups of different odd and even sizes
+    against the same fits run alone, repeated and permuted, bit for bit; and against stable_fit_host at 100 x the
+    round-off response, computed here from the host form alone."""
+    (lens, obs, ctrls), host, response = mixed
+    bases = MIXED_BASES
+    batch = _lib.stable_fit(lens, obs, ctrls, bases)
+    again = _lib.stable_fit(lens, obs, ctrls, bases)
+    perm = _lib.stable_fit(lens, obs, ctrls, bases[::-1])
+    for k, b in enumerate(bases):
+        alone = _lib.stable_fit(lens, obs, ctrls, [b])
+        for other, j in ((alone, 0), (again, k), (perm, 2 - k)):
+            assert np.array_equal(batch[0][k], other[0][j])
+            for f in (1, 2, 3, 4, 5):                       # status, error, iterations, trials, min_margin
+                assert np.array_equal(batch[f][k], other[f][j])
+    assert [c.shape for c in batch[0]] == [(21, 37), (42, 58), (63, 79)]
     assert np.all(batch[1] == 0)
+    assert np.array_equal(batch[3], host[3]) and np.array_equal(batch[4], host[4])
+    for k in range(3):
+        err = rel_err(batch[0][k], host[0][k])
+        print("mixed n", batch[0][k].shape[0], "device against stable_fit_host", err, "response", response[k])
+        assert err <= 100.0 * response[k]
+
+
+def test_length_one_trajectories_change_no_bit():
+    """The ragged case without its length-1 trajectories (stablefit_cases.without_lone_rows: the rows that remain keep
+    their row split and their order, one lone row staying as padding at the end of the first split): the same design
+    rows in the same splits, so the coefficients are equal, bit for bit."""
+    lens, obs, ctrls = data("sweep_ragged")
+    l2, o2, c2 = without_lone_rows(lens, obs, ctrls)
+    assert len(l2) < len(lens) and list(l2).count(1) == 1
+    a = _lib.stable_fit(lens, obs, ctrls, [basis("sweep_ragged")])
+    b = _lib.stable_fit(l2, o2, c2, [basis("sweep_ragged")])
+    assert a[1][0] == 0
+    for x, y in zip(a[1:], b[1:]):
+        assert np.array_equal(x, y)
+    assert np.array_equal(a[0][0], b[0][0])
 
 
 def test_refusals():
