@@ -2,13 +2,16 @@
 //
 // lqr_gains_kernel: one workgroup per Riccati problem, problems of different state dimension in one launch.
 // Each problem runs the reference's recursion from P = F (padded to the model state):
-//     M = P^T [A | B]                         (n x (n+nu))
-//     G = [A | B]^T M                         ((n+nu) x (n+nu)): G_AA = A^T P A, G_BA = B^T P A, G_BB = B^T P B
+//     M = P [A | B]                           (n x (n+nu))
+//     G = [A | B]^T M                         ((n+nu) x (n+nu)): G_AA = A^T P A, G_AB = A^T P B (upper right),
+//                                             G_BA = B^T P A (lower left), G_BB = B^T P B
 //     X = (R + G_BB)^-1 G_BA                  (Gauss-Jordan with partial pivoting, nu <= 16, in LDS)
-//     P <- (G_AA - G_BA^T X) + Q
-// horizon + 1 times, and returns K = -X of the last P.  P is symmetric up to rounding, so P^T [A | B] is the
-// reference's P [A | B] to that rounding; reading P by rows of P^T keeps every load of the products
-// coalesced.  Every entry of every product is ONE thread's sequential sum over k = 0 .. K-1, so the result of
+//     P <- (G_AA - G_AB X) + Q
+// horizon + 1 times, and returns K = -X of the last P.  Nothing is assumed symmetric: Q, F and R are taken as
+// given, as the reference takes them, and P is then not symmetric either.  The workspace holds P TRANSPOSED
+// (Pt[k][i] = P[i][k]), so lqr_gemm_tn's X^T Y with X = Pt is P [A | B] with every load of the product
+// coalesced; the update transposes 8 x 8 blocks between the lanes of a wave, so it loads and stores runs of 8.
+// Every entry of every product is ONE thread's sequential sum over k = 0 .. K-1, so the result of
 // a problem does not depend on which other problems share the launch or on their order.
 //
 // lqr_ctrl_kernel / lqr_record_kernel: one control step of the closed loop (FiniteHorizonLQR.run,
@@ -22,6 +25,7 @@ namespace ampc {
 constexpr int kLqrMaxN = 256, kLqrMaxNu = 16;
 constexpr int kLqrThreads = 256;
 constexpr int kLqrTile = 64, kLqrKt = 16;
+static_assert(kLqrThreads % 64 == 0, "the update of P hands values between the lanes of whole 64-lane waves");
 
 // One Riccati problem.  Read field by field through a global pointer (uniform, scalar loads): a copy of the
 // struct in registers indexed at run time is what spilled the plans' model table to scratch.
@@ -97,8 +101,8 @@ __global__ __launch_bounds__(kLqrThreads) void lqr_gains_kernel(const LqrDesc* _
   const int n = d->n, nu = d->nu, no = d->no, H = d->horizon, id = d->id;
   const double* __restrict__ ab = d->ab;
   const int m = n + nu, w = nu + n;          // w: width of the augmented system [S | G_BA]
-  double* P = ws + d->ws;
-  double* M = P + (size_t)n * n;
+  double* Pt = ws + d->ws;                   // P transposed: Pt[k][i] = P[i][k]
+  double* M = Pt + (size_t)n * n;
   double* G = M + (size_t)n * m;
   const double* Q = cost + d->cost;
   const double* R = Q + (size_t)no * no;
@@ -107,12 +111,12 @@ __global__ __launch_bounds__(kLqrThreads) void lqr_gains_kernel(const LqrDesc* _
   const int t = threadIdx.x;
   for (int e = t; e < n * n; e += kLqrThreads) {
     const int i = e / n, j = e - i * n;
-    P[e] = (i < no && j < no) ? F[i * no + j] : 0.0;
+    Pt[e] = (i < no && j < no) ? F[j * no + i] : 0.0;
   }
   if (t == 0) s_bad = 0;
   __syncthreads();
   for (int it = 0; it <= H + 1; ++it) {      // H + 1 Riccati updates (lqr.py:36-40), then the gain (:42)
-    lqr_gemm_tn(P, n, ab, m, M, m, n, m, n, tiles);
+    lqr_gemm_tn(Pt, n, ab, m, M, m, n, m, n, tiles);
     __syncthreads();
     lqr_gemm_tn(ab, m, M, m, G, m, m, m, n, tiles);
     __syncthreads();
@@ -163,12 +167,24 @@ __global__ __launch_bounds__(kLqrThreads) void lqr_gains_kernel(const LqrDesc* _
       }
       break;
     }
-    for (int e = t; e < n * n; e += kLqrThreads) {
-      const int i = e / n, j = e - i * n;
-      double y = 0.0;
-      for (int r = 0; r < nu; ++r) y = fma(G[(size_t)(n + r) * m + i], aug[r * w + nu + j], y);
-      const double q = (i < no && j < no) ? Q[i * no + j] : 0.0;
-      P[e] = (G[(size_t)i * m + j] - y) + q;
+    // P[i][j] = (G_AA[i][j] - sum_r G_AB[i][r] X[r][j]) + Q[i][j] in 8 x 8 blocks, one per wave at a time: lane
+    // (a, b) computes P[i0 + a][j0 + b] along rows of G, X and Q, takes P[i0 + b][j0 + a] from lane (b, a) and
+    // stores it to Pt[j0 + a][i0 + b]: loads and stores both run over 8 consecutive doubles, with no barrier
+    {
+      const int lane = t & 63, a = lane >> 3, b = lane & 7, nb = (n + 7) >> 3;
+      for (int blk = t >> 6; blk < nb * nb; blk += kLqrThreads / 64) {   // (uniform in the wave)
+        const int bi = blk / nb, i0 = 8 * bi, j0 = 8 * (blk - bi * nb);
+        const int i = i0 + a, j = j0 + b;
+        double v = 0.0;
+        if (i < n && j < n) {
+          double y = 0.0;
+          for (int r = 0; r < nu; ++r) y = fma(G[(size_t)i * m + n + r], aug[r * w + nu + j], y);
+          const double q = (i < no && j < no) ? Q[i * no + j] : 0.0;
+          v = (G[(size_t)i * m + j] - y) + q;
+        }
+        v = __shfl(v, 8 * b + a);              // every lane of the wave takes part
+        if (i0 + b < n && j0 + a < n) Pt[(size_t)(j0 + a) * n + i0 + b] = v;
+      }
     }
     __syncthreads();
   }

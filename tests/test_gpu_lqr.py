@@ -269,7 +269,7 @@ def _mixed_batch(B, seed):
 
 
 # The batch's random costs condition R + B'PB less well than the goldens: two valid association orders of the same
-# recursion in numpy (the reference's, and the device's P'[A | B] then [A | B]'M) differ by up to 2.6e-11 of max|K|
+# recursion in numpy (the reference's, and the device's P [A | B] then [A | B]'M) differ by up to 2.6e-11 of max|K|
 # on this batch (measured).  The device against the reference's order: MIXED_GAIN_TOL.
 MIXED_GAIN_TOL = 1e-9
 

@@ -1,4 +1,5 @@
-"""LQR controller surface without a GPU: LQRFactory's space, the refusals, the tuning-configuration keys."""
+"""LQR controller surface without a GPU: LQRFactory's space, the refusals, the tuning-configuration keys; the host
+gain and the numpy model of the gain kernel at the edge cases (lqr_edge_cases.py) against long double."""
 import numpy as np
 import pytest
 
@@ -7,6 +8,7 @@ from autompc_amd.control import LQR, LQRFactory, FiniteHorizonLQR, InfiniteHoriz
 from autompc_amd.control import lqr as lqr_mod
 from autompc_amd.sysid import ARX
 from autompc_amd.tuning.configs import candidate_from_config, sample_pipeline_configs
+import lqr_edge_cases as E
 
 
 def _system(no=4, nu=1):
@@ -64,6 +66,40 @@ def test_horizon_outside_factory_range_refused():
     for h in (0, 1001):
         with pytest.raises(ValueError, match="1..1000"):
             LQR(s, _task(s), ARX(s, history=2), "true", h)
+
+
+@pytest.mark.parametrize("name", list(E.CASES))
+def test_host_gain_against_long_double(name):
+    """lqr_gain_host at the edge cases (tile edges, non-symmetric Q / F / R, pivoting R) against the long-double
+    recursion of tests/golden/lqr_edges.npz."""
+    arrays = E.make_case(name)
+    fx = E.fixture()
+    np.testing.assert_array_equal(E.checksum(arrays), fx["checksum_" + name])
+    K = lqr_mod.lqr_gain_host(*arrays, E.CASES[name]["horizon"])
+    assert E.rel_err(K, fx["K_" + name]) <= 1e-13
+
+
+@pytest.mark.parametrize("name", list(E.CASES))
+def test_kernel_model_against_long_double(name):
+    """The numpy model of lqr_gains_kernel's arithmetic (lqr_edge_cases.kernel_model): within the device's own
+    tolerance of the long-double gain on every cost kind, and the row exchanges the fixture recorded -- one or more in
+    every solve of a pivoting case, none anywhere else."""
+    arrays = E.make_case(name)
+    fx = E.fixture()
+    np.testing.assert_array_equal(E.checksum(arrays), fx["checksum_" + name])
+    K, status, counts = E.kernel_model(*arrays, E.CASES[name]["horizon"])
+    assert status == 0
+    assert E.rel_err(K, fx["K_" + name]) <= E.tolerance(fx["host_err_" + name])
+    np.testing.assert_array_equal(counts, fx["exchanges_" + name])
+    assert min(counts) >= 1 if E.pivoting(name) else max(counts) == 0
+
+
+def test_kernel_model_singular():
+    A, B, Q, R, F = E.make_case("n17_u16_o17_diag")
+    Rs = np.diag(np.arange(1.0, 17.0))
+    Rs[7, 7] = 0.0
+    K, status, _ = E.kernel_model(A, B, 0 * Q, Rs, 0 * F, 2)
+    assert status == 1 and np.all(np.isnan(K))
 
 
 def test_mppi_and_ilqr_configs_unchanged():
