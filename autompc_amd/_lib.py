@@ -123,6 +123,11 @@ SIGNATURES = {
                                c_double, c_double, _dp, _ip, _dp, _ip]),
     "ampc_stable_fit": (c_int, [c_int, c_int, _ip, c_int, c_int, _dp, _dp, c_int, _ip, _ip, _dp, c_double, _dp, _ip,
                                 _dp, _ip, _ip, _dp]),
+    "ampc_mlpfit_create": (c_int, [c_int, c_void_p, c_int, _ip, _ip, _ip, _dp, POINTER(ctypes.c_longlong), c_void_p,
+                                   c_void_p, c_int, c_int, c_void_p, ctypes.c_longlong, POINTER(c_void_p)]),
+    "ampc_mlpfit_run_epoch": (c_int, [c_void_p, c_void_p]),
+    "ampc_mlpfit_steps": (c_int, [c_void_p, POINTER(ctypes.c_longlong)]),
+    "ampc_mlpfit_destroy": (c_int, [c_void_p]),
 }
 
 
@@ -894,6 +899,55 @@ class LqrPlan:
                                                    len(kinds), iptr(kinds), dptr(params), dptr(scores), dptr(obs),
                                                    dptr(ctl)))
         return scores, obs, ctl
+
+
+class MlpFitPlan:
+    """ampc_mlpfit_*: the MLP training loop for a table of models over one data set.  Every array is DEVICE memory the
+    caller owns and keeps alive (addresses, e.g. ``tensor.data_ptr()``); the plan owns Adam's state."""
+
+    MAX_HIDDEN, MAX_WIDTH, MAX_IN, MAX_OUT, MAX_BATCH = 4, 256, 80, 64, 4096
+
+    def __init__(self, n_hidden, dims, activations, lrs, param_offsets, feed_ptr, target_ptr, n_rows, n_batch,
+                 params_ptr, n_params, device=0, stream=None):
+        """dims [K][6] int32 (input, hidden widths, output, padding), param_offsets [K] int64 (doubles)."""
+        lib = load()
+        if lib.ampc_device_count() <= 0:
+            raise AmpcError("no HIP device visible: the MI355X path cannot run here "
+                            "(there is no CPU fallback by design)")
+        self.lib = lib
+        nh = np.ascontiguousarray(n_hidden, dtype=np.int32)
+        K = self.K = len(nh)
+        dims = np.ascontiguousarray(dims, dtype=np.int32).reshape(K, 6)
+        acts = np.array([ACTIVATIONS[a] for a in activations], dtype=np.int32)
+        lrs = as_f64(lrs).reshape(K)
+        offs = np.ascontiguousarray(param_offsets, dtype=np.int64).reshape(K)
+        self._p = c_void_p()
+        check(lib.ampc_mlpfit_create(int(device), c_void_p(stream) if stream else None, K, iptr(nh), iptr(dims),
+                                     iptr(acts), dptr(lrs), offs.ctypes.data_as(POINTER(ctypes.c_longlong)),
+                                     c_void_p(feed_ptr), c_void_p(target_ptr), int(n_rows), int(n_batch),
+                                     c_void_p(params_ptr), int(n_params), ctypes.byref(self._p)))
+        _live_plans.add(self)
+
+    def run_epoch(self, idx_ptr):
+        """One epoch on the row orders idx [K][n_rows] int32 (device address); only enqueues."""
+        check(self.lib.ampc_mlpfit_run_epoch(self._p, c_void_p(idx_ptr)))
+
+    @property
+    def steps(self):
+        n = ctypes.c_longlong(0)
+        check(self.lib.ampc_mlpfit_steps(self._p, ctypes.byref(n)))
+        return int(n.value)
+
+    def close(self):
+        if getattr(self, "_p", None) is not None and self._p:
+            self.lib.ampc_mlpfit_destroy(self._p)
+            self._p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def _fit_data(traj_len, obs, ctrls):

@@ -27,7 +27,7 @@ class ModelEvaluator(ABC):
     ``(model, [Trajectory]) -> float``."""
 
     def __init__(self, system, trajs, metric, rng, horizon=1, linear_fit="host", linear_kstep="host",
-                 sindy_kstep="host", sindy_fit="host", lasso_fit="host", stable_fit="host"):
+                 sindy_kstep="host", sindy_fit="host", lasso_fit="host", stable_fit="host", mlp_fit="torch"):
         """linear_fit: how ``evaluate_batch`` fits ARX / Koopman models -- "host": each by its own ``train()``;
         "device": all of a batch by one ``sysid.linear_fit.fit_linear_models`` call (one Gram pass on the device,
         equal configurations fitted once).
@@ -43,6 +43,9 @@ class ModelEvaluator(ABC):
         stable_fit: with ``linear_fit="device"``, how that call fits Koopman models of method "stable" -- "host": each
         by its own ``train()``, which refuses the method; "device": by ``ampc_stable_fit``, what it declines by
         ``sysid.stable_fit.stabilize_host`` (``fit_linear_models(..., stable="device")``).
+        mlp_fit: how ``evaluate_batch`` fits MLP models -- "torch": the lockstep PyTorch fit (``fit_mlps``); "device":
+        the library's own training kernels (``fit_mlps(..., fit="device")``, ampc_mlpfit_*: one launch chain for any
+        mix of shapes); ``last_mlp_fit`` holds what the call returned.
         ``last_kstep`` holds the ``KstepReport`` of the last ``evaluate_batch`` (``host_fallbacks``)."""
         if linear_fit not in ("host", "device"):
             raise ValueError("linear_fit must be 'host' or 'device'")
@@ -56,6 +59,10 @@ class ModelEvaluator(ABC):
             raise ValueError("lasso_fit must be 'host' or 'device'")
         if stable_fit not in ("host", "device"):
             raise ValueError("stable_fit must be 'host' or 'device'")
+        if mlp_fit not in ("torch", "device"):
+            raise ValueError("mlp_fit must be 'torch' or 'device'")
+        self.mlp_fit = mlp_fit
+        self.last_mlp_fit = None
         self.linear_fit = linear_fit
         self.lasso_fit = lasso_fit
         self.stable_fit = stable_fit
@@ -100,7 +107,7 @@ class ModelEvaluator(ABC):
             m.jit_kernels = False
         mlps = [m for m in models if isinstance(m, MLP)]
         if mlps:
-            fit_mlps(mlps, train_trajs)
+            self.last_mlp_fit = fit_mlps(mlps, train_trajs, fit=self.mlp_fit)
         others = [m for m in models if not isinstance(m, MLP)]
         if self.linear_fit == "device":
             from ..sysid.linear import ARX, Koopman

@@ -169,14 +169,15 @@ class MLP(Model):
         self._invalidate()                # weights must be re-staged
 
     # -- training (PyTorch, outside the hot path; mlp.py:177-217) ------------------------
-    def train(self, trajs, silent=False, seed=100):
+    def train(self, trajs, silent=False, seed=100, fit="torch"):
         """The reference's fit -- normalisers from the data, then n_train_iters epochs of Adam on SmoothL1 over
         shuffled mini-batches, with the reference's initial weights (torch.manual_seed(self.seed) before the
         layers are built) and mini-batch order (torch.manual_seed(seed) + DataLoader(shuffle=True)) -- run by
         sysid/mlp_fit.py on the GPU when there is one (HIP-graph-captured steps), else on the CPU.  The
-        fitted parameters stay on the device and are staged from there (ampc_set_mlp_dev)."""
+        fitted parameters stay on the device and are staged from there (ampc_set_mlp_dev).  fit="device": the same
+        training step in the library's own HIP kernels (``mlp_fit.DeviceFit``, ampc_mlpfit_*; needs a GPU)."""
         from .mlp_fit import fit_mlps
-        fit_mlps([self], trajs, train_seed=seed)
+        fit_mlps([self], trajs, train_seed=seed, fit=fit)
 
     def _adopt_fit(self, ws, bs, norms, norms_dev):
         """Take over fitted parameters: float64 torch tensors `ws`, `bs` (any device) plus the data's normalisers

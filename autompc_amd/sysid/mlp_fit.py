@@ -29,6 +29,12 @@ Training stays PyTorch; what this module adds is the SHAPE of the 
 * the fitted parameters stay on the device; ``MLP.stage_into`` hands their addresses to
   ``ampc_set_mlp_dev`` (no host round trip).  The numpy copies ``get_parameters`` needs are fetched lazily.
 
+``fit_mlps(..., fit="device")`` (opt-in) runs the same training step in the library's own HIP kernels instead
+(``DeviceFit``, ``ampc_mlpfit_*``, csrc/mlpfit_kernels.hpp): a table of models of ANY mix of depth, widths, activation
+and learning rate is one chain of launches per optimiser step -- one per layer forward, one per layer backward -- so
+the models of a batch are grouped by (epochs, batch size) only.  Initial weights and epoch orders are the same host
+streams as above.  The torch path stays the default and the yardstick.
+
 ``fit_reference_style`` is the plain ``nn.Linear`` + ``torch.optim.Adam`` + autograd loop, one model, kept
 as the cross-check of the hand-written backward pass / update and as the sequential baseline of
 ``tools/model_axis_rate.py``.
@@ -354,32 +360,198 @@ class LockstepFit:
         bs = [self.W[l][k, :d[l + 1], self.dmax[l]].contiguous() for l in range(self.nl)]
         return ws, bs
 
+# -- K models of any shapes, the library's own training kernels -------------------------------------------
+DEVICE_MAX_HIDDEN, DEVICE_MAX_WIDTH, DEVICE_MAX_IN, DEVICE_MAX_OUT, DEVICE_MAX_BATCH = 4, 256, 80, 64, 4096
+_DIMS_STRIDE = DEVICE_MAX_HIDDEN + 2
 
-def fit_mlps(models, trajs, train_seed=100, device=None, use_graphs=None):
-    """Fit every model of `models` (autompc_amd.sysid.MLP, any mix of shapes) on `trajs`, each exactly as its
-    own ``train(trajs, seed=train_seed)`` would, grouped into lockstep fits by (depth, activation, epochs,
-    batch size).  Returns {"groups": n, "fit_s": wall seconds, "steps": optimiser steps per model}."""
+
+def device_fit_supports(dims, n_batch):
+    """Can ampc_mlpfit_* train a network of layer widths `dims` (input, hidden..., output) on mini-batches of
+    `n_batch` rows?  (The inference kernels' own limits, include/autompc_hip.h.)"""
+    dims = [int(v) for v in dims]
+    return (1 <= len(dims) - 2 <= DEVICE_MAX_HIDDEN and 1 <= dims[0] <= DEVICE_MAX_IN
+            and 1 <= dims[-1] <= DEVICE_MAX_OUT and all(1 <= h <= DEVICE_MAX_WIDTH for h in dims[1:-1])
+            and 1 <= int(n_batch) <= DEVICE_MAX_BATCH)
+
+
+def pack_device_models(dims_list):
+    """The flat parameter layout ampc_mlpfit_create takes: model after model, per layer the weight [out][in]
+    row-major and then the bias [out].  Returns {"n_hidden" [K] int32, "dims" [K][6] int32 (zero padded), "offsets" [K]
+    int64 (a model's first double), "layers": per model a list of (weight offset, bias offset, out, in), "n_params"}."""
+    K = len(dims_list)
+    n_hidden = np.zeros(K, dtype=np.int32)
+    dims = np.zeros((K, _DIMS_STRIDE), dtype=np.int32)
+    offsets = np.zeros(K, dtype=np.int64)
+    layers, o = [], 0
+    for k, d in enumerate(dims_list):
+        d = [int(v) for v in d]
+        if not 1 <= len(d) - 2 <= DEVICE_MAX_HIDDEN:
+            raise ValueError("a device-fitted MLP has 1..%d hidden layers" % DEVICE_MAX_HIDDEN)
+        n_hidden[k] = len(d) - 2
+        dims[k, :len(d)] = d
+        offsets[k] = o
+        mine = []
+        for fan_in, fan_out in zip(d[:-1], d[1:]):
+            mine.append((o, o + fan_out * fan_in, fan_out, fan_in))
+            o += fan_out * fan_in + fan_out
+        layers.append(mine)
+    return {"n_hidden": n_hidden, "dims": dims, "offsets": offsets, "layers": layers, "n_params": o}
+
+
+def layer_views(flat, layers):
+    """The per-layer views (weights [out][in], biases [out]) of one model in the flat buffer `flat` (a 1-d tensor or
+    array); `layers` is that model's entry of pack_device_models(...)["layers"]."""
+    ws = [flat[w:w + fo * fi].reshape(fo, fi) for w, _, fo, fi in layers]
+    bs = [flat[b:b + fo] for _, b, fo, _ in layers]
+    return ws, bs
+
+
+def require_device_fit(device=None):
+    """The torch device fit="device" runs on; raises when there is none (no CPU fallback by design)."""
     import torch
+    from .. import _lib
+    dev = torch.device(device or "cuda") if torch.cuda.is_available() else None
+    if dev is None or dev.type != "cuda" or _lib.load().ampc_device_count() <= 0:
+        raise _lib.AmpcError("fit='device' trains MLPs with the library's HIP kernels and needs a usable GPU: none is "
+                             "visible here (there is no CPU fallback by design; fit='torch' runs anywhere)")
+    return torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
+
+
+class DeviceFit:
+    """K MLPs of ANY mix of depth, widths, activation and learning rate over one data set, trained by the
+    library's kernels (ampc_mlpfit_*): LockstepFit's surface -- `run(n_iter)`, `parameters(k)` --; `act` is one name
+    or one per model.  The parameters live in ONE flat device tensor laid out by pack_device_models; `parameters`
+    returns views of it (what ampc_set_mlp_dev reads, no copy)."""
+
+    def __init__(self, dims_list, act, lrs, init_seeds, feed, target, n_batch, train_seeds=None, device=None):
+        import torch
+        from .. import _lib
+        self.torch = torch
+        K = self.K = len(dims_list)
+        acts = [act] * K if isinstance(act, str) else list(act)
+        if len(acts) != K or any(a not in ACTS for a in acts):
+            raise NotImplementedError("Currently supported nonlinearity: relu, selu, tanh, sigmoid")
+        self.dims_list = [tuple(int(v) for v in d) for d in dims_list]
+        self.acts = acts
+        self.n_batch = int(n_batch)
+        for d in self.dims_list:
+            if not device_fit_supports(d, self.n_batch):
+                raise ValueError("layer widths %r / n_batch %d are over the device fit's limits (1..%d hidden layers "
+                                 "of <= %d units, <= %d inputs, <= %d outputs, n_batch <= %d)"
+                                 % (d, self.n_batch, DEVICE_MAX_HIDDEN, DEVICE_MAX_WIDTH, DEVICE_MAX_IN,
+                                    DEVICE_MAX_OUT, DEVICE_MAX_BATCH))
+        if any(d[0] != self.dims_list[0][0] or d[-1] != self.dims_list[0][-1] for d in self.dims_list):
+            raise ValueError("the models of one fit share the input and output width")
+        self.device = require_device_fit(device)
+        f64 = torch.float64
+        self.feed = feed.to(self.device, f64).contiguous()
+        self.target = target.to(self.device, f64).contiguous()
+        self.n = int(self.feed.shape[0])
+        if self.feed.shape[1] != self.dims_list[0][0] or self.target.shape[1] != self.dims_list[0][-1] \
+                or self.target.shape[0] != self.n:
+            raise ValueError("feed / target do not have the models' input / output width")
+        self.layout = pack_device_models(self.dims_list)
+        host = torch.zeros(self.layout["n_params"], dtype=f64)
+        for k, (d, seed) in enumerate(zip(self.dims_list, init_seeds)):
+            ws, bs = initial_parameters(seed, d)
+            hw, hb = layer_views(host, self.layout["layers"][k])
+            for l in range(len(ws)):
+                hw[l].copy_(ws[l])
+                hb[l].copy_(bs[l])
+        self.flat = host.to(self.device)
+        # models with equal train seeds share one row order (and one generator)
+        train_seeds = [100] * K if train_seeds is None else [int(s) for s in train_seeds]
+        self._seeds = sorted(set(train_seeds))
+        self.gens = [seeded_generator(s) for s in self._seeds]
+        self._order_of = torch.tensor([self._seeds.index(s) for s in train_seeds], dtype=torch.int64)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device)
+            self._plan = _lib.MlpFitPlan(self.layout["n_hidden"], self.layout["dims"], acts, [float(v) for v in lrs],
+                                         self.layout["offsets"], self.feed.data_ptr(), self.target.data_ptr(), self.n,
+                                         self.n_batch, self.flat.data_ptr(), self.layout["n_params"],
+                                         device=self.device.index, stream=stream.cuda_stream)
+        self._stream = stream
+        self.steps_done = 0
+        self.kernel_s = 0.0
+
+    def run(self, n_iter):
+        """`n_iter` more epochs (Adam's moments and step count persist between calls)."""
+        torch = self.torch
+        per_epoch = -(-self.n // self.n_batch)
+        t0 = time.perf_counter()
+        orders = []                                    # this call's uploaded row orders, alive until the stream is done
+        with torch.cuda.device(self.device), torch.cuda.stream(self._stream):
+            for _ in range(int(n_iter)):
+                perms = torch.stack([epoch_order(g, self.n) for g in self.gens]).to(torch.int32)
+                idx = perms[self._order_of].contiguous().to(self.device, non_blocking=True)
+                orders.append(idx)
+                self._plan.run_epoch(idx.data_ptr())
+                self.steps_done += per_epoch
+            self._stream.synchronize()
+        del orders
+        self.kernel_s += time.perf_counter() - t0
+
+    def parameters(self, k):
+        """Model k's weights [out][in] and biases [out]: float64 views of the flat device buffer."""
+        return layer_views(self.flat, self.layout["layers"][k])
+
+    def close(self):
+        self._plan.close()
+
+
+def fit_mlps(models, trajs, train_seed=100, device=None, use_graphs=None, fit="torch"):
+    """Fit every model of `models` (autompc_amd.sysid.MLP, any mix of shapes) on `trajs`, each exactly as its
+    own ``train(trajs, seed=train_seed)`` would.  fit="torch": grouped into lockstep fits by (depth, activation,
+    epochs, batch size).  fit="device": grouped by (epochs, batch size) only and trained by the library's kernels
+    (``DeviceFit``; needs a GPU), models over its limits by the torch lockstep path.  Returns {"groups": n, "fit_s":
+    wall seconds, "steps": optimiser steps per model, "device_models": fitted by the kernels, "torch_models": by
+    torch}."""
+    import torch
+    if fit not in ("torch", "device"):
+        raise ValueError("fit must be 'torch' or 'device'")
     t0 = time.perf_counter()
+    if fit == "device":
+        device = require_device_fit(device)
     XU, dY, xm, xs, dm, ds = training_arrays(trajs)
     feed_np, target_np = normalised(XU, dY, xm, xs, dm, ds)
     feed, target = torch.from_numpy(feed_np), torch.from_numpy(target_np)
-    groups = {}
-    for m in models:
-        n_iter, n_batch, _ = m._train_data
-        groups.setdefault((len(m.hidden_sizes), m.nonlintype, int(n_iter), int(n_batch)), []).append(m)
     dev = torch.device(device or ("cuda" if torch.cuda.is_available() else "cpu"))
     norm_dev = [torch.from_numpy(np.ascontiguousarray(v)).to(dev) for v in (xm, xs, dm, ds)]
     steps = 0
+    torch_models, device_groups = list(models), {}
+    if fit == "device":
+        torch_models = []
+        for m in models:
+            n_iter, n_batch, _ = m._train_data
+            dims = [XU.shape[1]] + list(m.hidden_sizes) + [dY.shape[1]]
+            if device_fit_supports(dims, n_batch) and m.nonlintype in ACTS:
+                device_groups.setdefault((int(n_iter), int(n_batch)), []).append(m)
+            else:
+                torch_models.append(m)
+    for (n_iter, n_batch), ms in device_groups.items():
+        dims = [[XU.shape[1]] + list(m.hidden_sizes) + [dY.shape[1]] for m in ms]
+        dfit = DeviceFit(dims, [m.nonlintype for m in ms], [m._train_data[2] for m in ms], [m.seed for m in ms], feed,
+                         target, n_batch, train_seeds=[train_seed] * len(ms), device=dev)
+        dfit.run(n_iter)
+        dfit.close()
+        steps = max(steps, dfit.steps_done)
+        for k, m in enumerate(ms):
+            ws, bs = dfit.parameters(k)
+            m._adopt_fit(ws, bs, (xm, xs, dm, ds), norm_dev)
+    groups = {}
+    for m in torch_models:
+        n_iter, n_batch, _ = m._train_data
+        groups.setdefault((len(m.hidden_sizes), m.nonlintype, int(n_iter), int(n_batch)), []).append(m)
     for (depth, act, n_iter, n_batch), ms in groups.items():
         dims = [[XU.shape[1]] + list(m.hidden_sizes) + [dY.shape[1]] for m in ms]
-        fit = LockstepFit(dims, act, [m._train_data[2] for m in ms], [m.seed for m in ms], feed, target, n_batch,
-                          train_seeds=[train_seed] * len(ms), device=dev, use_graphs=use_graphs)
-        fit.run(n_iter)
-        steps = max(steps, fit.steps_done)
+        fit_ = LockstepFit(dims, act, [m._train_data[2] for m in ms], [m.seed for m in ms], feed, target, n_batch,
+                           train_seeds=[train_seed] * len(ms), device=dev, use_graphs=use_graphs)
+        fit_.run(n_iter)
+        steps = max(steps, fit_.steps_done)
         for k, m in enumerate(ms):
-            ws, bs = fit.parameters(k)
+            ws, bs = fit_.parameters(k)
             m._adopt_fit(ws, bs, (xm, xs, dm, ds), norm_dev)
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
-    return {"groups": len(groups), "fit_s": time.perf_counter() - t0, "steps": steps}
+    return {"groups": len(groups) + len(device_groups), "fit_s": time.perf_counter() - t0, "steps": steps,
+            "device_models": len(models) - len(torch_models), "torch_models": len(torch_models)}

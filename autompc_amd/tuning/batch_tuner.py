@@ -46,7 +46,7 @@ class BatchPipelineTuner:
     def __init__(self, system, evaluator, batch_size=64, sampler=None, truedyn_noise="device",
                  eval_kwargs=None, keep_trajs=False, balance=None, models=None, model_factory=None,
                  trajs=None, as_configs=False, linear_fit="host", sindy_fit="host", lasso_fit="host",
-                 stable_fit="host"):
+                 stable_fit="host", mlp_fit="torch"):
         """truedyn_noise: the noise mode of the controllers scored against the true dynamics
         (MPPI(noise=...): "device" Philox, or "numpy" / "numpy_device" = the reference's global
         legacy stream).  eval_kwargs: extra keyword arguments for every ``evaluator.evaluate`` call
@@ -72,6 +72,10 @@ class BatchPipelineTuner:
         stable_fit: with ``linear_fit="device"``, "device" lets that call fit Koopman configurations of method
         "stable" by ``ampc_stable_fit`` (``fit_linear_models(..., stable="device")``; what it declines is fitted by
         ``sysid.stable_fit.stabilize_host``) instead of handing them to ``train()``, which refuses the method.
+
+        mlp_fit: "torch" fits a shard's MLP configurations by the lockstep PyTorch fit; "device" by the library's own
+        training kernels (``fit_mlps(..., fit="device")``, ampc_mlpfit_*: any mix of shapes in one launch chain);
+        ``mlp_device_fits`` counts the models those kernels fitted.
 
         sindy_fit: the same for SINDy configurations ("device": one ``sysid.sindy_fit.fit_sindy_models`` call per
         shard); ``sindy_host_fits`` counts the ``train()`` calls it made.
@@ -112,6 +116,10 @@ class BatchPipelineTuner:
             raise ValueError("lasso_fit must be 'host' or 'device'")
         if stable_fit not in ("host", "device"):
             raise ValueError("stable_fit must be 'host' or 'device'")
+        if mlp_fit not in ("torch", "device"):
+            raise ValueError("mlp_fit must be 'torch' or 'device'")
+        self.mlp_fit = mlp_fit
+        self.mlp_device_fits = 0
         self.linear_fit = linear_fit
         self.lasso_fit = lasso_fit
         self.stable_fit = stable_fit
@@ -201,7 +209,7 @@ class BatchPipelineTuner:
             from ..sysid.mlp_fit import fit_mlps
             mlps = [m for m in fresh.values() if isinstance(m, MLP)]
             if mlps:
-                fit_mlps(mlps, self.trajs)
+                self.mlp_device_fits += fit_mlps(mlps, self.trajs, fit=self.mlp_fit)["device_models"]
             others = [m for m in fresh.values() if not isinstance(m, MLP)]
             if self.linear_fit == "device":
                 from ..sysid.linear import ARX, Koopman

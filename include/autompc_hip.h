@@ -30,6 +30,7 @@ typedef struct ampc_handle ampc_handle;
 typedef struct ampc_mppi_plan ampc_mppi_plan;
 typedef struct ampc_ilqr_plan ampc_ilqr_plan;
 typedef struct ampc_lqr_plan ampc_lqr_plan;
+typedef struct ampc_mlpfit_plan ampc_mlpfit_plan;
 
 enum { AMPC_F64 = 0, AMPC_F32 = 1 };
 enum { AMPC_ACT_RELU = 0, AMPC_ACT_TANH = 1, AMPC_ACT_SIGMOID = 2, AMPC_ACT_SELU = 3 };
@@ -43,7 +44,8 @@ int ampc_version(void);   /* 100 * major + minor; 104: + ampc_mppi_run_legacy; 1
                            *      ampc_mppi_plan_set_models, ampc_ilqr_plan_set_models; 107: + ampc_set_mlp_dev, ampc_ilqr_plan_set_constants;
                            * 108: + ampc_kstep_errors; 109: + ampc_lqr_*; 110: + ampc_linfit_fit;
                            * 111: + ampc_kstep_errors_linear; 112: + ampc_kstep_errors_sindy;
-                           * 113: + ampc_sindy_fit; 114: + ampc_lasso_fit; + ampc_stable_fit (no bump: callers detect it by its symbol) */
+                           * 113: + ampc_sindy_fit; 114: + ampc_lasso_fit; + ampc_stable_fit, + ampc_mlpfit_* (no bump: callers detect them by
+                           *      their symbols) */
 int ampc_device_count(void);
 
 /* ---- handle ------------------------------------------------------------------------------ */
@@ -613,6 +615,38 @@ int ampc_stable_fit(int device, int n_traj, const int* traj_len, int obs_dim, in
                     const double* ctrls, int n_bases, const int* basis_n, const int* basis_kinds,
                     const double* basis_params, double tie, double* coeffs, int* status, double* error,
                     int* iterations, int* trials, double* min_margin);
+
+/* ---- MLP training (f64 only) ---------------------------------------------------------------------
+ * MLP.train's loop (autompc/sysid/mlp.py:192-217: DataLoader(shuffle=True) mini-batches, SmoothL1Loss, Adam(lr)) for
+ * n_models networks of ANY mix of depth, widths, activation and learning rate over one normalised data set, every
+ * model exactly as its own training would run.  One optimiser step is one launch per layer forward and one per layer
+ * backward for all models together (csrc/mlpfit_kernels.hpp); all ordering comes from kernel boundaries on `stream`.
+ *   stream: the hipStream_t everything is enqueued on (e.g. torch's current stream; NULL: the default stream);
+ *   n_hidden [n_models] in 1..4; dims [n_models][6]: nx + nu (<= 80), the hidden widths (<= 256), nx (<= 64), the
+ *   rest ignored -- every model has the data's input and output width; activations as ampc_set_mlp; lrs: Adam's lr;
+ *   feed_dev [n_rows][nx + nu], target_dev [n_rows][nx]: the normalised inputs and targets (mlp.py:179-190);
+ *   n_batch in 1..4096 (mlp.py:194); the ragged last batch of an epoch is kept and averaged over its own rows;
+ *   params_dev [n_params]: every model's parameters, model k from param_offsets[k] (in doubles): per layer the
+ *   weight, row-major [out][in] (torch.nn.Linear's layout), then the bias [out] -- a layer's two addresses are what
+ *   ampc_set_mlp_dev takes.  Models must not overlap.  Trained in place.
+ * feed, target, params (and idx below) are DEVICE memory of `device`, owned by the caller and alive as long as the
+ * plan; host pointers are refused.  The plan owns Adam's moments (zero at creation), the step count and the
+ * activation buffers.  Refused: shapes over the limits.  Deterministic: no atomics, every sum in a fixed order that
+ * depends on the model's own dimensions and the batch's row count only -- a model's result does not depend on the
+ * other models of the plan. */
+int ampc_mlpfit_create(int device, void* stream, int n_models, const int* n_hidden, const int* dims,
+                       const int* activations, const double* lrs, const long long* param_offsets,
+                       const double* feed_dev, const double* target_dev, int n_rows, int n_batch, double* params_dev,
+                       long long n_params, ampc_mlpfit_plan** out);
+/* One epoch (mlp.py:201-214): ceil(n_rows / n_batch) optimiser steps, step s on rows idx[k][s n_batch ..] of model k.
+ * idx_dev [n_models][n_rows] int32, device memory: each model's row order of this epoch (what its DataLoader would
+ * draw; entries outside 0..n_rows-1 are clamped into the data).  Only enqueues: idx_dev must stay valid until the
+ * stream has run the epoch.  A later call continues the same optimisation (moments and step count persist). */
+int ampc_mlpfit_run_epoch(ampc_mlpfit_plan* p, const int* idx_dev);
+/* Optimiser steps enqueued so far (Adam's t). */
+int ampc_mlpfit_steps(const ampc_mlpfit_plan* p, long long* steps);
+/* Waits for the stream, then frees what the plan owns (mlp.py has no counterpart: the optimiser is garbage collected). */
+int ampc_mlpfit_destroy(ampc_mlpfit_plan* p);
 
 /* ---- finite-horizon LQR (f64 only) ---------------------------------------------------------- */
 /* A plan of n_problems LQR controllers (reference: autompc/control/lqr.py:139-192 FiniteHorizonLQR) that keeps
