@@ -294,6 +294,20 @@ __device__ __forceinline__ void lds_barrier() {
   asm volatile("" ::: "memory");
 }
 
+// A lane's LDS address as a 32-bit value of its own (the address operand of a ds_* instruction) that the
+// compiler can no longer trace to its operands.  The tile's per-lane addresses do not change from call to
+// call, but each is one or two cheap integer instructions away from values that are live anyway, so hipcc
+// re-forms them inside a caller's time loop instead of keeping a register for them -- some two dozen VALU
+// instructions per wave and rollout step in the 16-row f64 tile, each ~8 cycles of matrix-pipe time, with
+// a third of the register file unused.  Formed once (TileNet::pin), pinned with an empty asm, and used
+// with constant offsets only (immediates of the ds_* instruction for a StaticShape).
+template <typename T> using lds_ptr = __attribute__((address_space(3))) T*;
+template <typename T> __device__ __forceinline__ lds_ptr<T> lds_pin(T* p) {
+  lds_ptr<T> q = (lds_ptr<T>)p;
+  asm volatile("" : "+v"(q));
+  return q;
+}
+
 __host__ __device__ inline int imax(int a, int b) { return a > b ? a : b; }
 __host__ __device__ inline int round_up(int a, int m) { return (a + m - 1) / m * m; }
 
@@ -485,25 +499,33 @@ __device__ __forceinline__ void load_group(rsrc_t r, unsigned so, unsigned lo, i
 // sub-groups of SG k-steps; tall f64 tiles (MT >= 2) have enough MFMA work per k-step to cover an
 // L2 round trip with SG = 4, which halves the buffer's registers (64 VGPRs).
 struct NoSide { __device__ __forceinline__ void operator()() const {} };
+struct NoGroups {};     // layer_mma_static: no pinned fragment addresses, form them from (A, a_stride, rot)
 
 // `mid` is invoked once, right after the barrier an OWN layer takes behind its first group (never
 // for !OWN): caller work placed there issues between this layer's MFMAs instead of on the serial
 // chain at the end of a step.
 // APERM: A is an activation buffer (rows stored at act_row<T>()); false for the [x | u] operand.
+// `group_at(g)`, when given, is this lane's (pinned) address of the fragments of the g-th group in the
+// order the layer consumes them -- the rotation already applied; A and rot are then not used.
 template <typename T, int NT, int MT, int KS, int G, bool PIPE = false, bool OWN = false, int SG = G,
-          bool APERM = false, typename Mid = NoSide>
+          bool APERM = false, typename Mid = NoSide, typename Groups = NoGroups>
 __device__ __forceinline__ void layer_mma_static(const T* __restrict__ A, int a_stride,
                                                  rsrc_t wr, unsigned wl, int lane,
                                                  const T (&first)[G][NT],
                                                  typename Acc<T>::type (&acc)[MT][NT], int rot = 0,
-                                                 Mid&& mid = Mid()) {
+                                                 Mid&& mid = Mid(), Groups&& group_at = Groups()) {
   static_assert(KS % G == 0 && G % SG == 0, "group sizes must divide the k extent");
   constexpr int NG = KS / G;       // groups (the unit of the rotated k order)
   constexpr int NS = KS / SG;      // sub-groups (the unit of the weight stream)
   constexpr int FS = G / SG;       // sub-groups that arrive pre-loaded in `first`
   static_assert(!OWN || (NG & (NG - 1)) == 0, "rotated k order needs a power-of-two group count");
   const int i = lane & 15, q = lane >> 4;
-  const T* arow = A + (APERM ? act_row<T>(i) : i) * a_stride + q;
+  constexpr bool PINNED = !std::is_same<typename std::decay<Groups>::type, NoGroups>::value;
+  const T* arow = A + (APERM ? act_row<T>(i) : i) * a_stride + q;        // (not used when PINNED)
+  auto sub_group = [&](int g, int sub) {
+    if constexpr (PINNED) return group_at(g) + 4 * SG * sub;
+    else return (OWN ? arow + 4 * G * ((g + rot) & (NG - 1)) : arow + 4 * G * g) + 4 * SG * sub;
+  };
   T b[2][SG][NT];
   if constexpr (FS == 1) {       // whole-group streaming: the pre-loaded group IS buffer 0
 #pragma unroll
@@ -515,7 +537,7 @@ __device__ __forceinline__ void layer_mma_static(const T* __restrict__ A, int a_
   for (int sgi = 0; sgi < NS; ++sgi) {
     if (sgi + 1 >= FS && sgi + 1 < NS) load_group<T, NT, SG>(wr, wl, (unsigned)lane * NT, sgi + 1, b[(sgi + 1) & 1]);
     const int g = sgi / FS;
-    const T* ag = (OWN ? arow + 4 * G * ((g + rot) & (NG - 1)) : arow + 4 * G * g) + 4 * SG * (sgi % FS);
+    const auto ag = sub_group(g, sgi % FS);
 #pragma unroll
     for (int kk = 0; kk < SG; ++kk) {
       T a[MT];
@@ -626,8 +648,9 @@ __device__ __forceinline__ void layer_mma_static(const T* __restrict__ A, int a_
 // lifts -- arx.py:146-162, koopman.py:166-181) and first layers of up to 20 k-steps (nx + nu <= 80).
 // Instantiated for the 64-wide tile only (W = 4, NT = 1: such models are linear, staged with a hidden
 // width equal to the state dimension); the output fragments are always resident there.
+// PINNED: the caller runs the tile in a loop and has called pin() -- see PIN below.
 template <typename T, int NT, int MT, int W, bool DERIV = false, int LEAN = 0, typename SH = DynShape,
-          bool WIDE = false>
+          bool WIDE = false, bool PINNED = false>
 struct TileNet {
   using acc_t = typename Acc<T>::type;
   static constexpr int M = 16 * MT;
@@ -719,6 +742,59 @@ struct TileNet {
   T pfn[GH][NT];
   ProbeWave<Probe::wave_time> probe;    // (empty in the product build)
 
+  // This lane's LDS addresses, pinned (lds_pin) for the kernel's lifetime.  Only where a kernel asks for
+  // it (PINNED: it calls run() in a loop; a single call gains nothing from the registers), and only in
+  // shape-specialised instantiations: there every use is the register plus an immediate, and the
+  // activation buffer a layer works on is known at compile time (two fixed sets, no swap at run time).
+  // Every other instantiation forms the addresses where it uses them.  f64 only: the f32 rollout (half the
+  // MFMA time per k-step, 116 of the 128 VGPRs that two workgroups per CU allow) measured 1.6 % SLOWER per
+  // single c3 solve with its addresses pinned (126 VGPRs) and 1 % faster at eight solves per launch; it
+  // stays as it was.
+  static constexpr bool PIN = PINNED && SH::kStatic && sizeof(T) == 8;
+  static constexpr int RS = sizeof(T) == 8 ? 4 : 1;   // acc_row(q, r) = acc_row(q, 0) + RS*r
+  static constexpr int NGH = KSH / GH;                // k-groups of a hidden -> hidden layer
+  lds_ptr<T> ep_[2][4];            // epilogue stores into activation buffer b: accumulator register r of tile (0, 0)
+  lds_ptr<const T> rd_[2][NGH];    // hidden layer reading buffer b: fragments of the g-th group in this wave's order
+  lds_ptr<const T> ro_;            // output layer: this wave's k-slice of the last hidden layer's activations
+  lds_ptr<const T> x0_;            // layer 0: fragments of [x | u]
+  lds_ptr<T> pp_, pt_;             // partials: accumulator register 0 of tile (0, 0) / the tail4 value
+  int w_;                          // the wave's index (a readfirstlane in run() is not hoisted out of a caller's loop)
+
+  // Once per kernel, next to init() (PINNED callers).  (L, lds: the map and the buffer of every later run())
+  __device__ __forceinline__ void pin(const MlpDev<T>& m_in, const TileLds& L_in, T* lds) {
+    if constexpr (PIN) {
+      const MlpDev<T> m = SH::template fold<T>(m_in);
+      const TileLds L = SH::template fold_lds<T, M, W>(L_in);
+      const int lane = threadIdx.x & 63;
+      const int w = w_ = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+      const int i = lane & 15, q = lane >> 4;
+      const int as = L.act_stride;
+      const bool pingpong = L.act2 != L.act;
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        T* buf = lds + (b ? L.act2 : L.act);
+        const bool written = b == 0 || pingpong;
+        const bool read = b == 0 ? m.n_hidden > 1 : (pingpong && m.n_hidden > 2);   // by a hidden layer
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          ep_[b][r] = written ? lds_pin(buf + (act_row<T>(acc_row<T>(q, 0)) + RS * r) * as + 16 * NT * w + i) : ep_[0][r];
+#pragma unroll
+        for (int g = 0; g < NGH; ++g) {
+          const T* grp = buf + act_row<T>(i) * as + q + 4 * GH * (OWN ? ((g + w) & (NGH - 1)) : g);
+          // (without the rotation the groups are constant offsets from the first)
+          rd_[b][g] = (read && (OWN || g == 0)) ? lds_pin(grp) : lds_ptr<const T>(nullptr);
+        }
+      }
+      const T* last = lds + ((pingpong && ((m.n_hidden - 1) & 1)) ? L.act2 : L.act);
+      ro_ = lds_pin(last + act_row<T>(i) * as + q + 4 * w * KSW);
+      x0_ = lds_pin(static_cast<const T*>(lds + L.xu + i * L.xu_stride + q));
+      const int ps = part_stride((int)sizeof(T), m.nxp);
+      T* part = lds + L.part + w * M * ps;
+      pp_ = lds_pin(part + acc_row<T>(q, 0) * ps + i);
+      pt_ = m.tail4 ? lds_pin(part + tail_row(lane) * ps + 16 + tail_col(lane)) : pp_;
+    }
+  }
+
   // Once per kernel, before the first run(): resident biases / output weights + the first prefetch.
   __device__ __forceinline__ void init(const MlpDev<T>& m_in) {
     const MlpDev<T> m = SH::template fold<T>(m_in);
@@ -762,11 +838,10 @@ struct TileNet {
 
   // Layer 0 from the resident fragments: KS k-steps, operands straight from pf0 (static indices:
   // no reinterpreted views of the member array, which the compiler answers with a stack copy).
-  template <int KS>
-  __device__ __forceinline__ void layer0_resident(const T* __restrict__ A, int a_stride, int lane,
-                                                  acc_t (&acc)[MT][NT]) const {
+  // (arow: the lane's first fragment value, A + (lane & 15) * a_stride + (lane >> 4), or its pinned address)
+  template <int KS, typename AP>
+  __device__ __forceinline__ void layer0_resident(AP arow, int a_stride, acc_t (&acc)[MT][NT]) const {
     static_assert(KS <= KS0RES, "layer 0 wider than the resident buffer");
-    const T* arow = A + (lane & 15) * a_stride + (lane >> 4);
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       T a[MT];
@@ -814,12 +889,18 @@ struct TileNet {
     const MlpDev<T> m = SH::template fold<T>(m_in);
     const TileLds L = SH::template fold_lds<T, M, W>(L_in);
     const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // PIN: the wave index is only the start of the weight streams here.  Re-read from its register and opaque,
+    // so that the streams' scalar offsets are formed where they are used, as they are behind a readfirstlane
+    // (hoisted out of a caller's loop they take more scalar registers than a wave has: they end up in VGPR lanes).
+    int w;
+    if constexpr (PIN) { w = w_; asm volatile("" : "+s"(w)); }
+    else w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int i = lane & 15, q = lane >> 4;
     AMPC_PROBE_LOCALS(probe);
     T* act = lds + L.act;            // buffer the next layer reads
     T* act_other = lds + L.act2;     // buffer the next epilogue may write (== act if single-buffered)
     const bool pingpong = L.act2 != L.act;
+    int cur = 0;                     // which of the two `act` is (a compile-time value wherever PIN)
     const int as = L.act_stride;
     const int no = m.nxp / 16;
     static_assert(WIDE || GH * NT == KSW * NOMAX, "prefetch buffer shapes must coincide");   // pfn holds either
@@ -864,35 +945,53 @@ struct TileNet {
     // of a lane's values are addressed from one base pointer with constant offsets (immediates of
     // the ds_write when the strides are compile-time, i.e. for a StaticShape): every VALU
     // instruction here costs matrix-pipe time (VALU does not overlap MFMA on gfx950).
-    auto epilogue_k = [&](int l, acc_t (&acc)[MT][NT], T* dst, auto kind_tag) {
+    // (dst = activation buffer db: 0 = L.act, 1 = L.act2)
+    auto epilogue_k = [&](int l, acc_t (&acc)[MT][NT], T* dst, int db, auto kind_tag) {
       constexpr int KIND = decltype(kind_tag)::value;
-      constexpr int RS = sizeof(T) == 8 ? 4 : 1;                    // acc_row(q, r) = acc_row(q, 0) + RS*r
       const T* bias = lds + L.bias + l * m.hpad + 16 * NT * w + i;
       T* d0 = dst + act_row<T>(acc_row<T>(q, 0)) * as + 16 * NT * w + i;   // (+ ro: bits 0-1 and >= 4 only)
       T* z0 = DERIV ? dz + (size_t)l * dz_layer_stride + (size_t)acc_row<T>(q, 0) * m.hpad + 16 * NT * w + i : nullptr;
+      auto bias_of = [&](int nt) -> T {
+        if (RESIDENT_BIAS && l < kResBias) return (l == 0) ? bias_r[0][nt] : bias_r[kResBias - 1][nt];
+        return bias[16 * nt];
+      };
+      auto emit = [&](int mt, int nt, int r, T bc) {
+        const int ro = 16 * mt + RS * r;
+        const T z = acc[mt][nt][r] + bc;
+        if constexpr (PIN) (db ? ep_[1][r] : ep_[0][r])[16 * mt * as + 16 * nt] = act_apply<T>(KIND, z);
+        else d0[ro * as + 16 * nt] = act_apply<T>(KIND, z);
+        if (DERIV) z0[(size_t)ro * m.hpad + 16 * nt] = act_deriv<T>(KIND, z);
+      };
+      if constexpr (PIN) {
+        // a row's column tiles next to each other: the compiler cannot tell that stores through different
+        // pinned addresses do not overlap, and pairs up (ds_write2) only stores that follow one another
+        T bc[NT];
 #pragma unroll
-      for (int mt = 0; mt < MT; ++mt)
+        for (int nt = 0; nt < NT; ++nt) bc[nt] = bias_of(nt);
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-          T bc;
-          if (RESIDENT_BIAS && l < kResBias) bc = (l == 0) ? bias_r[0][nt] : bias_r[kResBias - 1][nt];
-          else bc = bias[16 * nt];
+        for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int ro = 16 * mt + RS * r;
-            const T z = acc[mt][nt][r] + bc;
-            d0[ro * as + 16 * nt] = act_apply<T>(KIND, z);
-            if (DERIV) z0[(size_t)ro * m.hpad + 16 * nt] = act_deriv<T>(KIND, z);
+          for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) emit(mt, nt, r, bc[nt]);
+      } else {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+          for (int nt = 0; nt < NT; ++nt) {
+            const T bc = bias_of(nt);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) emit(mt, nt, r, bc);
           }
-        }
+      }
     };
-    auto epilogue = [&](int l, acc_t (&acc)[MT][NT], T* dst) {
+    auto epilogue = [&](int l, acc_t (&acc)[MT][NT], T* dst, int db) {
       switch (m.act) {
-        case 0: epilogue_k(l, acc, dst, std::integral_constant<int, 0>{}); break;
-        case 1: epilogue_k(l, acc, dst, std::integral_constant<int, 1>{}); break;
-        case 2: epilogue_k(l, acc, dst, std::integral_constant<int, 2>{}); break;
-        case 4: epilogue_k(l, acc, dst, std::integral_constant<int, 4>{}); break;
-        default: epilogue_k(l, acc, dst, std::integral_constant<int, 3>{}); break;
+        case 0: epilogue_k(l, acc, dst, db, std::integral_constant<int, 0>{}); break;
+        case 1: epilogue_k(l, acc, dst, db, std::integral_constant<int, 1>{}); break;
+        case 2: epilogue_k(l, acc, dst, db, std::integral_constant<int, 2>{}); break;
+        case 4: epilogue_k(l, acc, dst, db, std::integral_constant<int, 4>{}); break;
+        default: epilogue_k(l, acc, dst, db, std::integral_constant<int, 3>{}); break;
       }
     };
 
@@ -912,16 +1011,20 @@ struct TileNet {
       // first group of hidden layer 1: in flight under layer 0's MFMAs (64-row tiles have no
       // registers to spare for that and fetch it after the MFMAs instead)
       if (resident0(m)) {
+        const auto arow0 = [&] {
+          if constexpr (PIN) return x0_;
+          else return A + i * L.xu_stride + q;
+        }();
         switch (m.k1p) {   // one fully unrolled variant per padded input width, no loads
-          case 8: layer0_resident<2>(A, L.xu_stride, lane, acc); break;
-          case 16: layer0_resident<4>(A, L.xu_stride, lane, acc); break;
-          case 24: layer0_resident<6>(A, L.xu_stride, lane, acc); break;
+          case 8: layer0_resident<2>(arow0, L.xu_stride, acc); break;
+          case 16: layer0_resident<4>(arow0, L.xu_stride, acc); break;
+          case 24: layer0_resident<6>(arow0, L.xu_stride, acc); break;
           default:
             if constexpr (KS0RES >= 12) {
               switch (m.k1p) {
-                case 32: layer0_resident<8>(A, L.xu_stride, lane, acc); break;
-                case 40: layer0_resident<10>(A, L.xu_stride, lane, acc); break;
-                default: layer0_resident<12>(A, L.xu_stride, lane, acc); break;
+                case 32: layer0_resident<8>(arow0, L.xu_stride, acc); break;
+                case 40: layer0_resident<10>(arow0, L.xu_stride, acc); break;
+                default: layer0_resident<12>(arow0, L.xu_stride, acc); break;
               }
             }
             break;
@@ -949,7 +1052,7 @@ struct TileNet {
         }
       }
       AMPC_MARK(2);
-      epilogue(0, acc, act);
+      epilogue(0, acc, act, 0);
     }
     // Barrier placement.  A layer's epilogue leaves wave w's columns in LDS.  The output layer is
     // K-split so that wave w consumes exactly those columns: no barrier before it.  A hidden
@@ -971,20 +1074,29 @@ struct TileNet {
       // +2 %, and the 16-row tile has room for the early prefetch); f32 keeps whole groups
       // (half-groups measured -4 % there)
       constexpr int SGH = (sizeof(T) == 8 && !Probe::sg8) ? GH / 2 : GH;
-      layer_mma_static<T, NT, MT, KSH, GH, (W == 8), OWN, SGH, true>(
-          act, as, wr, slice_h(m, l, w), lane, pfn, acc, w, [&] {
-            if (!Probe::side_late && l == 1) { side(); side_done = true; }
-          });
+      auto mid = [&] {
+        if (!Probe::side_late && l == 1) { side(); side_done = true; }
+      };
+      if constexpr (PIN)
+        layer_mma_static<T, NT, MT, KSH, GH, (W == 8), OWN, SGH, true>(
+            act, as, wr, slice_h(m, l, w), lane, pfn, acc, w, mid, [&](int g) {
+              if constexpr (OWN) return cur ? rd_[1][g] : rd_[0][g];
+              else return (cur ? rd_[1][0] : rd_[0][0]) + 4 * GH * g;
+            });
+      else
+        layer_mma_static<T, NT, MT, KSH, GH, (W == 8), OWN, SGH, true>(
+            act, as, wr, slice_h(m, l, w), lane, pfn, acc, w, mid);
       AMPC_MARK(4);
       prefetch_next(l + 1);
       // single buffer: every wave must finish reading act before it is overwritten;
       // ping-pong: the epilogue writes the other buffer, no barrier needed here
       if (!pingpong) lds_barrier();
       AMPC_MARK(5);
-      epilogue(l, acc, act_other);
+      epilogue(l, acc, act_other, pingpong ? cur ^ 1 : 0);
       if (!OWN && l + 1 < m.n_hidden) lds_barrier();
       AMPC_MARK(6);
       { T* tmp = act; act = act_other; act_other = tmp; }
+      if (pingpong) cur ^= 1;
     }
 
     // ---- output layer: K-split, wave w owns k-steps [w*KSW, (w+1)*KSW) -----------------------
@@ -997,7 +1109,10 @@ struct TileNet {
       for (int n = 0; n < NOMAX; ++n) oacc[mt][n] = acc_t{0, 0, 0, 0};
     }
     {
-      const T* arow = act + act_row<T>(i) * as + q + 4 * w * KSW;
+      const auto arow = [&] {
+        if constexpr (PIN) return ro_;
+        else return static_cast<const T*>(act) + act_row<T>(i) * as + q + 4 * w * KSW;
+      }();
       if constexpr (WIDE) {
 #pragma unroll
         for (int ks = 0; ks < KSW; ++ks)
@@ -1057,11 +1172,18 @@ struct TileNet {
         if (n < nfull) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const int row = 16 * mt + acc_row<T>(q, r);
-            part[row * ps + 16 * n + i] = oacc[mt][n][r];
+            if constexpr (PIN) {
+              pp_[(16 * mt + RS * r) * ps + 16 * n] = oacc[mt][n][r];
+            } else {
+              const int row = 16 * mt + acc_row<T>(q, r);
+              part[row * ps + 16 * n + i] = oacc[mt][n][r];
+            }
           }
         }
-      if (m.tail4) part[(16 * mt + tail_row(lane)) * ps + 16 + tail_col(lane)] = tacc[mt];
+      if (m.tail4) {
+        if constexpr (PIN) pt_[16 * mt * ps] = tacc[mt];
+        else part[(16 * mt + tail_row(lane)) * ps + 16 + tail_col(lane)] = tacc[mt];
+      }
     }
     AMPC_MARK(13);
     lds_barrier();

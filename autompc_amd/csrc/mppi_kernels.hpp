@@ -193,7 +193,7 @@ template <typename T, int NT, int MT, int W, typename SH = DynShape, bool WIDE =
 __global__ __launch_bounds__(64 * W) void mppi_rollout_kernel(const MppiArgs<T> args) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   T* lds = reinterpret_cast<T*>(smem_raw);
-  using Net = TileNet<T, NT, MT, W, false, 0, SH, WIDE>;
+  using Net = TileNet<T, NT, MT, W, false, 0, SH, WIDE, true>;   // (pinned addresses: run() in the time loop)
   constexpr int M = 16 * MT, NTHR = 64 * W;
   constexpr int TPS = NTHR / M;                 // threads per sample (32..4), all in one wave
   constexpr int EPT = (16 + TPS - 1) / TPS;     // noise elements per thread (nu <= 16)
@@ -232,6 +232,7 @@ __global__ __launch_bounds__(64 * W) void mppi_rollout_kernel(const MppiArgs<T> 
   }
   Net net;
   net.init(mlp);
+  net.pin(mlp, L, lds);
 
   T* aseq = lds + lds_aseq;              // [H][nu] shifted warm start
   T* cpar = lds + lds_cost;              // Q R F goal | lo hi scale
@@ -280,6 +281,9 @@ __global__ __launch_bounds__(64 * W) void mppi_rollout_kernel(const MppiArgs<T> 
   // (the thread's bounds / scale / R weight are loop invariants kept in registers: every LDS
   // read and every VALU instruction of this lambda sits between the MFMAs of a time step)
   T lo_r[EPT], hi_r[EPT], sc_r[EPT], rd_r[EPT];
+  // the thread's noise of the NEXT step (kernels with pinned tile addresses, Net::PIN): one pointer, moved on
+  // by a row per call -- an index t * nu formed from the loop counter costs a second VALU instruction per step
+  const T* eps_nx = eps_row + nu + r;
   auto actions = [&](int t) {
 #pragma unroll
     for (int e = 0; e < EPT; ++e) {
@@ -298,9 +302,14 @@ __global__ __launch_bounds__(64 * W) void mppi_rollout_kernel(const MppiArgs<T> 
         const T u = A * sc_r[e];
         xu[m * xs_ + nx + j] = u;
         if (diag) c_part += rd_r[e] * u * u;          // diagonal R: the term is thread-local
-        if (t + 1 < H) e_next[e] = valid ? eps_row[(t + 1) * nu + j] : T(0);
+        if constexpr (Net::PIN) {
+          if (t + 1 < H && valid) e_next[e] = eps_nx[e * TPS];      // (rows past N keep their zero)
+        } else {
+          if (t + 1 < H) e_next[e] = valid ? eps_row[(t + 1) * nu + j] : T(0);
+        }
       }
     }
+    if constexpr (Net::PIN) eps_nx += nu;
   };
 #pragma unroll
   for (int e = 0; e < EPT; ++e) {          // (cpar was published by the barrier above)
