@@ -108,6 +108,9 @@ SIGNATURES = {
     "ampc_kstep_errors_linear": (c_int, [POINTER(c_void_p), c_int, c_int, _ip, c_int, _dp, _dp, _ip, _ip, _ip, _ip, _dp,
                                          POINTER(c_void_p), c_int, _dp, _dp, _dp]),
     "ampc_kstep_errors_sindy": (c_int, [POINTER(c_void_p), c_int, c_int, _ip, c_int, _dp, _dp, c_int, _dp, _dp, _dp]),
+    "ampc_kstep_errors_mlp": (c_int, [c_int, c_int, _ip, _ip, _ip, POINTER(c_void_p), POINTER(c_void_p),
+                                      POINTER(c_void_p), _ip, c_int, c_int, c_int, _ip, c_int, _dp, _dp, c_int, _dp, _dp,
+                                      _dp]),
     "ampc_lqr_plan_create": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
     "ampc_lqr_plan_destroy": (c_int, [c_void_p]),
     "ampc_lqr_plan_set_models": (c_int, [c_void_p, POINTER(c_void_p)]),

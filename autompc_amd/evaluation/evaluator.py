@@ -9,7 +9,8 @@ the ARX / Koopman models by one ``sysid.linear_fit.fit_linear_models`` call, wit
 models by one ``sysid.sindy_fit.fit_sindy_models`` call -- and all are scored by
 ``model_errors`` (one k-step kernel call per model shape; with ``linear_kstep="device"`` the ARX / Koopman models
 wider than 64 states too, all of them in one ``ampc_kstep_errors_linear`` call, instead of the host loop; with
-``sindy_kstep="device"`` the SINDy models in one ``ampc_kstep_errors_sindy`` call).
+``sindy_kstep="device"`` the SINDy models in one ``ampc_kstep_errors_sindy`` call; with ``mlp_kstep="batch"`` the f64
+MLPs of any mix of shapes in one ``ampc_kstep_errors_mlp`` call, read where the fit left them, no handle staged).
 
 Deviation from the reference (bug not reproduced): the reference's ``"rmsmens"`` string raises ``NameError``
 (evaluator.py:32-38: ``get_model_rmsmens`` is not imported and is called with ``horizon=``); here it scores
@@ -27,7 +28,8 @@ class ModelEvaluator(ABC):
     ``(model, [Trajectory]) -> float``."""
 
     def __init__(self, system, trajs, metric, rng, horizon=1, linear_fit="host", linear_kstep="host",
-                 sindy_kstep="host", sindy_fit="host", lasso_fit="host", stable_fit="host", mlp_fit="torch"):
+                 sindy_kstep="host", sindy_fit="host", lasso_fit="host", stable_fit="host", mlp_fit="torch",
+                 mlp_kstep="shape"):
         """linear_fit: how ``evaluate_batch`` fits ARX / Koopman models -- "host": each by its own ``train()``;
         "device": all of a batch by one ``sysid.linear_fit.fit_linear_models`` call (one Gram pass on the device,
         equal configurations fitted once).
@@ -46,6 +48,10 @@ class ModelEvaluator(ABC):
         mlp_fit: how ``evaluate_batch`` fits MLP models -- "torch": the lockstep PyTorch fit (``fit_mlps``); "device":
         the library's own training kernels (``fit_mlps(..., fit="device")``, ampc_mlpfit_*: one launch chain for any
         mix of shapes); ``last_mlp_fit`` holds what the call returned.
+        mlp_kstep: how the string metrics score MLP models -- "shape": one ``ampc_kstep_errors`` call per shape, one
+        launch and one staged handle per model; "batch": one ``ampc_kstep_errors_mlp`` call for the f64 MLPs of any
+        mix of depth, widths and activation, their parameters read in device memory where the fit left them
+        (``model_errors(..., mlp_kstep="batch")``; ``last_kstep.mlp_batch_calls``).
         ``last_kstep`` holds the ``KstepReport`` of the last ``evaluate_batch`` (``host_fallbacks``)."""
         if linear_fit not in ("host", "device"):
             raise ValueError("linear_fit must be 'host' or 'device'")
@@ -61,6 +67,9 @@ class ModelEvaluator(ABC):
             raise ValueError("stable_fit must be 'host' or 'device'")
         if mlp_fit not in ("torch", "device"):
             raise ValueError("mlp_fit must be 'torch' or 'device'")
+        if mlp_kstep not in ("shape", "batch"):
+            raise ValueError("mlp_kstep must be 'shape' or 'batch'")
+        self.mlp_kstep = mlp_kstep
         self.mlp_fit = mlp_fit
         self.last_mlp_fit = None
         self.linear_fit = linear_fit
@@ -79,11 +88,13 @@ class ModelEvaluator(ABC):
             if metric == "rmse":
                 self.metric = lambda model, trajs: get_model_rmse(model, trajs, horizon=self.horizon,
                                                                   linear_kstep=self.linear_kstep,
-                                                                  sindy_kstep=self.sindy_kstep)
+                                                                  sindy_kstep=self.sindy_kstep,
+                                                                  mlp_kstep=self.mlp_kstep)
             elif metric == "rmsmens":
                 self.metric = lambda model, trajs: get_model_rmsmens(model, trajs, horiz=self.horizon,
                                                                      linear_kstep=self.linear_kstep,
-                                                                     sindy_kstep=self.sindy_kstep)
+                                                                     sindy_kstep=self.sindy_kstep,
+                                                                     mlp_kstep=self.mlp_kstep)
             else:
                 raise ValueError("metric must be one of %s or a callable, not %r" % (", ".join(METRICS), metric))
             self.metric_name = metric
@@ -130,5 +141,5 @@ class ModelEvaluator(ABC):
             self.last_kstep = KstepReport()
             return model_errors(models, test_trajs, [self.horizon], self.metric_name,
                                 linear_kstep=self.linear_kstep, report=self.last_kstep,
-                                sindy_kstep=self.sindy_kstep)[:, 0]
+                                sindy_kstep=self.sindy_kstep, mlp_kstep=self.mlp_kstep)[:, 0]
         return np.array([float(self.metric(m, test_trajs)) for m in models])

@@ -37,6 +37,7 @@ class HoldoutModelEvaluator(ModelEvaluator):
 
     def evaluate_batch(self, model_factory, configurations):
         """Scores of every configuration (one lockstep fit of the MLPs, one k-step kernel call per model
-        shape; ``linear_kstep`` / ``sindy_kstep`` = "device" put the wide linear / SINDy models on the GPU too);
+        shape; ``linear_kstep`` / ``sindy_kstep`` = "device" put the wide linear / SINDy models on the GPU too,
+        ``mlp_kstep="batch"`` scores the MLPs of any mix of shapes in one launch);
         equal to ``[self(model_factory, cfg) for cfg in configurations]``."""
         return self._train_and_score(model_factory, list(configurations), self.training_set, self.holdout)

@@ -17,6 +17,16 @@ the GPU: they are grouped by ``(precision, device, obs_dim, ctrl_dim)`` (``sindy
 ``ampc_kstep_errors_sindy`` call, whatever mix of feature libraries, coefficients and time modes it holds
 (csrc/kstep_sindy_kernels.hpp).  The state is the observation; the device step is ``pred_batch``'s own.
 
+``mlp_kstep="batch"`` (opt-in; the default ``"shape"`` is the path above, bit for bit) scores f64 ``MLP`` models of ANY
+mix of depth, widths and activation together: they are grouped by ``(device, obs_dim, ctrl_dim)`` (``mlp_batch_key``) and
+each group is ONE ``ampc_kstep_errors_mlp`` call -- one launch over (row tiles, models) that reads the plain
+``torch.nn.Linear``-layout parameters through a device table (csrc/kstep_mlp_kernels.hpp).  No model of such a call is
+staged into a handle: a model whose fit left its parameters on the device (``fit_mlps``, either fit) hands over their
+addresses, the others their numpy arrays, uploaded once by the call.  The step applies the normalisers as
+``pred_batch`` of the reference does (not folded into the weights), so it agrees with the per-shape path at rounding
+level, not bit for bit.  f32 models, subclasses with their own ``pred_batch`` and models over the entry's limits keep
+the per-shape path.
+
 ``linear_kstep="device"`` (opt-in; the default ``"host"`` is the path above, bit for bit) scores trained
 ``_LinearModel``s of 65..256 states on the GPU too: they are grouped by ``(precision, device, ctrl_dim)``
 (``wide_linear_key``) and each group is ONE ``ampc_kstep_errors_linear`` call, whatever mix of state dimensions it
@@ -52,6 +62,10 @@ _WIDE_MAX_CTRLS = 16
 _LDS_BYTES = 160 * 1024
 LINEAR_KSTEP = ("host", "device")
 SINDY_KSTEP = ("host", "device")
+MLP_KSTEP = ("shape", "batch")
+_MLP_BATCH_MAX_HIDDEN, _MLP_BATCH_MAX_WIDTH = 4, 256        # csrc/kstep_mlp_kernels.hpp
+_MLP_BATCH_MAX_IN, _MLP_BATCH_MAX_STATES = 80, 64
+_MLP_BATCH_LAYERS = _MLP_BATCH_MAX_HIDDEN + 1               # pointer slots per model
 _SINDY_MAX_TAB = 160                    # kSindyMaxTab (csrc/sindy_kernels.hpp)
 _SINDY_STAGE_BYTES = 48 * 1024          # kSindyStageBytes
 _SINDY_ROWS, _SINDY_CHUNK, _SINDY_ERR_STRIDE = 64, 8, 65      # csrc/kstep_sindy_kernels.hpp
@@ -60,16 +74,19 @@ _SINDY_ROWS, _SINDY_CHUNK, _SINDY_ERR_STRIDE = 64, 8, 65      # csrc/kstep_sindy
 class KstepReport:
     """What one ``model_errors`` call did: ``device_models`` scored by ``ampc_kstep_errors``, ``wide_models`` by
     ``ampc_kstep_errors_linear`` in ``wide_calls`` calls, ``sindy_models`` by ``ampc_kstep_errors_sindy`` in
-    ``sindy_calls`` calls, ``host_fallbacks`` by the host loop over ``pred_batch``."""
+    ``sindy_calls`` calls, ``mlp_batch_models`` by ``ampc_kstep_errors_mlp`` in ``mlp_batch_calls`` calls,
+    ``host_fallbacks`` by the host loop over ``pred_batch``."""
 
     def __init__(self):
         self.device_models = self.wide_models = self.wide_calls = self.host_fallbacks = 0
         self.sindy_models = self.sindy_calls = 0
+        self.mlp_batch_models = self.mlp_batch_calls = 0
 
     def __repr__(self):
         return ("KstepReport(device_models=%d, wide_models=%d, wide_calls=%d, sindy_models=%d, sindy_calls=%d, "
-                "host_fallbacks=%d)" % (self.device_models, self.wide_models, self.wide_calls, self.sindy_models,
-                                        self.sindy_calls, self.host_fallbacks))
+                "mlp_batch_models=%d, mlp_batch_calls=%d, host_fallbacks=%d)"
+                % (self.device_models, self.wide_models, self.wide_calls, self.sindy_models, self.sindy_calls,
+                   self.mlp_batch_models, self.mlp_batch_calls, self.host_fallbacks))
 
 
 last_report = KstepReport()
@@ -369,6 +386,128 @@ def kstep_sums_sindy(models, trajs, kmax, delta=False):
     return S, D
 
 
+# ---- MLP models of any mix of shapes: the one-launch entry ------------------------------------------------
+def mlp_batch_key(model, obs_dim=None):
+    """Key of the MLP models that share one ``ampc_kstep_errors_mlp`` call -- ("mlp-batch", device, obs_dim, ctrl_dim):
+    depth, widths and activation may differ -- or None: not an f64 ``MLP`` with the class's own ``pred_batch``, a
+    system the entry does not take (``obs_dim`` is not the model's, more than 64 states, 16 controls or 80 inputs), or
+    a network over its limits (1..4 hidden layers of 1..256 units).  Needs no GPU."""
+    from ..sysid.mlp import MLP
+    if not isinstance(model, MLP) or type(model).pred_batch is not MLP.pred_batch:
+        return None
+    if model.precision != "f64" or model.nonlintype not in _lib.ACTIVATIONS:
+        return None
+    s = model.system
+    no = s.obs_dim if obs_dim is None else int(obs_dim)
+    if no != s.obs_dim or not (1 <= no <= _MLP_BATCH_MAX_STATES) or not (1 <= s.ctrl_dim <= _WIDE_MAX_CTRLS):
+        return None
+    if no + s.ctrl_dim > _MLP_BATCH_MAX_IN:
+        return None
+    hidden = [int(h) for h in model.hidden_sizes]
+    if not (1 <= len(hidden) <= _MLP_BATCH_MAX_HIDDEN) or any(not (1 <= h <= _MLP_BATCH_MAX_WIDTH) for h in hidden):
+        return None
+    return ("mlp-batch", int(model.device), no, s.ctrl_dim)
+
+
+def _device_resident(model):
+    """The fit's device tensors of `model` when they stand for it on its own GPU (float64, contiguous, the fit's
+    normalisers still in place), else None."""
+    dp = getattr(model, "_dev_params", None)
+    if dp is None:
+        return None
+    tensors = list(dp["w"]) + list(dp["b"]) + list(dp["norm_dev"])
+    for t in tensors:
+        if not (t.is_cuda and t.device.index == int(model.device) and t.is_contiguous()
+                and str(t.dtype) == "torch.float64"):
+            return None
+    return dp if model._normalisers_are_the_fit() else None
+
+
+def mlp_batch_args(models):
+    """What ``ampc_kstep_errors_mlp`` takes for `models`, as plain arrays (no GPU, no library call): ``n_hidden`` [n],
+    ``dims`` [n][6] (nx + nu, hidden widths, nx, zero padded), ``acts`` [n], ``weights`` / ``biases`` [n][5] and
+    ``norms`` [n][4] (addresses as uint64, 0 past a model's layers), ``on_device`` [n] and ``keep``: the objects the
+    addresses point into.  A model whose ``_dev_params`` holds the fit's device tensors hands over their
+    ``data_ptr()``s (``on_device`` 1), the others contiguous float64 numpy copies of ``weights`` / ``biases`` and of the
+    normalisers."""
+    n, L = len(models), _MLP_BATCH_LAYERS
+    n_hidden = np.zeros(n, dtype=np.int32)
+    dims = np.zeros((n, L + 1), dtype=np.int32)
+    acts = np.zeros(n, dtype=np.int32)
+    weights = np.zeros((n, L), dtype=np.uint64)
+    biases = np.zeros((n, L), dtype=np.uint64)
+    norms = np.zeros((n, 4), dtype=np.uint64)
+    on_device = np.zeros(n, dtype=np.int32)
+    keep = []
+    for k, m in enumerate(models):
+        s = m.system
+        hidden = [int(h) for h in m.hidden_sizes]
+        if not 1 <= len(hidden) <= _MLP_BATCH_MAX_HIDDEN:
+            raise ValueError("ampc_kstep_errors_mlp takes models of 1..%d hidden layers, not %d"
+                             % (_MLP_BATCH_MAX_HIDDEN, len(hidden)))
+        if m.precision != "f64":
+            raise ValueError("ampc_kstep_errors_mlp takes f64 models only")
+        d = [s.obs_dim + s.ctrl_dim] + hidden + [s.obs_dim]
+        n_hidden[k] = len(hidden)
+        dims[k, :len(d)] = d
+        acts[k] = _lib.ACTIVATIONS[m.nonlintype]
+        dp = _device_resident(m)
+        if dp is not None:
+            on_device[k] = 1
+            ws, bs, nm = dp["w"], dp["b"], dp["norm_dev"]
+            ptr = lambda t: t.data_ptr()
+        else:
+            ws, bs = [_lib.as_f64(w) for w in m.weights], [_lib.as_f64(b) for b in m.biases]
+            nm = [_lib.as_f64(v) for v in (m.xu_means, m.xu_std, m.dy_means, m.dy_std)]
+            ptr = lambda a: a.ctypes.data
+        if len(ws) != len(d) - 1 or len(bs) != len(d) - 1:
+            raise ValueError("one weight and one bias per layer (hidden + output) expected")
+        for l, (w, b) in enumerate(zip(ws, bs)):
+            if tuple(w.shape) != (d[l + 1], d[l]) or tuple(b.shape) != (d[l + 1],):
+                raise ValueError("layer %d has shape %r, expected %r" % (l, tuple(w.shape), (d[l + 1], d[l])))
+            weights[k, l], biases[k, l] = ptr(w), ptr(b)
+        for i, v in enumerate(nm):
+            if tuple(v.shape) != ((d[0],) if i < 2 else (d[-1],)):
+                raise ValueError("normaliser shapes do not match (nx+nu, nx+nu, nx, nx)")
+            norms[k, i] = ptr(v)
+        keep.append((ws, bs, nm))
+    return {"n_hidden": n_hidden, "dims": dims, "acts": acts, "weights": weights, "biases": biases, "norms": norms,
+            "on_device": on_device, "keep": keep}
+
+
+def kstep_sums_mlp(models, trajs, kmax, delta=False):
+    """(S [n_models][kmax], D or None) of MLP models of ONE ``mlp_batch_key``: one ``ampc_kstep_errors_mlp`` call.  No
+    model is staged into a handle."""
+    import ctypes
+    lib = _lib.load()
+    obs_dim = _obs_dim(trajs, models[0])
+    s = models[0].system
+    lens, obs, ctrls = _concat(trajs)
+    n = len(models)
+    args = mlp_batch_args(models)
+    device = int(models[0].device)
+    if any(int(m.device) != device for m in models):
+        raise ValueError("the models of one ampc_kstep_errors_mlp call live on one device")
+    if args["on_device"].any():
+        import torch
+        torch.cuda.current_stream(torch.device("cuda", device)).synchronize()    # the fit's kernels have finished
+    inv_std = None
+    if delta:
+        _, std = _increment_stats(trajs)
+        with np.errstate(divide="ignore"):
+            inv_std = np.ascontiguousarray(1.0 / std)
+    S = np.empty((n, kmax))
+    D = np.empty((n, kmax)) if delta else None
+    vpp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_void_p))
+    _lib.check(lib.ampc_kstep_errors_mlp(device, n, _lib.iptr(args["n_hidden"]), _lib.iptr(args["dims"]),
+                                         _lib.iptr(args["acts"]), vpp(args["weights"]), vpp(args["biases"]),
+                                         vpp(args["norms"]), _lib.iptr(args["on_device"]), s.obs_dim, s.ctrl_dim,
+                                         len(trajs), _lib.iptr(lens), obs_dim, _lib.dptr(obs), _lib.dptr(ctrls),
+                                         int(kmax), _lib.dptr(inv_std), _lib.dptr(S), _lib.dptr(D)))
+    del args
+    return S, D
+
+
 def _concat(trajs):
     lens = np.array([len(t) for t in trajs], dtype=np.int32)
     obs = np.ascontiguousarray(np.concatenate([np.asarray(t.obs, dtype=np.float64) for t in trajs]))
@@ -408,13 +547,16 @@ def row_counts(trajs, kmax):
     return np.array([np.maximum(lens - h, 0).sum() for h in range(1, kmax + 1)], dtype=np.float64)
 
 
-def model_errors(models, trajs, horizons, metric="rmse", linear_kstep="host", report=None, sindy_kstep="host"):
+def model_errors(models, trajs, horizons, metric="rmse", linear_kstep="host", report=None, sindy_kstep="host",
+                 mlp_kstep="shape"):
     """RMSE or RMSMENS of every model at every horizon: ndarray [len(models), len(horizons)] in input order
     (the data of a ``KstepPredAccGraph`` curve).  Device models are grouped by shape, one ``ampc_kstep_errors``
     call per group covering every horizon; the others take the host fallback (module docstring) -- except, with
     ``linear_kstep="device"``, the wide linear models: one ``ampc_kstep_errors_linear`` call per
     ``wide_linear_key``, and, with ``sindy_kstep="device"``, the SINDy models: one ``ampc_kstep_errors_sindy`` call
-    per ``sindy_kstep_key``.  ``report``: a ``KstepReport`` to fill (one is made otherwise; either way it becomes
+    per ``sindy_kstep_key``, and, with ``mlp_kstep="batch"``, the f64 MLPs of any mix of shapes: one
+    ``ampc_kstep_errors_mlp`` call per ``mlp_batch_key`` instead of one ``ampc_kstep_errors`` launch per model (MLPs that
+    key refuses keep the per-shape path).  ``report``: a ``KstepReport`` to fill (one is made otherwise; either way it becomes
     ``model_metrics.last_report``)."""
     global last_report
     if metric not in METRICS:
@@ -423,6 +565,8 @@ def model_errors(models, trajs, horizons, metric="rmse", linear_kstep="host", re
         raise ValueError("linear_kstep must be 'host' or 'device'")
     if sindy_kstep not in SINDY_KSTEP:
         raise ValueError("sindy_kstep must be 'host' or 'device'")
+    if mlp_kstep not in MLP_KSTEP:
+        raise ValueError("mlp_kstep must be 'shape' or 'batch'")
     report = KstepReport() if report is None else report
     last_report = report
     models = list(models)
@@ -436,8 +580,12 @@ def model_errors(models, trajs, horizons, metric="rmse", linear_kstep="host", re
         for m in models:
             _check_rmsmens_model(m, obs_dim)
     delta = metric == "rmsmens"
-    groups, wide, sindy = {}, {}, {}
+    groups, wide, sindy, batch = {}, {}, {}, {}
     for i, m in enumerate(models):
+        key = mlp_batch_key(m, obs_dim) if mlp_kstep == "batch" and trajs else None
+        if key is not None:
+            batch.setdefault(key, []).append(i)
+            continue
         key = device_shape_key(m) if trajs else None
         if key is not None:
             groups.setdefault(key, []).append(i)
@@ -455,11 +603,12 @@ def model_errors(models, trajs, horizons, metric="rmse", linear_kstep="host", re
             host = host_rmse if metric == "rmse" else host_rmsmens
             out[i] = [host(m, trajs, h) for h in horizons]
             report.host_fallbacks += 1
-    if groups or wide or sindy:
+    if groups or wide or sindy or batch:
         kmax = max(horizons)
         N = row_counts(trajs, kmax)
         hidx = np.array(horizons) - 1
-        for sums, grp in ((kstep_sums, groups), (kstep_sums_linear, wide), (kstep_sums_sindy, sindy)):
+        for sums, grp in ((kstep_sums, groups), (kstep_sums_linear, wide), (kstep_sums_sindy, sindy),
+                          (kstep_sums_mlp, batch)):
             for idx in grp.values():
                 S, D = sums([models[i] for i in idx], trajs, kmax, delta=delta)
                 with np.errstate(divide="ignore", invalid="ignore"):
@@ -471,19 +620,22 @@ def model_errors(models, trajs, horizons, metric="rmse", linear_kstep="host", re
                 elif grp is sindy:
                     report.sindy_models += len(idx)
                     report.sindy_calls += 1
+                elif grp is batch:
+                    report.mlp_batch_models += len(idx)
+                    report.mlp_batch_calls += 1
                 else:
                     report.device_models += len(idx)
     return out
 
 
-def get_model_rmse(model, trajs, horizon=1, linear_kstep="host", sindy_kstep="host"):
+def get_model_rmse(model, trajs, horizon=1, linear_kstep="host", sindy_kstep="host", mlp_kstep="shape"):
     """Unnormalised RMSE at a fixed horizon (model_metrics.py:12-43); see the module docstring."""
     return float(model_errors([model], trajs, [horizon], "rmse", linear_kstep=linear_kstep,
-                              sindy_kstep=sindy_kstep)[0, 0])
+                              sindy_kstep=sindy_kstep, mlp_kstep=mlp_kstep)[0, 0])
 
 
-def get_model_rmsmens(model, trajs, horiz=1, linear_kstep="host", sindy_kstep="host"):
+def get_model_rmsmens(model, trajs, horiz=1, linear_kstep="host", sindy_kstep="host", mlp_kstep="shape"):
     """Root mean squared model error, normalised step-wise (model_metrics.py:45-111); see the module
     docstring for the deviations from the reference."""
     return float(model_errors([model], trajs, [horiz], "rmsmens", linear_kstep=linear_kstep,
-                              sindy_kstep=sindy_kstep)[0, 0])
+                              sindy_kstep=sindy_kstep, mlp_kstep=mlp_kstep)[0, 0])

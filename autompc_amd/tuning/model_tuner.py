@@ -33,7 +33,9 @@ class BatchModelTuner:
     evaluator's own options decide where a batch's linear models are fitted and scored (``linear_fit="device"``,
     ``linear_kstep="device"``: ARX / Koopman models wider than 64 states in one k-step launch;
     ``sindy_kstep="device"``: a batch's SINDy models in one k-step launch; ``sindy_fit="device"``: their thresholded
-    fits in one ``ampc_sindy_fit`` call; ``mlp_fit="device"``: a batch's MLPs by the library's training kernels).
+    fits in one ``ampc_sindy_fit`` call; ``mlp_fit="device"``: a batch's MLPs by the library's training kernels;
+    ``mlp_kstep="batch"``: a batch's MLPs of any mix of shapes scored by one ``ampc_kstep_errors_mlp`` launch, read where
+    the fit left them).
     sampler: ``sampler(tuner, n, rng) -> n combined configurations``; the default draws a factory uniformly and
     its configuration from its ranges (``MLPFactory`` / ``ARXFactory`` / ``KoopmanFactory``: ``sample_mlp_config`` /
     ``sample_arx_config`` / ``sample_koopman_config``; other factories need a

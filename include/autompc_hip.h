@@ -44,8 +44,8 @@ int ampc_version(void);   /* 100 * major + minor; 104: + ampc_mppi_run_legacy; 1
                            *      ampc_mppi_plan_set_models, ampc_ilqr_plan_set_models; 107: + ampc_set_mlp_dev, ampc_ilqr_plan_set_constants;
                            * 108: + ampc_kstep_errors; 109: + ampc_lqr_*; 110: + ampc_linfit_fit;
                            * 111: + ampc_kstep_errors_linear; 112: + ampc_kstep_errors_sindy;
-                           * 113: + ampc_sindy_fit; 114: + ampc_lasso_fit; + ampc_stable_fit, + ampc_mlpfit_* (no bump: callers detect them by
-                           *      their symbols) */
+                           * 113: + ampc_sindy_fit; 114: + ampc_lasso_fit; + ampc_stable_fit, + ampc_mlpfit_*, + ampc_kstep_errors_mlp (no bump:
+                           *      callers detect them by their symbols) */
 int ampc_device_count(void);
 
 /* ---- handle ------------------------------------------------------------------------------ */
@@ -518,6 +518,33 @@ int ampc_kstep_errors_linear(ampc_handle* const* models, int n_models, int n_tra
 int ampc_kstep_errors_sindy(ampc_handle* const* models, int n_models, int n_traj, const int* traj_len, int obs_dim,
                             const double* obs, const double* ctrls, int kmax, const double* inv_std, double* sq_err,
                             double* sq_delta_err);
+
+/* ... of MLP models of ANY mix of depth, widths and activation in ONE launch (csrc/kstep_mlp_kernels.hpp; f64 only).  No
+ * handle is involved and nothing is packed per shape: a model is its plain parameters, read through a device table.
+ *   device: the GPU everything runs on;
+ *   n_hidden [n_models] in 1..4; dims [n_models][6]: nx + nu, the hidden widths (1..256), nx, the rest ignored;
+ *   activations [n_models] as ampc_set_mlp;
+ *   weights / biases [n_models][5]: per linear layer (hidden layers, then the output layer; entries past a model's
+ *   layers are ignored) the address of the weight [out][in], row-major as torch.nn.Linear keeps it, and of the bias
+ *   [out]; norms [n_models][4]: xu_means [nx + nu], xu_std [nx + nu], dy_means [nx], dy_std [nx] (float64);
+ *   on_device [n_models]: nonzero -- ALL of that model's addresses are memory of `device` (e.g. views of the flat buffer
+ *   ampc_mlpfit_* trained, or separate torch tensors); they are read in place, complete when this is called, with no
+ *   copy and no packing kernel (each address is checked to be memory of `device`; the extents are the caller's).
+ *   Zero -- host memory: packed and uploaded once by the call.
+ *   nx (1..64), nu (1..16), nx + nu <= 80: every model of a call takes nx + nu inputs and gives nx outputs.
+ * The step is MLP.pred_batch's (autompc/sysid/mlp.py:229-236): x' = x + (net(([x, u] - xu_means) / xu_std) dy_std +
+ * dy_means), normalisers applied as written (not folded into the weights).  The state is the observation (obs_dim ==
+ * nx, no initial-state rows); data and outputs as ampc_kstep_errors.  Grid (16-row tiles, models), 256 threads.
+ * Refused: depths, widths or dimensions over the limits, a model of other input / output width, obs_dim != nx, NULL
+ * addresses, an address flagged as device memory that is not memory of `device`.  A diverging model yields non-finite
+ * sums for itself only.  Deterministic: every sum runs in a fixed order that depends on the model's own layer widths
+ * and the 16-row tile only -- a model's sums do not depend on the other models of the call or on their order.
+ * Synchronises. */
+int ampc_kstep_errors_mlp(int device, int n_models, const int* n_hidden, const int* dims, const int* activations,
+                          const double* const* weights, const double* const* biases, const double* const* norms,
+                          const int* on_device, int nx, int nu, int n_traj, const int* traj_len, int obs_dim,
+                          const double* obs, const double* ctrls, int kmax, const double* inv_std, double* sq_err,
+                          double* sq_delta_err);
 
 /* ---- least-squares model fits (f64 only) ---------------------------------------------------- */
 /* Fits ARX models (sysid/arx.py:62-116) and Koopman models of method "lstsq" (sysid/koopman.py:141-154) of ONE data

@@ -1,0 +1,171 @@
+"""The host side of the mixed-shape MLP k-step path (ampc_kstep_errors_mlp, evaluation/model_metrics.py): the ABI, the
+grouping key ``mlp_batch_key``, the ``mlp_kstep`` option, the pointer table ``mlp_batch_args`` builds for host-resident
+parameters, and the default path left as it is.  No GPU."""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+
+from autompc_amd import MLP
+from autompc_amd.evaluation import model_metrics as MM
+from helpers import golden_params, make_system
+from kstep_mlp_cases import TAGS, fixture_model, mlp_of
+from oracle.mlp import MLPOracle
+
+
+def test_abi_exports_and_binds_the_entry():
+    from autompc_amd import _lib
+    from autompc_amd.csrc import build as B
+    lib = ctypes.CDLL(B.build(verbose=False))
+    assert hasattr(lib, "ampc_kstep_errors_mlp")
+    assert len(_lib.SIGNATURES["ampc_kstep_errors_mlp"][1]) == 20
+    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include",
+                               "autompc_hip.h")).read()
+    assert "ampc_kstep_errors_mlp(" in header
+    units = {u[1]: u[2] for u in B.UNITS}
+    assert units["launch_kstep_mlp.cpp"] == ["-DAMPC_T=double", "-DAMPC_T_IS_F64=1"] and "api_kstep_mlp.cpp" in units
+    # refused before any device call: there is no GPU here
+    z = np.zeros(8, dtype=np.int32)
+    rc = _lib.load().ampc_kstep_errors_mlp(0, 0, _lib.iptr(z), _lib.iptr(z), _lib.iptr(z), None, None, None,
+                                           _lib.iptr(z), 4, 1, 0, None, 4, None, None, 1, None,
+                                           _lib.dptr(np.zeros(1)), None)
+    assert rc != 0 and b"no models" in _lib.load().ampc_last_error()
+
+
+@pytest.mark.parametrize("tag", TAGS)
+def test_fixture_models_take_the_batch_group(tag):
+    m, trajs, g = fixture_model(tag)
+    nx, nu = int(g["nx"]), int(g["nu"])
+    assert MM.mlp_batch_key(m, nx) == MM.mlp_batch_key(m) == ("mlp-batch", 0, nx, nu)
+    assert MM.device_shape_key(m)[0] == "mlp"                  # and the per-shape group as before
+
+
+def test_mlp_batch_key_decisions():
+    a, b, c = (fixture_model(t)[0] for t in ("hc_relu2", "hc_selu4", "hc_tanh1"))
+    assert MM.mlp_batch_key(a) == MM.mlp_batch_key(b) == MM.mlp_batch_key(c) == ("mlp-batch", 0, 17, 6)
+    assert len({MM.device_shape_key(m) for m in (a, b, c)}) == 3
+    assert MM.mlp_batch_key(fixture_model("c4_relu1")[0]) == ("mlp-batch", 0, 4, 1)
+    assert MM.mlp_batch_key(fixture_model("hc_relu2", precision="f32")[0]) is None       # f32: the per-shape path
+    assert MM.device_shape_key(fixture_model("hc_relu2", precision="f32")[0]) is not None
+    assert MM.mlp_batch_key(a, obs_dim=4) is None                                        # data of another system
+    on1 = MLP(make_system(3, 2), n_hidden_layers=1, hidden_size_1=16, device=1)
+    assert MM.mlp_batch_key(on1) == ("mlp-batch", 1, 3, 2)
+
+    class Foreign(MLP):
+        def pred_batch(self, states, ctrls):
+            return states
+
+    assert MM.mlp_batch_key(Foreign(make_system(3, 2), n_hidden_layers=1, hidden_size_1=16)) is None
+    assert MM.mlp_batch_key(MLPOracle(make_system(3, 2), golden_params(3, 2, [16], "relu", 1))) is None
+    # the limits: widths 1..256, 1..4 hidden layers, nx <= 64, nu <= 16, nx + nu <= 80
+    s = make_system(3, 2)
+    assert MM.mlp_batch_key(MLP(s, n_hidden_layers=2, hidden_size_1=256, hidden_size_2=1)) is not None
+    assert MM.mlp_batch_key(MLP(s, n_hidden_layers=2, hidden_size_1=257, hidden_size_2=16)) is None
+    assert MM.mlp_batch_key(MLP(s, n_hidden_layers=4, hidden_size=16)) is not None
+    assert MM.mlp_batch_key(MLP(s, n_hidden_layers=5, hidden_size=16)) is None
+    assert MM.mlp_batch_key(MLP(make_system(64, 16), n_hidden_layers=1, hidden_size=16)) is not None
+    assert MM.mlp_batch_key(MLP(make_system(65, 2), n_hidden_layers=1, hidden_size=16)) is None
+    assert MM.mlp_batch_key(MLP(make_system(8, 17), n_hidden_layers=1, hidden_size=16)) is None
+    from kstep_wide_cases import wide_model
+    assert MM.mlp_batch_key(wide_model("arx4_hc")[0]) is None
+
+
+def _read(addr, shape):
+    n = int(np.prod(shape))
+    return np.ctypeslib.as_array(ctypes.cast(int(addr), ctypes.POINTER(ctypes.c_double)), shape=(n,)).reshape(shape)
+
+
+def test_pointer_table_of_host_parameters_reads_back_the_models():
+    models = [fixture_model(t)[0] for t in ("hc_selu4", "hc_tanh1", "hc_relu2")]
+    a = MM.mlp_batch_args(models)
+    assert a["n_hidden"].tolist() == [4, 1, 2] and a["acts"].tolist() == [3, 1, 0] and not a["on_device"].any()
+    assert a["dims"].tolist() == [[23, 37, 16, 200, 256, 17], [23, 200, 17, 0, 0, 0], [23, 256, 256, 17, 0, 0]]
+    assert a["dims"].dtype == np.int32 and a["weights"].shape == (3, 5) and a["norms"].shape == (3, 4)
+    for k, m in enumerate(models):
+        d = [int(v) for v in a["dims"][k][:a["n_hidden"][k] + 2]]
+        for l in range(len(d) - 1):
+            assert np.array_equal(_read(a["weights"][k, l], (d[l + 1], d[l])), m.weights[l])
+            assert np.array_equal(_read(a["biases"][k, l], (d[l + 1],)), m.biases[l])
+        assert not a["weights"][k, len(d) - 1:].any() and not a["biases"][k, len(d) - 1:].any()
+        for i, v in enumerate((m.xu_means, m.xu_std, m.dy_means, m.dy_std)):
+            assert np.array_equal(_read(a["norms"][k, i], v.shape), v)
+    # a non-contiguous, non-float64 weight is handed over as a contiguous float64 copy
+    m = models[1]
+    m.weights = [np.asfortranarray(m.weights[0]), m.weights[1].astype(np.float32)]
+    b = MM.mlp_batch_args([m])
+    assert np.array_equal(_read(b["weights"][0, 0], (200, 23)), m.weights[0])
+    assert np.array_equal(_read(b["weights"][0, 1], (17, 200)), m.weights[1].astype(np.float64))
+    with pytest.raises(ValueError, match="1..4 hidden layers"):
+        MM.mlp_batch_args([MLP(make_system(3, 2), n_hidden_layers=5, hidden_size=16)])
+    with pytest.raises(ValueError, match="f64"):
+        MM.mlp_batch_args([fixture_model("hc_relu2", precision="f32")[0]])
+    bad = fixture_model("c4_relu1")[0]
+    bad._weights[0] = bad._weights[0][:, :-1]
+    with pytest.raises(ValueError, match="layer 0 has shape"):
+        MM.mlp_batch_args([bad])
+
+
+class _Counting(MLPOracle):
+    calls = 0
+
+    def pred_batch(self, states, ctrls):
+        type(self).calls += 1
+        return super().pred_batch(states, ctrls)
+
+
+def test_mlp_kstep_option_is_checked_and_the_default_is_untouched(monkeypatch):
+    from autompc_amd.evaluation import HoldoutModelEvaluator, get_model_rmse, get_model_rmsmens, model_errors
+    _, trajs, g = fixture_model("c4_tanh2")
+    s = trajs[0].system
+    for bad in ("device", None, "Batch"):
+        with pytest.raises(ValueError, match="mlp_kstep"):
+            model_errors([], trajs, [1], "rmse", mlp_kstep=bad)
+        with pytest.raises(ValueError, match="mlp_kstep"):
+            HoldoutModelEvaluator(s, trajs, "rmse", np.random.default_rng(0), mlp_kstep=bad)
+        with pytest.raises(ValueError, match="mlp_kstep"):
+            get_model_rmse(None, trajs, 1, mlp_kstep=bad)
+        with pytest.raises(ValueError, match="mlp_kstep"):
+            get_model_rmsmens(None, trajs, 1, mlp_kstep=bad)
+    ev = HoldoutModelEvaluator(s, trajs, "rmse", np.random.default_rng(0))
+    assert ev.mlp_kstep == "shape" and ev.sindy_kstep == "host" and ev.linear_kstep == "host"
+    assert HoldoutModelEvaluator(s, trajs, "rmsmens", np.random.default_rng(0), mlp_kstep="batch").mlp_kstep == "batch"
+
+    def boom(*a, **k):
+        raise AssertionError("the default path must not reach the batch entry")
+
+    monkeypatch.setattr(MM, "kstep_sums_mlp", boom)
+    monkeypatch.setattr(MM, "mlp_batch_key", boom)
+    m = _Counting(s, golden_params(4, 1, g["hidden"], "tanh", int(g["seed"])))
+    r0, r1 = MM.KstepReport(), MM.KstepReport()
+    a = model_errors([m, m], trajs, [1, 3, 20], "rmse", report=r0)
+    n0 = _Counting.calls
+    b = model_errors([m, m], trajs, [1, 3, 20], "rmse", report=r1, mlp_kstep="shape")
+    assert _Counting.calls == 2 * n0 and np.array_equal(a, b) and MM.last_report is r1
+    assert vars(r0) == vars(r1) and r0.host_fallbacks == 2 and r0.mlp_batch_models == 0 and r0.mlp_batch_calls == 0
+    assert "mlp_batch_models=0, mlp_batch_calls=0" in repr(r0)
+    np.testing.assert_allclose(a[0], g["rmse"][[0, 2, 10]], rtol=1e-9, atol=0)       # the oracle over the host loop
+    assert a[0, 1] == MM.host_rmse(m, trajs, 3) == get_model_rmse(m, trajs, 3) == get_model_rmse(m, trajs, 3,
+                                                                                                  mlp_kstep="shape")
+    assert get_model_rmsmens(m, trajs, 2, mlp_kstep="shape") == MM.host_rmsmens(m, trajs, 2)
+    # the default routing of a real MLP is the per-shape group, with or without the option spelled out
+    real = mlp_of(s, golden_params(4, 1, [37, 200], "tanh", 42), [37, 200], "tanh")
+    seen = []
+    monkeypatch.setattr(MM, "kstep_sums", lambda ms, t, kmax, delta=False: (seen.append(len(ms)),
+                                                                            (np.ones((len(ms), kmax)), None))[1])
+    model_errors([real, real], trajs, [2], "rmse")
+    model_errors([real, real], trajs, [2], "rmse", mlp_kstep="shape")
+    assert seen == [2, 2] and MM.last_report.device_models == 2 and MM.last_report.mlp_batch_calls == 0
+    monkeypatch.undo()
+    # with the option on, a foreign model stays on the host loop and a keyed one goes to the batch entry, once
+    got = []
+    monkeypatch.setattr(MM, "kstep_sums_mlp", lambda ms, t, kmax, delta=False: (got.append(list(ms)),
+                                                                                (np.ones((len(ms), kmax)), None))[1])
+    wide = MLP(s, n_hidden_layers=1, hidden_size_1=257)
+    monkeypatch.setattr(MM, "kstep_sums", lambda ms, t, kmax, delta=False: (seen.append(list(ms)),
+                                                                            (np.ones((len(ms), kmax)), None))[1])
+    r2 = MM.KstepReport()
+    c = model_errors([real, m, wide, real], trajs, [1, 3, 20], "rmse", report=r2, mlp_kstep="batch")
+    assert np.array_equal(c[1], a[0]) and r2.host_fallbacks == 1
+    assert got == [[real, real]] and r2.mlp_batch_models == 2 and r2.mlp_batch_calls == 1
+    assert seen[-1] == [wide] and r2.device_models == 1                  # over the limits: the per-shape path
