@@ -12,8 +12,10 @@ from autompc_amd import SINDy, SINDyFactory
 from autompc_amd.evaluation import HoldoutModelEvaluator
 from autompc_amd.sysid import sindy_fit as SF
 from autompc_amd.tuning.configs import DictConfiguration
-from sindy_fit_cases import (CONFIGS, ELIGIBLE, FEATURES, LONG, data, host_fit, new_model, rel_err, request,
-                             same_support, trained)
+from autompc_amd.sysid.linear_fit import PIVOT_EPS
+from sindy_fit_cases import (ALPHAS, BOTH, CONFIGS, EDGE_KEPT, EDGE_SMALL, EDGE_WIDE, EDGES, ELIGIBLE, EXTREMES,
+                             FEATURES, LIMITS, LONG, NEIGHBOURS, alpha_of, data, first_features, host_fit, new_model,
+                             rel_err, request, same_support, trained)
 
 
 def test_feature_counts():
@@ -32,6 +34,87 @@ def test_gram_route_matches_train(name, k):
     assert same_support(c, ref) and err <= 1e-9
     if k == 9:
         assert not ref.any() and iters == 1
+
+
+# every case the GPU tests expect to be fitted (status 0), the caller's-xdot ones last: (data, case, xdot)
+STATUS0 = ([c + (False,) for c in EDGE_SMALL + EDGE_WIDE + LIMITS + EDGES + EDGE_KEPT + ALPHAS + EXTREMES[:2]
+            + [("small", "7d"), ("small", "dup")] + NEIGHBOURS[0.0] + NEIGHBOURS[1e-9]]
+           + [("small", "7d", True), ("small", 7, True), ("wide", "trig1:240c", True)])
+
+
+def _kept_counts(name, k):
+    """Kept-feature counts of the second and later solves of a case: the nonzeros stlsq_gram leaves when max_iter
+    ends its loop right after the drop before that solve."""
+    (lens, obs, ctrls, designs, configs), kw = request(name, [k])
+    G = SF.design_gram(np.asarray(lens), obs, ctrls, designs[0], kw.get("ycont"))
+    nf, thr, counts = len(designs[0][0]), float(configs[0][2]), set()
+    for j in range(obs.shape[1]):
+        natural = SF.stlsq_gram(G, nf, nf + j, thr, alpha_of(k), 20)[4]
+        for m in range(1, natural):
+            counts.add(int(np.count_nonzero(SF.stlsq_gram(G, nf, nf + j, thr, alpha_of(k), m)[0])))
+    return counts
+
+
+def test_first_features_truncates_the_feature_arrays_only():
+    lib = new_model("small", 6).library
+    cut = first_features(lib, 20)
+    assert [len(a) for a in cut[:4]] == [20] * 4 and all(np.array_equal(a, b[:20]) for a, b in zip(cut[:4], lib))
+    assert cut[4] is lib[4] and cut[5] is lib[5] and len(lib[4]) > 0
+    for (name, k), n in [(c, int(c[1].split(":")[1].rstrip("c"))) for c in EDGE_SMALL + EDGE_WIDE + LIMITS]:
+        assert new_model(name, k).library[0].shape == (n,) and new_model(name, k).coefficients.shape[1] == n
+    with pytest.raises(ValueError):
+        first_features(lib, len(lib[0]) + 1)
+
+
+@pytest.mark.parametrize("name,k,xdot", STATUS0)
+def test_new_cases_cannot_hide_behind_a_decline(name, k, xdot):
+    """What keeps a GPU test from passing by a decline: on the host restatement alone every new case is fitted with
+    train()'s support, a smallest squared pivot >= 4 x the pivot line and a smallest margin >= 16 x the tie line."""
+    ref = trained(name, k, xdot)
+    c, status, pivot, margin, iters = host_fit(name, k, xdot)
+    n = ref.shape[1]
+    print("stlsq_gram_host %s %s%s: %d features, err %.2e, pivot^2 %.2e (%.1f x the line), margin %.2e, %d solves"
+          % (name, k, " xdot" if xdot else "", n, rel_err(c, ref), pivot, pivot / (n * PIVOT_EPS), margin, iters))
+    assert status == 0 and same_support(c, ref) and rel_err(c, ref) <= 1e-9
+    assert pivot >= 4 * n * PIVOT_EPS and margin >= 16 * SF.TIE_MARGIN
+    if (name, k) in ALPHAS:
+        assert iters == {0.0: 2, 10.0: 3}[alpha_of(k)] and not np.array_equal(ref, trained(name, k[0]))
+
+
+def test_later_solves_of_the_new_cases_keep_1_8_and_9_features():
+    """The back substitution's degenerate case and both sides of the Cholesky panel width (8) are reached by solves
+    on a gathered sub-matrix.  (Counted over the 3 / 1 cases; the union over all new cases only grows.)"""
+    counts = set()
+    for name, k in EDGE_SMALL + EDGE_KEPT + ALPHAS:
+        counts |= _kept_counts(name, k)
+    assert {1, 8, 9} <= counts
+    assert 1 not in set().union(*(_kept_counts(*c) for c in EDGE_SMALL + ALPHAS))     # why EDGE_KEPT exists
+
+
+def test_the_cases_that_must_decline_do_so_on_the_host():
+    """Library D (a feature twice) is singular without the ridge: status 1 by a failed pivot at alpha 0 and by the
+    pivot line at alpha 1e-9, and a fit at 0.05; an all-zero control column at alpha 0 is a zero diagonal entry."""
+    for a in (0.0, 1e-9):
+        ks = [NEIGHBOURS[a][0][1], ("dup", a), NEIGHBOURS[a][1][1]]
+        args, kw = request("small", ks)
+        c, status, pivot, margin, iters = SF.stlsq_gram_host(*args, **kw)
+        assert list(status) == [1 if k[0] == "dup" else 0 for k in ks] and np.all(np.isnan(c[1]))
+        assert np.array_equal(c[0], host_fit("small", ks[0])[0]) and np.array_equal(c[2], host_fit("small", ks[2])[0])
+    assert iters[1] == 1 and 0 < pivot[1] < 13 * PIVOT_EPS                        # (the 1e-9 call)
+    args, kw = request("small", [("states", 0.0), (1, 0.0), ("states_c", 0.0)])
+    args = args[:2] + (np.zeros_like(args[2]),) + args[3:]
+    c, status, pivot, margin, iters = SF.stlsq_gram_host(*args, **kw)
+    assert list(status) == [0, 1, 0] and pivot[1] == 0.0 and iters[1] == 0 and np.all(np.isnan(c[1]))
+    assert pivot[0] >= 4 * 3 * PIVOT_EPS and min(margin[0], margin[2]) >= 16 * SF.TIE_MARGIN
+    m = new_model("small", ("dup", 1e-9))
+    rep = SF.fit_sindy_models([m], data("small")[1], alpha=1e-9, backend="numpy")
+    assert rep[0]["where"] == "host" and rep[0]["reason"] == "status 1" and rep[0]["iters"] == 1
+    assert np.array_equal(m.coefficients, trained("small", ("dup", 1e-9)))
+
+
+def test_both_target_sets_share_one_design():
+    for name, kd, kc in BOTH:
+        assert len(request(name, [kd, kc])[0][3]) == 1 and request(name, [kd, kc])[1]["ycont"] is not None
 
 
 def test_models_of_two_libraries_share_two_designs():
