@@ -20,7 +20,10 @@ LIB_PATH = os.environ.get("AMPC_LIB") or os.path.join(_HERE, "libautompc_hip.so"
 
 
 class AmpcError(RuntimeError):
-    pass
+    code = -1          # the library call's return code
+
+
+MPPI_TABLE_NO_FIT = -3     # ampc_mppi_plan_set_model_table: the table kernel's LDS map exceeds 160 KB for this plan
 
 
 _lib = None
@@ -103,6 +106,8 @@ SIGNATURES = {
                                           _ip, POINTER(ctypes.c_longlong)]),
     "ampc_ilqr_plan_set_models": (c_int, [c_void_p, c_int, POINTER(c_void_p)]),
     "ampc_mppi_plan_set_models": (c_int, [c_void_p, c_int, POINTER(c_void_p), _ip]),
+    "ampc_mppi_plan_set_model_table": (c_int, [c_void_p, c_int, _ip, _ip, _ip, POINTER(c_void_p), POINTER(c_void_p),
+                                               POINTER(c_void_p), _ip, _ip]),
     "ampc_kstep_errors": (c_int, [POINTER(c_void_p), c_int, c_int, _ip, c_int, _dp, _dp, _dp, c_int, _dp, _dp,
                                   _dp]),
     "ampc_kstep_errors_linear": (c_int, [POINTER(c_void_p), c_int, c_int, _ip, c_int, _dp, _dp, _ip, _ip, _ip, _ip, _dp,
@@ -162,7 +167,9 @@ def legacy_log_mode():
 def check(rc):
     if rc != 0:
         msg = load().ampc_last_error()
-        raise AmpcError(msg.decode() if msg else "libautompc_hip error %d" % rc)
+        err = AmpcError(msg.decode() if msg else "libautompc_hip error %d" % rc)
+        err.code = int(rc)
+        raise err
 
 
 def as_f64(a):
@@ -549,6 +556,31 @@ class MppiPlan:
         mi = None if not hs else np.ascontiguousarray(np.broadcast_to(np.asarray(model_index, dtype=np.int32), (self.B,)))
         check(self.lib.ampc_mppi_plan_set_models(self._p, len(hs), arr, iptr(mi)))
         self._models = hs
+
+    def set_model_table(self, models, model_index):
+        """MLP models of any mix of depth, widths and activation per problem (ampc_mppi_plan_set_model_table, f64):
+        `models` are sysid.MLP models of the plan handle's system, model_index [B] names each problem's.  Device-
+        resident fits hand over their tensors' addresses and are read in place; the plan keeps them (and the host
+        arrays of the others) alive.  The call fixes the plan's geometry to 16-row tiles: call it before upload().
+        None / empty models: removes the table.  A refusal raises AmpcError; its ``code`` is MPPI_TABLE_NO_FIT when
+        the plan's states / controls / horizon cap / cost block do not fit the kernel's LDS."""
+        ms = list(models or [])
+        if not ms:
+            check(self.lib.ampc_mppi_plan_set_model_table(self._p, 0, None, None, None, None, None, None, None, None))
+            self._table_args = None
+            return
+        from .evaluation.model_metrics import mlp_batch_args
+        args = mlp_batch_args(ms)
+        mi = np.ascontiguousarray(np.broadcast_to(np.asarray(model_index, dtype=np.int32), (self.B,)))
+        if args["on_device"].any():
+            import torch
+            # (the fit's kernels have finished before the rollout reads their parameters)
+            torch.cuda.current_stream(torch.device("cuda", int(self.handle.device))).synchronize()
+        vpp = lambda a: a.ctypes.data_as(POINTER(c_void_p))
+        check(self.lib.ampc_mppi_plan_set_model_table(
+            self._p, len(ms), iptr(args["n_hidden"]), iptr(args["dims"]), iptr(args["acts"]), vpp(args["weights"]),
+            vpp(args["biases"]), vpp(args["norms"]), iptr(args["on_device"]), iptr(mi)))
+        self._table_args = args            # (keeps the parameters the table points into alive)
 
     def solve(self):
         check(self.lib.ampc_mppi_solve(self._p))

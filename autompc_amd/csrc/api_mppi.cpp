@@ -8,6 +8,7 @@
 #include <atomic>
 #include <mutex>
 #include "jit_host.hpp"                // shape plugins compiled at run time
+#include "mppi_table_host.hpp"         // ampc_mppi_plan_set_model_table: checks and packing without a device call
 
 extern template int pred_impl<double>(ampc_handle*, const double*, const double*, double*, double*, double*, int);
 extern template int pred_impl<float>(ampc_handle*, const double*, const double*, double*, double*, double*, int);
@@ -89,7 +90,10 @@ template <typename T> static int plan_build(ampc_mppi_plan* p) {
   // pipe.  AMPC_QUAD: -1 automatic, 0 never, 1 whenever the shape is supported.
   p->quad = false;
   p->eps_inline = false;
-  if (sizeof(T) == 8 && h->has_mlp && q4_supported(m.hpad, m.n_hidden, m.nxp, m.k1p)) {
+  // a table of MLP models of mixed shapes (ampc_mppi_plan_set_model_table): 16-row tiles of mppi_rollout_table_kernel,
+  // its own LDS map, no static shape and no plugin
+  const bool table = p->table_n > 0;
+  if (!table && sizeof(T) == 8 && h->has_mlp && q4_supported(m.hpad, m.n_hidden, m.nxp, m.k1p)) {
     long long tiles16 = 0;
     for (int b = 0; b < p->B; ++b) tiles16 += (p->N[b] + 15) / 16;
     const int mode = env_int("AMPC_QUAD", -1);
@@ -103,6 +107,8 @@ template <typename T> static int plan_build(ampc_mppi_plan* p) {
           "most two hidden layers) and at most 32 states");
   if (p->quad) {
     p->mt = 0;
+  } else if (table) {
+    p->mt = 1;
   } else if (h->has_sindy) {
     p->mt = 4;
   } else if (h->has_lin) {
@@ -126,6 +132,9 @@ template <typename T> static int plan_build(ampc_mppi_plan* p) {
   p->tile_m = M;
   if (p->quad) {
     std::memset(&p->L, 0, sizeof(p->L));          // (the kernel derives its own map: make_q4_lds)
+  } else if (table) {
+    std::memset(&p->L, 0, sizeof(p->L));
+    p->L.extra = mppi_table_lds_base();            // act[2][16][257], xu[16][81], norm[288] (mppi_table_kernels.hpp)
   } else if (h->has_sindy) {
     std::memset(&p->L, 0, sizeof(p->L));
     p->L.extra = (2 * nx + nu + h->s_ntab) * 64;   // per-thread columns: [x|u], next x, value table
@@ -161,7 +170,7 @@ template <typename T> static int plan_build(ampc_mppi_plan* p) {
   p->static_shape = -1;
   p->jit = nullptr;
   // (indicator cost terms live in the run-time-shape kernels only: mppi_kernels.hpp)
-  const bool ext = h->n_ind > 0;
+  const bool ext = h->n_ind > 0 || table;
   if (ext) {
   } else if (p->quad && env_int("AMPC_STATIC", 1) != 0) {          // (the four-row kernel has one LDS map)
     int sid = static_shape_of<T>(h, m);
@@ -302,6 +311,7 @@ extern "C" int ampc_mppi_plan_destroy(ampc_mppi_plan* p) {
   if (p->lg_drawn) (void)hipEventDestroy(p->lg_drawn);
   for (DevBuf* b : bufs) b->release();
   p->mlp_tab.release(); p->tile_order.release();
+  p->table_models.release(); p->table_stage.release();
   for (ampc_handle* mh : p->models) handle_release(mh);
   for (hipEvent_t e : p->ev) (void)hipEventDestroy(e);
   ampc_handle* h = p->h;
@@ -340,6 +350,8 @@ extern "C" int ampc_mppi_plan_set_models(ampc_mppi_plan* p, int n_models, ampc_h
     return 0;
   }
   REQUIRE(n_models >= 1 && models && model_index, "ampc_mppi_plan_set_models: NULL argument");
+  REQUIRE(p->table_n == 0, "ampc_mppi_plan_set_models: the plan holds a table of MLP models of mixed shapes "
+                           "(ampc_mppi_plan_set_model_table); remove it first");
   for (int i = 0; i < n_models; ++i)
     if (int rc = check_same_shape(p->h, models[i], "ampc_mppi_plan_set_models")) return rc;
   for (int b = 0; b < p->B; ++b)
@@ -839,6 +851,16 @@ extern "C" int ampc_mppi_plan_set_geometry(ampc_mppi_plan* p, int tile_rows, int
   REQUIRE(tile_rows == 0 || tile_rows == 4 || tile_rows == 16 || tile_rows == 32 || tile_rows == 64,
           "ampc_mppi_plan_set_geometry: tile_rows must be 0 (automatic), 4, 16, 32 or 64");
   REQUIRE(horizon_cap >= 0, "ampc_mppi_plan_set_geometry: horizon_cap < 0");
+  REQUIRE(p->table_n == 0 || tile_rows == 0 || tile_rows == 16,
+          "ampc_mppi_plan_set_geometry: a plan that holds a table of MLP models (ampc_mppi_plan_set_model_table) rolls "
+          "out in 16-row tiles: tile_rows must be 0 or 16");
+  if (p->table_n > 0) {
+    int mh = horizon_cap;
+    for (int hb : p->H) mh = hb > mh ? hb : mh;
+    mh = p->max_h > mh ? p->max_h : mh;
+    REQUIRE(mppi_table_lds_bytes(mppi_table_lds_base(), p->h->cost_stride, p->h->nu, mh, false) <= kLdsLimit,
+            "ampc_mppi_plan_set_geometry: this horizon cap needs more than 160 KB of LDS in the table kernel");
+  }
   HIP_OK(hipSetDevice(p->h->device));
   HIP_OK(hipStreamSynchronize(p->h->stream));
   p->forced_mt = tile_rows / 16;
@@ -862,6 +884,101 @@ extern "C" int ampc_mppi_plan_set_geometry(ampc_mppi_plan* p, int tile_rows, int
     if (int rc = build_tile_order(p)) return rc;
   }
   return redraw ? ampc_mppi_generate_eps(p, seed, stream) : 0;
+}
+
+
+// ---------------------------------------------------------------------------------------------
+// MLP models of any mix of depth, widths and activation in one plan (mppi_table_kernels.hpp)
+// ---------------------------------------------------------------------------------------------
+size_t kstep_mlp_model_bytes();
+void kstep_mlp_pack_model(void* dst, int n_layers, int act, const int* dims, const double* const* w,
+                          const double* const* b, const double* const* norm);
+
+// Rebuild the plan's geometry around a change of its model table; device noise drawn before is drawn again
+// (ampc_mppi_plan_set_geometry).
+static int mppi_table_rebuild(ampc_mppi_plan* p) {
+  p->forced_quad = false;
+  p->forced_mt = p->table_n > 0 ? 1 : p->forced_mt;
+  p->lds_eps = -1;
+  p->lds_red = 0;
+  const bool redraw = p->eps_from_generator;
+  const uint64_t seed = p->eps_seed, stream = p->eps_stream;
+  p->eps_from_generator = false; p->ahead_valid = false; p->ahead_on = false;
+  if (int rc = p->h->precision == AMPC_F64 ? plan_build<double>(p) : plan_build<float>(p)) return rc;
+  return redraw ? ampc_mppi_generate_eps(p, seed, stream) : 0;
+}
+
+extern "C" int ampc_mppi_plan_set_model_table(ampc_mppi_plan* p, int n_models, const int* n_hidden, const int* dims,
+                                              const int* activations, const double* const* weights,
+                                              const double* const* biases, const double* const* norms,
+                                              const int* on_device, const int* model_index) {
+  if (!p) return mppi_table_fail("NULL plan");
+  ampc_handle* h = p->h;
+  if (n_models == 0) {                               // back to the handle's own model and the automatic geometry
+    if (p->table_n == 0) return 0;
+    HIP_OK(hipSetDevice(h->device));
+    HIP_OK(hipStreamSynchronize(h->stream));
+    p->table_n = 0;
+    p->model_idx.clear();
+    p->table_models.release(); p->table_stage.release();
+    p->forced_mt = 0;
+    return mppi_table_rebuild(p);
+  }
+  MppiTablePlanView v;
+  v.f64 = h->precision == AMPC_F64; v.has_mlp = h->has_mlp; v.nx = h->nx; v.nu = h->nu; v.obs_dim = h->obs_dim;
+  v.n_ind = h->n_ind; v.lift_n = p->lift_n; v.n_shape_models = (int)p->models.size();
+  v.B = p->B; v.max_h = p->max_h; v.cost_stride = h->cost_stride;
+  KstepMlpPrep prep;
+  if (int rc = mppi_table_check(v, n_models, n_hidden, dims, activations, weights, biases, norms, on_device, model_index,
+                                mppi_table_lds_base(), kLdsLimit, &prep))
+    return rc;
+  HIP_OK(hipSetDevice(h->device));
+  const int ML = prep.max_layers;
+  auto resident = [&](const void* q) -> int {
+    hipPointerAttribute_t attr;
+    const hipError_t e = hipPointerGetAttributes(&attr, q);
+    if (e != hipSuccess) (void)hipGetLastError();     // (a host address is an error of the query: not left behind)
+    if (!(e == hipSuccess && attr.type == hipMemoryTypeDevice && attr.device == h->device))
+      return mppi_table_fail("a model flagged as device-resident has a parameter that is not device memory of the "
+                             "plan's device");
+    return 0;
+  };
+  for (int k = 0; k < n_models; ++k) {
+    if (!on_device[k]) continue;
+    for (int l = 0; l <= n_hidden[k]; ++l) {
+      if (int rc = resident(weights[(size_t)k * ML + l])) return rc;
+      if (int rc = resident(biases[(size_t)k * ML + l])) return rc;
+    }
+    for (int i = 0; i < 4; ++i)
+      if (int rc = resident(norms[(size_t)k * 4 + i])) return rc;
+  }
+  // (a running solve may read the table being replaced)
+  HIP_OK(hipStreamSynchronize(h->stream));
+  if (!prep.stage.empty()) {
+    HIP_OK(p->table_stage.reserve(prep.stage.size() * 8));
+    HIP_OK(hipMemcpy(p->table_stage.p, prep.stage.data(), prep.stage.size() * 8, hipMemcpyHostToDevice));
+  }
+  const size_t mb = kstep_mlp_model_bytes();
+  std::vector<char> table((size_t)n_models * mb);
+  const double* sb = (const double*)p->table_stage.p;
+  for (int k = 0; k < n_models; ++k) {
+    const double* w[8] = {nullptr};
+    const double* b[8] = {nullptr};
+    const double* nm[4];
+    for (int l = 0; l <= n_hidden[k]; ++l) {
+      const size_t e = (size_t)k * ML + l;
+      w[l] = on_device[k] ? weights[e] : sb + prep.w_off[e];
+      b[l] = on_device[k] ? biases[e] : sb + prep.b_off[e];
+    }
+    for (int i = 0; i < 4; ++i) nm[i] = on_device[k] ? norms[(size_t)k * 4 + i] : sb + prep.n_off[(size_t)k * 4 + i];
+    kstep_mlp_pack_model(table.data() + (size_t)k * mb, n_hidden[k] + 1, activations[k], dims + (size_t)k * (ML + 1),
+                         w, b, nm);
+  }
+  HIP_OK(p->table_models.reserve(table.size()));
+  HIP_OK(hipMemcpy(p->table_models.p, table.data(), table.size(), hipMemcpyHostToDevice));
+  p->table_n = n_models;
+  p->model_idx.assign(model_index, model_index + p->B);
+  return mppi_table_rebuild(p);
 }
 
 extern "C" int ampc_mppi_plan_set_step_offset(ampc_mppi_plan* p, uint64_t first_step) {

@@ -474,7 +474,16 @@ struct ampc_mppi_plan {
   long long timing_count = 0;
   std::vector<hipEvent_t> ev;   // 3 per solve: before rollout, after rollout, after update
   size_t ev_used = 0;
+  // MLP models of any mix of shapes (ampc_mppi_plan_set_model_table, f64): the device table of their entries
+  // (KstepMlpModel, kstep_mlp_kernels.hpp) and the host-resident parameters the call uploaded; model_idx names a
+  // problem's entry.  table_n > 0: the plan runs mppi_rollout_table_kernel in 16-row tiles (plan_build).
+  int table_n = 0;
+  DevBuf table_models, table_stage;
 };
+
+// launch_mppi_table.cpp (f64 only, not part of a shape plugin)
+int mppi_table_lds_base();
+int mppi_table_launch(ampc_mppi_plan* p, const void* args);
 
 template <typename T> static MppiArgs<T> make_args(ampc_mppi_plan* p) {
   ampc_handle* h = p->h;

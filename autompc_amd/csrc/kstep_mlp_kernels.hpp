@@ -220,6 +220,9 @@ __device__ __forceinline__ void km_layer(const double* __restrict__ W, const dou
   }
 }
 
+// (a unit that shares the layer routines above with a kernel of its own -- mppi_table_kernels.hpp -- leaves this
+//  kernel out: it is defined once, in launch_kstep_mlp.cpp)
+#ifndef AMPC_KM_LAYERS_ONLY
 __global__ __launch_bounds__(kKmThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void kstep_mlp_table_kernel(const KstepMlpModel* __restrict__ models,
                                                                       const KstepMlpArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -320,5 +323,6 @@ __global__ __launch_bounds__(kKmThreads) __attribute__((amdgpu_waves_per_eu(2, 2
   __syncthreads();
   if (tid == 0) tile_sum(a.kmax);
 }
+#endif  // AMPC_KM_LAYERS_ONLY
 
 }  // namespace ampc

@@ -21,6 +21,13 @@ template <typename T> int mppi_solve_impl(ampc_mppi_plan* p) {
   if (!p->models.empty() && p->static_shape < 0 && !p->jit)
     return fail("ampc_mppi_solve: the plan holds a table of controller models but is no longer on the shape-specialised "
                 "kernels (its geometry was rebuilt?): call ampc_mppi_plan_set_models again after ampc_mppi_plan_set_geometry");
+  // (a table of MLP models of mixed shapes -- ampc_mppi_plan_set_model_table -- runs mppi_rollout_table_kernel: quadratic
+  //  cost blocks on the observation only)
+  if (p->table_n > 0 && p->h->n_ind > 0)
+    return fail("ampc_mppi_solve: the plan holds a table of MLP models (ampc_mppi_plan_set_model_table) and its handle has "
+                "indicator cost terms; the table kernel takes quadratic cost blocks only");
+  if (p->table_n > 0 && p->lift_n > 0)
+    return fail("ampc_mppi_solve: the plan holds a table of MLP models (ampc_mppi_plan_set_model_table) and a state lift");
   if (p->jit) return jit_result(p->jit, p->jit->mppi_solve(p));     // same function, compiled for the shape
 #endif
   ampc_handle* h = p->h;
@@ -80,7 +87,13 @@ template <typename T> int mppi_solve_impl(ampc_mppi_plan* p) {
     if (sizeof(T) != 8) return fail("internal: four-row rollout in f32");      // (launched above)
   } else
 #ifndef AMPC_JIT_PLUGIN
-  if (h->has_lin) {               // wide linear model (linear_kernels.hpp)
+  if (p->table_n > 0) {           // MLP models of mixed shapes through a device table (mppi_table_kernels.hpp)
+    if constexpr (sizeof(T) == 8) {
+      if (int rc = mppi_table_launch(p, &a)) return rc;
+    } else {
+      return fail("internal: table rollout in f32");
+    }
+  } else if (h->has_lin) {        // wide linear model (linear_kernels.hpp)
     HIP_OK(allow_lds(linear_rollout_kernel<T>, p->lds_bytes));
     hipLaunchKernelGGL(linear_rollout_kernel<T>, dim3(p->n_tiles), dim3(64 * kLinW), p->lds_bytes, h->stream, a,
                        lin_of<T>(h));

@@ -119,6 +119,40 @@ def _by_model(candidates, default):
     return list(groups.values())
 
 
+def table_decision(candidates, default, precision="f64", device=0, task_cost=None, obs_dim=None, ctrl_dim=None,
+                   lift=None):
+    """(True, "") when ONE MPPI plan with a model table (MppiPlan.set_model_table) takes the whole batch, else
+    (False, why).  It does when every candidate's controller model (`default` for a candidate without a "model") passes
+    ``mlp_batch_key`` -- an f64 ``MLP`` with the class's own ``pred_batch`` inside the kernel's limits -- with one common
+    key on the evaluator's device, the evaluator computes in f64, the task cost has no indicator (threshold / box)
+    terms and the controller model is not lifted.  Needs no GPU."""
+    from ..evaluation.model_metrics import mlp_batch_key
+    if precision != "f64":
+        return False, "the table kernel is f64 only"
+    if lift is not None:
+        return False, "the controller model's state is a lift of the observation"
+    if task_cost is not None:
+        try:
+            kinds, _ = cost_terms(task_cost, obs_dim, ctrl_dim)
+        except TypeError:
+            kinds = ()
+        if any(int(k) != 0 for k in kinds):
+            return False, "the task cost has indicator terms"
+    keys = set()
+    for c in candidates:
+        m = c.get("model") if isinstance(c, dict) else None
+        m = default if m is None else m
+        key = mlp_batch_key(m, obs_dim)
+        if key is None:
+            return False, "%s is not an f64 MLP within the table kernel's limits" % type(m).__name__
+        keys.add(key)
+    if len(keys) != 1:
+        return False, "the candidates' models live on different devices or systems"
+    if next(iter(keys))[1] != int(device):
+        return False, "the models live on another device than the evaluator"
+    return True, ""
+
+
 def _needs_specialised_kernels(err):
     """The library's refusal of a model TABLE on a plan that runs the run-time-shape kernels (several models of one
     unregistered shape whose plugin is not built -- and, for one-evaluation models, never will be)."""
@@ -268,14 +302,24 @@ class CandidateEvaluator:
     accepts_global_ids = True          # evaluate(index_offset=<array of global indices>) is understood
 
     def __init__(self, system, task, model, surrogate=None, precision="f64", device=0,
-                 tile_rows=32, horizon_cap=30, term_check_every=8):
-        """tile_rows / horizon_cap fix the rollout geometry (MppiPlan.set_geometry) so that a
+                 tile_rows=32, horizon_cap=30, term_check_every=8, mlp_models="shape"):
+        """mlp_models: "shape" -- candidates that carry controller models of different shapes run in one plan per
+        shape -- or "table": one plan with a model table for the whole batch (MppiPlan.set_model_table, 16-row tiles
+        of one kernel) whenever ``table_decision`` allows it, the "shape" way otherwise.  ``last_models`` tells what
+        the last evaluate() did: {"path": "table" | "shape", "models": n, "plans": n}.
+
+        tile_rows / horizon_cap fix the rollout geometry (MppiPlan.set_geometry) so that a
         candidate's score is bit-identical for any batch it is evaluated in; horizon_cap defaults
         to the top of the reference's MPPI horizon range (mppi.py:52-55).  term_check_every: with
         a user termination condition the episode runs on the device in segments of this many
         control steps, the condition being asked on the host in between."""
         self.tile_rows, self.horizon_cap = int(tile_rows), int(horizon_cap)
         self.term_check_every = max(1, int(term_check_every))
+        if mlp_models not in ("shape", "table"):
+            raise ValueError('mlp_models must be "shape" or "table", not %r' % (mlp_models,))
+        self.mlp_models = mlp_models
+        self.last_models = None
+        self._table = False
         if not hasattr(model, "stage_into"):
             raise TypeError("needs a device-stageable model (autompc_amd.sysid.MLP)")
         self.system, self.task, self.model = system, task, model
@@ -342,7 +386,29 @@ class CandidateEvaluator:
                              "CandidateEvaluator(horizon_cap=...) for the range being searched"
                              % (max(too_long), self.horizon_cap))
         ids = global_ids(index_offset, B)
+        n_models = len(candidate_models(candidates, self.model)[0])
+        if self.mlp_models == "table" and not self._table:
+            ok, _why = table_decision(candidates, self.model, self.precision, self.device, self.task.get_cost(),
+                                      self.system.obs_dim, self.system.ctrl_dim, self._lift)
+            if ok:
+                import copy
+                sub = copy.copy(self)
+                sub._table = True
+                opened = []
+                try:
+                    out = sub._evaluate(candidates, n_steps, seed, init_obs, eps_all, act_init, return_trajectories,
+                                        ids, opened, timing)
+                    self.last_lengths = sub.last_lengths
+                    self.last_models = {"path": "table", "models": n_models, "plans": 1}
+                    return out
+                except _lib.AmpcError as e:
+                    if e.code != _lib.MPPI_TABLE_NO_FIT:      # (the kernel's LDS map: the "shape" way takes the batch)
+                        raise
+                finally:
+                    _close_or_defer(self, opened)
         shape_groups = _by_model_shape(candidates, self.model)
+        self.last_models = {"path": "shape", "models": n_models,
+                            "plans": 1 if shape_groups is None else len(shape_groups)}
         if shape_groups is not None:
             # Candidates that carry controller models of DIFFERENT shapes (pipeline.py:138-145: a model per
             # configuration): one plan per shape, evaluated in turn; same-shape models share a plan
@@ -366,6 +432,7 @@ class CandidateEvaluator:
             if not _needs_specialised_kernels(e) or own_only or eps_all is not None or act_init is not None \
                     or timing is not None:
                 raise
+            self.last_models["plans"] = len(by_model)
             return self._evaluate_shape_groups(by_model, candidates, ids, dict(
                 n_steps=n_steps, seed=seed, init_obs=init_obs, return_trajectories=return_trajectories))
         finally:
@@ -384,6 +451,7 @@ class CandidateEvaluator:
         def run_group(idx):
             sub = copy.copy(self)
             sub._close_later = later
+            sub.mlp_models = "shape"                      # (the batch was declined as a whole: every group goes the default way)
             sub.model = candidates[idx[0]]["model"]       # the group's plan handle is staged with one of ITS models
             # (sub.surrogate stays the evaluator's simulation model: copy.copy kept the reference)
             return idx, sub, sub.evaluate([candidates[i] for i in idx], index_offset=ids[idx], **kw)
@@ -429,21 +497,24 @@ class CandidateEvaluator:
     def _stage(self, candidates, opened):
         nu, no = self.system.ctrl_dim, self.system.obs_dim
         B = len(candidates)
-        h = _lib.Handle(self.device, self.precision, jit=getattr(self.model, "jit_kernels", True))
+        h = _lib.Handle(self.device, self.precision,
+                        jit=False if self._table else getattr(self.model, "jit_kernels", True))
         opened.append(h)
         self.model.stage_into(h)
         # controller models the candidates carry (same shape as the evaluator's: evaluate() groups by shape):
         # one handle each, holding only the weights; the plan gets their table (ampc_mppi_plan_set_models)
         models, self._model_index = candidate_models(candidates, self.model)
         self._model_handles = []
-        if len(models) > 1 or models[0] is not self.model:
+        self._table_models = models if self._table else None       # (no per-model handles: the plan reads a table)
+        if not self._table and (len(models) > 1 or models[0] is not self.model):
             self._model_handles = [model_handle(m, self.device, self.precision, opened) for m in models]
         blocks, _ = candidate_cost_blocks(candidates, self.goal, no, nu)
         h.set_cost_blocks(**blocks)
         h.set_ctrl_bounds(self.umin, self.umax)
         sur = None
         if self.surrogate is not self.model:
-            sur = _lib.Handle(self.device, self.precision)
+            sur = _lib.Handle(self.device, self.precision, jit=False) if self._table else \
+                _lib.Handle(self.device, self.precision)
             opened.append(sur)
             self.surrogate.stage_into(sur)
         return h, sur
@@ -455,7 +526,9 @@ class CandidateEvaluator:
                              [float(candidates[i]["sigma"]) for i in which],
                              [float(candidates[i]["lmda"]) for i in which], cost_index=np.asarray(which))
         opened.append(plan)
-        plan.set_geometry(self.tile_rows, self.horizon_cap)
+        plan.set_geometry(16 if self._table else self.tile_rows, self.horizon_cap)
+        if self._table:
+            plan.set_model_table(self._table_models, self._model_index[np.asarray(which)])
         if self._lift is not None:
             plan.set_state_lift(*self._lift)
         plan.set_noise_ids(np.asarray(noise_ids)[which])

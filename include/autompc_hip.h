@@ -449,6 +449,24 @@ int ampc_ilqr_plan_set_models(ampc_ilqr_plan* p, int n_models, ampc_handle* cons
  * problem b then runs on models[model_index[b]] (MLP plans: the sixteen-row and the four-row rollout). */
 int ampc_mppi_plan_set_models(ampc_mppi_plan* p, int n_models, ampc_handle* const* models,
                               const int* model_index);
+/* MLP models of ANY mix of depth, widths and activation in one f64 MPPI plan: the rollout of every problem b runs on
+ * entry model_index[b] of a device table, in 16-row tiles of one kernel for the whole plan (csrc/mppi_table_kernels.hpp).
+ * The model arguments are those of ampc_kstep_errors_mlp (below): host-resident parameters are packed and uploaded
+ * once by this call, on_device parameters are read in place (memory of the plan's device; the caller keeps it alive
+ * and orders its own writes before the call).  The plan keeps the table until it is destroyed or n_models = 0 removes
+ * it.  The call rebuilds the plan's geometry (as ampc_mppi_plan_set_geometry(p, 16, horizon cap) does: call it before
+ * uploads); ampc_mppi_plan_set_geometry afterwards keeps the table and takes tile_rows 0 or 16 only.
+ * Refused with a message: an f32 plan; a handle whose model is not an MLP, that has indicator cost terms (again at
+ * solve time if they are set later), a state lift, per-problem models of one shape (ampc_mppi_plan_set_models);
+ * models whose nx / nu are not the handle's, obs_dim != nx, anything over ampc_kstep_errors_mlp's limits; a
+ * model_index out of range; and -- return code -3 instead of -1 -- an LDS map of more than 160 KB for the plan's
+ * states, controls, horizon cap and cost block.
+ * Deterministic: a problem's controls are the same bits alone, in any plan, at any position of it.  (Added without a
+ * version bump: callers detect it by its symbol.) */
+int ampc_mppi_plan_set_model_table(ampc_mppi_plan* p, int n_models, const int* n_hidden, const int* dims,
+                                   const int* activations, const double* const* weights,
+                                   const double* const* biases, const double* const* norms, const int* on_device,
+                                   const int* model_index);
 
 /* simulate() with IterativeLQR controllers, device resident (utils/simulation.py:44-63 as eval_cfg drives it,
  * pipeline_tuner.py:222-231; IterativeLQR.run, ilqr.py:267-295: every control step is a full solve from a zero
