@@ -24,6 +24,7 @@ class AmpcError(RuntimeError):
 
 
 MPPI_TABLE_NO_FIT = -3     # ampc_mppi_plan_set_model_table: the table kernel's LDS map exceeds 160 KB for this plan
+ILQR_TABLE_NO_FIT = -3     # ampc_ilqr_plan_set_model_table: the same for the table iteration kernel
 
 
 _lib = None
@@ -108,6 +109,8 @@ SIGNATURES = {
     "ampc_mppi_plan_set_models": (c_int, [c_void_p, c_int, POINTER(c_void_p), _ip]),
     "ampc_mppi_plan_set_model_table": (c_int, [c_void_p, c_int, _ip, _ip, _ip, POINTER(c_void_p), POINTER(c_void_p),
                                                POINTER(c_void_p), _ip, _ip]),
+    "ampc_ilqr_plan_set_model_table": (c_int, [c_void_p, c_int, _ip, _ip, _ip, POINTER(c_void_p), POINTER(c_void_p),
+                                               POINTER(c_void_p), _ip]),
     "ampc_kstep_errors": (c_int, [POINTER(c_void_p), c_int, c_int, _ip, c_int, _dp, _dp, _dp, c_int, _dp, _dp,
                                   _dp]),
     "ampc_kstep_errors_linear": (c_int, [POINTER(c_void_p), c_int, c_int, _ip, c_int, _dp, _dp, _ip, _ip, _ip, _ip, _dp,
@@ -792,6 +795,30 @@ class IlqrPlan:
         arr = (c_void_p * max(len(hs), 1))(*[h._h for h in hs])
         check(self.lib.ampc_ilqr_plan_set_models(self._p, len(hs), arr))
         self._models = hs                   # (kept alive on this side as well)
+
+    def set_model_table(self, models):
+        """MLP models of any mix of depth, widths and activation (ampc_ilqr_plan_set_model_table, f64): `models` are
+        sysid.MLP models of the plan handle's system; solve_queue / closed_loop then take model_index (entry 0
+        without it).  Device-resident fits hand over their tensors' addresses and are read in place; the plan keeps
+        them (and the host arrays of the others) alive.  None / empty models: removes the table.  A refusal raises
+        AmpcError; its ``code`` is ILQR_TABLE_NO_FIT when the plan's states / controls / cost block do not fit the
+        kernel's LDS."""
+        ms = list(models or [])
+        if not ms:
+            check(self.lib.ampc_ilqr_plan_set_model_table(self._p, 0, None, None, None, None, None, None, None))
+            self._table_args = None
+            return
+        from .evaluation.model_metrics import mlp_batch_args
+        args = mlp_batch_args(ms)
+        if args["on_device"].any():
+            import torch
+            # (the fit's kernels have finished before the solves read their parameters)
+            torch.cuda.current_stream(torch.device("cuda", int(self.handle.device))).synchronize()
+        vpp = lambda a: a.ctypes.data_as(POINTER(c_void_p))
+        check(self.lib.ampc_ilqr_plan_set_model_table(
+            self._p, len(ms), iptr(args["n_hidden"]), iptr(args["dims"]), iptr(args["acts"]), vpp(args["weights"]),
+            vpp(args["biases"]), vpp(args["norms"]), iptr(args["on_device"])))
+        self._table_args = args            # (keeps the parameters the table points into alive)
 
     def _model_index(self, model_index, n):
         if model_index is None:

@@ -4,6 +4,7 @@
 #include "host_common.hpp"
 #include <mutex>
 #include "jit_host.hpp"                // shape plugins compiled at run time
+#include "ilqr_table_host.hpp"         // ampc_ilqr_plan_set_model_table: checks and the LDS map without a device call
 
 extern template int pred_impl<double>(ampc_handle*, const double*, const double*, double*, double*, double*, int);
 extern template int pred_impl<float>(ampc_handle*, const double*, const double*, double*, double*, double*, int);
@@ -203,6 +204,7 @@ extern "C" int ampc_ilqr_plan_destroy(ampc_ilqr_plan* p) {
                     &p->q_obj, &p->q_flags, &p->c_ints, &p->c_iters, &p->c_stage, &p->c_obs, &p->c_ctl, &p->slot_h, &p->vj};
   for (DevBuf* b : bufs) b->release();
   p->mlp_tab.release(); p->slot_model.release(); p->slot_of.release();
+  p->table_models.release(); p->table_stage.release(); p->table_dz.release();
   for (ampc_handle* mh : p->models) handle_release(mh);
   for (hipEvent_t e : p->ev) (void)hipEventDestroy(e);
   if (p->poll_host) (void)hipHostFree(p->poll_host);
@@ -494,9 +496,11 @@ static int check_horizons(const ampc_ilqr_plan* p, int n, const int* horizon, co
 
 static int check_models(const ampc_ilqr_plan* p, int n, const int* model_index, const char* who) {
   if (model_index) {
-    REQUIRE(!p->models.empty(), std::string(who) + ": model_index given but the plan has no model table (ampc_ilqr_plan_set_models)");
+    REQUIRE(!p->models.empty() || p->table_n > 0,
+            std::string(who) + ": model_index given but the plan has no model table (ampc_ilqr_plan_set_models)");
+    const int n_models = p->table_n > 0 ? p->table_n : (int)p->models.size();
     for (int j = 0; j < n; ++j)
-      REQUIRE(model_index[j] >= 0 && model_index[j] < (int)p->models.size(), std::string(who) + ": bad model_index");
+      REQUIRE(model_index[j] >= 0 && model_index[j] < n_models, std::string(who) + ": bad model_index");
   }
   return 0;
 }
@@ -511,6 +515,8 @@ extern "C" int ampc_ilqr_plan_set_models(ampc_ilqr_plan* p, int n_models, ampc_h
     return 0;
   }
   REQUIRE(n_models >= 1 && models, "ampc_ilqr_plan_set_models: NULL argument");
+  REQUIRE(p->table_n == 0, "ampc_ilqr_plan_set_models: the plan holds a table of MLP models of mixed shapes "
+                           "(ampc_ilqr_plan_set_model_table); remove it first");
   for (int i = 0; i < n_models; ++i)
     if (int rc = check_same_shape(p->h, models[i], "ampc_ilqr_plan_set_models")) return rc;
   if (p->static_shape < 0) {
@@ -524,6 +530,94 @@ extern "C" int ampc_ilqr_plan_set_models(ampc_ilqr_plan* p, int n_models, ampc_h
   }
   return p->h->precision == AMPC_F64 ? build_model_table<double>(p->h, n_models, models, &p->mlp_tab, &p->models)
                                      : build_model_table<float>(p->h, n_models, models, &p->mlp_tab, &p->models);
+}
+
+// ---------------------------------------------------------------------------------------------
+// MLP models of any mix of depth, widths and activation in one plan (ilqr_table_kernels.hpp)
+// ---------------------------------------------------------------------------------------------
+size_t kstep_mlp_model_bytes();
+void kstep_mlp_pack_model(void* dst, int n_layers, int act, const int* dims, const double* const* w,
+                          const double* const* b, const double* const* norm);
+
+extern "C" int ampc_ilqr_plan_set_model_table(ampc_ilqr_plan* p, int n_models, const int* n_hidden, const int* dims,
+                                              const int* activations, const double* const* weights,
+                                              const double* const* biases, const double* const* norms,
+                                              const int* on_device) {
+  if (!p) return ilqr_table_fail("NULL plan");
+  ampc_handle* h = p->h;
+  if (n_models == 0) {                               // back to the handle's own model and its kernels
+    if (p->table_n == 0) return 0;
+    HIP_OK(hipSetDevice(h->device));
+    HIP_OK(hipStreamSynchronize(h->stream));
+    p->table_n = 0; p->table_wmax = 0; p->table_hidden = 0;
+    p->table_models.release(); p->table_stage.release(); p->table_dz.release();
+    return ilqr_plan_build<double>(p);               // (the kernel choices of the handle's shape)
+  }
+  IlqrTablePlanView v;
+  v.f64 = h->precision == AMPC_F64;
+  v.has_mlp = h->has_mlp && !h->has_sindy && !h->has_lin && h->lin_n == 0;    // (a small linear model is staged as a network)
+  v.nx = h->nx; v.nu = h->nu; v.obs_dim = h->obs_dim;
+  v.n_shape_models = (int)p->models.size(); v.cost_stride = h->cost_stride;
+  KstepMlpPrep prep;
+  if (int rc = ilqr_table_check(v, n_models, n_hidden, dims, activations, weights, biases, norms, on_device,
+                                ilqr_table_lds_base(), kLdsLimit, &prep))
+    return rc;
+  HIP_OK(hipSetDevice(h->device));
+  const int ML = prep.max_layers;
+  auto resident = [&](const void* q) -> int {
+    hipPointerAttribute_t attr;
+    const hipError_t e = hipPointerGetAttributes(&attr, q);
+    if (e != hipSuccess) (void)hipGetLastError();     // (a host address is an error of the query: not left behind)
+    if (!(e == hipSuccess && attr.type == hipMemoryTypeDevice && attr.device == h->device))
+      return ilqr_table_fail("a model flagged as device-resident has a parameter that is not device memory of the "
+                             "plan's device");
+    return 0;
+  };
+  for (int k = 0; k < n_models; ++k) {
+    if (!on_device[k]) continue;
+    for (int l = 0; l <= n_hidden[k]; ++l) {
+      if (int rc = resident(weights[(size_t)k * ML + l])) return rc;
+      if (int rc = resident(biases[(size_t)k * ML + l])) return rc;
+    }
+    for (int i = 0; i < 4; ++i)
+      if (int rc = resident(norms[(size_t)k * 4 + i])) return rc;
+  }
+  // (a running solve may read the table being replaced)
+  HIP_OK(hipStreamSynchronize(h->stream));
+  // From here on the plan holds NO table until the new one is complete: a failure below leaves the plan on its
+  // handle's own model, never on entries that point into memory this call has overwritten or released.
+  p->table_n = 0; p->table_wmax = 0; p->table_hidden = 0;
+  p->static_shape = -1;
+  p->jit = nullptr;
+  int wmax = 0, hmax = 0;
+  ilqr_table_extent(n_models, n_hidden, dims, ML, &wmax, &hmax);
+  const size_t mb = kstep_mlp_model_bytes();
+  HIP_OK(p->table_dz.reserve((size_t)hmax * p->B * round_up(p->H, 16) * wmax * 8));
+  HIP_OK(p->table_models.reserve((size_t)n_models * mb));
+  if (!prep.stage.empty()) {
+    HIP_OK(p->table_stage.reserve(prep.stage.size() * 8));
+    HIP_OK(hipMemcpy(p->table_stage.p, prep.stage.data(), prep.stage.size() * 8, hipMemcpyHostToDevice));
+  }
+  std::vector<char> table((size_t)n_models * mb);
+  const double* sb = (const double*)p->table_stage.p;
+  for (int k = 0; k < n_models; ++k) {
+    const double* w[8] = {nullptr};
+    const double* b[8] = {nullptr};
+    const double* nm[4];
+    for (int l = 0; l <= n_hidden[k]; ++l) {
+      const size_t e = (size_t)k * ML + l;
+      w[l] = on_device[k] ? weights[e] : sb + prep.w_off[e];
+      b[l] = on_device[k] ? biases[e] : sb + prep.b_off[e];
+    }
+    for (int i = 0; i < 4; ++i) nm[i] = on_device[k] ? norms[(size_t)k * 4 + i] : sb + prep.n_off[(size_t)k * 4 + i];
+    kstep_mlp_pack_model(table.data() + (size_t)k * mb, n_hidden[k] + 1, activations[k], dims + (size_t)k * (ML + 1),
+                         w, b, nm);
+  }
+  HIP_OK(hipMemcpy(p->table_models.p, table.data(), table.size(), hipMemcpyHostToDevice));
+  // (the run-time-shape sweep serves every model of the table; no shape-specialised kernel or plugin is involved:
+  //  static_shape / jit were cleared above)
+  p->table_n = n_models; p->table_wmax = wmax; p->table_hidden = hmax;
+  return 0;
 }
 
 extern "C" int ampc_ilqr_solve_queue_var(ampc_ilqr_plan* p, int n_problems, const double* x0, const double* uguess,

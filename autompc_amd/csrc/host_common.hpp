@@ -599,7 +599,19 @@ struct ampc_ilqr_plan {
   DevBuf vj;                    // wide linear models: the sweep's VJ scratch [B][nxp][ldj] (ilqr_wide.hpp)
   DevBuf c_ints, c_iters, c_stage, c_obs, c_ctl;   // ampc_ilqr_closed_loop: chain bookkeeping, staged rows, trajectories
   long long last_queue_launches = 0;   // iterations launched by the last queue solve
+  // MLP models of any mix of shapes (ampc_ilqr_plan_set_model_table, f64): the device table of their entries
+  // (KstepMlpModel, kstep_mlp_kernels.hpp), the host-resident parameters the call uploaded and the stored activation
+  // derivatives [table_hidden][B * padded H][table_wmax] of the refresh.  table_n > 0: the line search, the forward
+  // pass and the Jacobian chain are ilqr_table_kernels.hpp's, on the run-time-shape sweep; a queue problem / episode
+  // names its entry (ampc_ilqr_*_var), the slot carries it.  (Behind everything a shape plugin reads.)
+  int table_n = 0, table_wmax = 0, table_hidden = 0;
+  DevBuf table_models, table_stage, table_dz;
 };
+
+// launch_ilqr_table.cpp (f64 only, not part of a shape plugin)
+int ilqr_table_lds_base();
+int ilqr_table_launch_iter(ampc_ilqr_plan* p, const void* args);
+int ilqr_table_refresh(ampc_ilqr_plan* p);
 
 template <typename T> static IlqrArgs<T> make_ilqr_args(ampc_ilqr_plan* p, int mode) {
   ampc_handle* h = p->h;

@@ -153,6 +153,16 @@ def table_decision(candidates, default, precision="f64", device=0, task_cost=Non
     return True, ""
 
 
+def ilqr_table_decision(candidates, default, precision="f64", device=0, obs_dim=None, ctrl_dim=None):
+    """(True, "") when ONE iLQR plan with a model table (IlqrPlan.set_model_table) takes the whole batch, else (False,
+    why): ``table_decision`` without a task cost -- it only scores the trajectories here, so indicator terms in it are
+    no obstacle -- and the sweep's limit of 63 states + controls.  Needs no GPU."""
+    ok, why = table_decision(candidates, default, precision, device, None, obs_dim, ctrl_dim)
+    if ok and int(obs_dim) + int(ctrl_dim) > 63:
+        return False, "state dim + ctrl dim exceeds 63, the iLQR sweep's limit"
+    return ok, why
+
+
 def _needs_specialised_kernels(err):
     """The library's refusal of a model TABLE on a plan that runs the run-time-shape kernels (several models of one
     unregistered shape whose plugin is not built -- and, for one-evaluation models, never will be)."""
@@ -719,15 +729,27 @@ class IlqrCandidateEvaluator:
     accepts_global_ids = True
 
     def __init__(self, system, task, model, surrogate=None, precision="f64", device=0, device_resident=True,
-                 max_slots=1024, max_threads=32, one_plan=True):
+                 max_slots=1024, max_threads=32, one_plan=True, mlp_models="shape"):
         """device_resident: episodes of known length run entirely on the device (ampc_ilqr_closed_loop_var;
         a user termination condition is asked on the host, one queue of solves per control step);
         max_slots: problems solved side by side (one workgroup each);
         one_plan = False: the round-4 scheme, kept for comparison (tools/ilqr_eval_rate.py) -- one plan per
         horizon, the horizon groups evaluated concurrently on max_threads host threads (one plan and stream
-        each); same scores bit for bit."""
+        each); same scores bit for bit;
+        mlp_models: "shape" -- candidates that carry controller models of different shapes run in one plan per
+        shape (the default); "table" -- they run in ONE plan on a device table of their parameters
+        (IlqrPlan.set_model_table: the line search, forward pass and Jacobian chain of csrc/ilqr_table_kernels.hpp)
+        whenever ``ilqr_table_decision`` allows it, the "shape" way otherwise (one_plan=False: refused).  ``last_models`` tells
+        what the last evaluate() did: {"path": "table" | "shape", "models": distinct models, "plans": plans built}."""
         self.device_resident, self.max_slots, self.max_threads = bool(device_resident), int(max_slots), max(1, int(max_threads))
         self.one_plan = bool(one_plan)
+        if mlp_models not in ("shape", "table"):
+            raise ValueError('mlp_models must be "shape" or "table", not %r' % (mlp_models,))
+        if mlp_models == "table" and not self.one_plan:
+            raise ValueError('mlp_models="table" puts every candidate into one plan: it needs one_plan=True')
+        self.mlp_models = mlp_models
+        self.last_models = None
+        self._table = False
         if not hasattr(model, "stage_into"):
             raise TypeError("needs a device-stageable model (autompc_amd.sysid.MLP)")
         if precision != "f64":
@@ -760,7 +782,30 @@ class IlqrCandidateEvaluator:
         B = len(candidates)
         if B == 0:
             return (np.zeros(0), None, None) if return_trajectories else np.zeros(0)
+        n_models = len(candidate_models(candidates, self.model)[0])
+        if self.mlp_models == "table" and not self._table:
+            ok, _why = ilqr_table_decision(candidates, self.model, self.precision, self.device,
+                                           self.system.obs_dim, self.system.ctrl_dim)
+            if ok:
+                import copy
+                sub = copy.copy(self)
+                sub._table = True
+                opened = []
+                try:
+                    out = sub._evaluate(candidates, n_steps, init_obs, return_trajectories, int(max_iter), opened)
+                    self.last_lengths = sub.last_lengths
+                    if hasattr(sub, "last_iterations"):
+                        self.last_iterations = sub.last_iterations
+                    self.last_models = {"path": "table", "models": n_models, "plans": 1}
+                    return out
+                except _lib.AmpcError as e:
+                    if e.code != _lib.ILQR_TABLE_NO_FIT:      # (the kernel's LDS map: the "shape" way takes the batch)
+                        raise
+                finally:
+                    _close_or_defer(self, opened)
         shape_groups = _by_model_shape(candidates, self.model)
+        self.last_models = {"path": "shape", "models": n_models,
+                            "plans": 1 if shape_groups is None else len(shape_groups)}
         if shape_groups is not None:       # controller models of different shapes: one plan per shape, in turn
             return CandidateEvaluator._evaluate_shape_groups(
                 self, shape_groups, candidates, global_ids(index_offset, B),
@@ -773,6 +818,7 @@ class IlqrCandidateEvaluator:
             own_only = len(by_model) == 1 and (candidates[0].get("model") is None or candidates[0]["model"] is self.model)
             if not _needs_specialised_kernels(e) or own_only:
                 raise
+            self.last_models["plans"] = len(by_model)
             return CandidateEvaluator._evaluate_shape_groups(
                 self, by_model, candidates, global_ids(index_offset, B),
                 dict(n_steps=n_steps, init_obs=init_obs, return_trajectories=return_trajectories, max_iter=max_iter))
@@ -804,14 +850,21 @@ class IlqrCandidateEvaluator:
         # the plan gets their table (ampc_ilqr_plan_set_models), a queue problem / episode names its entry
         models, model_index = candidate_models(candidates, self.model)
         model_handles = []
-        if len(models) > 1 or models[0] is not self.model:
+        table = self._table                   # ONE plan on a table of the models' parameters: no handle per model
+        if not table and (len(models) > 1 or models[0] is not self.model):
             if not self.one_plan:
                 raise ValueError("candidates that carry their own model need the one-plan evaluator (one_plan=True)")
             model_handles = [model_handle(m, self.device, self.precision, opened) for m in models]
         for H, idx in groups.items():
-            h = _lib.Handle(self.device, self.precision, jit=getattr(self.model, "jit_kernels", True))
+            # (table: the handle gives the plan its dimensions, costs and sweep -- no shape-specialised kernel runs)
+            h = _lib.Handle(self.device, self.precision, jit=False if table else getattr(self.model, "jit_kernels", True))
             opened.append(h)
-            self.model.stage_into(h)
+            base = self.model
+            if table:
+                # (the evaluator's own model when it is an MLP of the table's kind, else the first candidate's)
+                from ..evaluation.model_metrics import mlp_batch_key
+                base = self.model if mlp_batch_key(self.model, no) is not None else models[0]
+            base.stage_into(h)
             blocks, term_goal = candidate_cost_blocks([candidates[i] for i in idx], self.goal, no, nu)
             h.set_cost_blocks(**blocks)
             if self.bounded:
@@ -822,8 +875,10 @@ class IlqrCandidateEvaluator:
             opened.append(plan)
             if model_handles:
                 plan.set_models(model_handles)
+            if table:
+                plan.set_model_table(models)
             plans[H] = (plan, np.array(idx))
-        mi_all = model_index if model_handles else None
+        mi_all = model_index if (model_handles or table) else None
         obs = np.full((B, n_ctl + 1, nx), np.nan)
         ctl = np.full((B, n_ctl + 1, nu), np.nan)
         init_obs = np.asarray(init_obs, dtype=np.float64)

@@ -44,8 +44,9 @@ int ampc_version(void);   /* 100 * major + minor; 104: + ampc_mppi_run_legacy; 1
                            *      ampc_mppi_plan_set_models, ampc_ilqr_plan_set_models; 107: + ampc_set_mlp_dev, ampc_ilqr_plan_set_constants;
                            * 108: + ampc_kstep_errors; 109: + ampc_lqr_*; 110: + ampc_linfit_fit;
                            * 111: + ampc_kstep_errors_linear; 112: + ampc_kstep_errors_sindy;
-                           * 113: + ampc_sindy_fit; 114: + ampc_lasso_fit; + ampc_stable_fit, + ampc_mlpfit_*, + ampc_kstep_errors_mlp (no bump:
-                           *      callers detect them by their symbols) */
+                           * 113: + ampc_sindy_fit; 114: + ampc_lasso_fit; + ampc_stable_fit, + ampc_mlpfit_*, + ampc_kstep_errors_mlp,
+                           *      + ampc_mppi_plan_set_model_table, + ampc_ilqr_plan_set_model_table (no bump: callers detect them by
+                           *      their symbols) */
 int ampc_device_count(void);
 
 /* ---- handle ------------------------------------------------------------------------------ */
@@ -467,6 +468,26 @@ int ampc_mppi_plan_set_model_table(ampc_mppi_plan* p, int n_models, const int* n
                                    const int* activations, const double* const* weights,
                                    const double* const* biases, const double* const* norms, const int* on_device,
                                    const int* model_index);
+
+/* MLP models of ANY mix of depth, widths and activation in one f64 iLQR plan: the slot of a problem / episode runs on
+ * the entry of a device table that model_index[n] of ampc_ilqr_solve_queue_var / ampc_ilqr_closed_loop_var names (range-
+ * checked against the table; NULL, and the entries without that argument -- ampc_ilqr_solve, _solve_queue,
+ * _closed_loop -- run entry 0).  The line search, the forward pass and the Jacobian chain of an iteration are the
+ * kernels of csrc/ilqr_table_kernels.hpp (16-row tiles, one kernel each for the whole plan), the sweep is the plan's
+ * run-time-shape sweep; refill / compaction / chains, the surrogate step, harvest, stats, timing, set_constants and
+ * set_terminal_goal are the plan's own.  The model arguments are those of ampc_kstep_errors_mlp (below): host-
+ * resident parameters are packed and uploaded once by this call, on_device parameters are read in place (memory of the
+ * plan's device; the caller keeps it alive and orders its own writes before the call).  The plan keeps the table until
+ * it is destroyed or n_models = 0 removes it.
+ * Refused with a message: a NULL plan / argument; an f32 plan; a handle whose model is not an MLP (SINDy and linear
+ * models included); obs_dim != nx; models whose nx / nu are not the handle's; anything over ampc_kstep_errors_mlp's
+ * limits; nx + nu > 63; a plan that holds ampc_ilqr_plan_set_models handles (and that call on a plan with a table);
+ * and -- return code -3 instead of -1 -- an LDS map of more than 160 KB for the plan's states, controls and cost block.
+ * Deterministic: a problem's results are the same bits alone, in any plan, in any slot, at any position of the table.
+ * (Added without a version bump: callers detect it by its symbol.) */
+int ampc_ilqr_plan_set_model_table(ampc_ilqr_plan* p, int n_models, const int* n_hidden, const int* dims,
+                                   const int* activations, const double* const* weights,
+                                   const double* const* biases, const double* const* norms, const int* on_device);
 
 /* simulate() with IterativeLQR controllers, device resident (utils/simulation.py:44-63 as eval_cfg drives it,
  * pipeline_tuner.py:222-231; IterativeLQR.run, ilqr.py:267-295: every control step is a full solve from a zero
