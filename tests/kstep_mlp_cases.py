@@ -1,5 +1,7 @@
 """Shared builders of the ``ampc_kstep_errors_mlp`` tests: the models and trajectories of the reference-generated
 fixtures tests/golden/kstep_mlp_*.npz (the recipe of test_gpu_model_metrics.py), and a seeded synthetic data set."""
+import functools
+
 import numpy as np
 
 from conftest import golden
@@ -49,3 +51,204 @@ def synthetic_trajs(system, lens=(40, 23, 31, 17), seed=0):
         ctrls = rng.uniform(-1, 1, size=(L, system.ctrl_dim))
         out.append(Trajectory(system, L, obs, ctrls))
     return out
+
+
+# ---- an independent reference of the raw sums, in any numpy float type ------------------------------------------
+SELU_ALPHA, SELU_SCALE = 1.6732632423543772848170429916717, 1.0507009873554804934193349852946   # mlpfit_kernels.hpp
+
+
+def _act(name, z):
+    one = z.dtype.type(1)
+    if name == "relu":
+        return np.where(z > 0, z, z.dtype.type(0))
+    if name == "tanh":
+        return np.tanh(z)
+    if name == "sigmoid":
+        return one / (one + np.exp(-z))
+    if name == "selu":
+        return z.dtype.type(SELU_SCALE) * np.where(z > 0, z, z.dtype.type(SELU_ALPHA) * np.expm1(np.minimum(z, 0)))
+    raise ValueError(name)
+
+
+def _cast(params, dtype):
+    return ([np.asarray(w, dtype=dtype) for w in params["weights"]], [np.asarray(b, dtype=dtype) for b in params["biases"]],
+            [np.asarray(params[k], dtype=dtype) for k in ("xu_means", "xu_std", "dy_means", "dy_std")])
+
+
+def _step(cast, act, x, u):
+    """in = ([x, u] - xu_mean) / xu_std;  a = act(a W' + b);  x' = x + (z dy_std + dy_mean)."""
+    W, B, (xm, xs, dm, ds) = cast
+    a = (np.concatenate([x, u], axis=1) - xm) / xs
+    for w, b in zip(W[:-1], B[:-1]):
+        a = _act(act, a @ w.T + b)
+    return x + ((a @ W[-1].T + B[-1]) * ds + dm)
+
+
+def kstep_sums_ref(params, act, trajs, kmax, dtype, horizons=None):
+    """(S [kmax], D [kmax]), the raw sums ``MM.kstep_sums_mlp(..., delta=True)`` returns, computed horizon by horizon and
+    trajectory by trajectory as get_model_rmse / get_model_rmsmens do: obs[:L - h] rolled forward h steps with ctrls[k :
+    L - h + k]; S[h - 1] the sum of the squared state errors, D[h - 1] that of the squared differences of the predicted
+    and the actual last increment, each over the data's increment std.  A trajectory of L <= h rows adds nothing; no
+    index is clamped.  ``dtype`` is the type of every operation (np.longdouble: the reference; np.float64: what
+    rounding does to it); ``horizons``: only these are computed, the others stay 0.  Calls neither pred_batch nor the
+    oracle nor the library."""
+    from autompc_amd.evaluation import model_metrics as MM
+    cast = _cast(params, dtype)
+    std = np.asarray(MM._increment_stats(trajs)[1], dtype=dtype)
+    S, D = np.zeros(kmax, dtype=dtype), np.zeros(kmax, dtype=dtype)
+    for h in (range(1, kmax + 1) if horizons is None else horizons):
+        for t in trajs:
+            L = len(t)
+            if L <= h:
+                continue
+            obs, ctrls = np.asarray(t.obs, dtype=dtype), np.asarray(t.ctrls, dtype=dtype)
+            x = obs[:L - h]
+            for k in range(h):
+                prev, x = x, _step(cast, act, x, ctrls[k:L - h + k])
+            S[h - 1] += np.sum((x - obs[h:]) ** 2)
+            D[h - 1] += np.sum(((x - prev) / std - (obs[h:] - obs[h - 1:L - 1]) / std) ** 2)
+    return S, D
+
+
+def reference(params, act, trajs, kmax):
+    """(S, D, cond): the long-double sums and the largest relative deviation of the f64 run from them -- what the
+    rounding of ANY f64 evaluation does to this case."""
+    S, D = kstep_sums_ref(params, act, trajs, kmax, np.longdouble)
+    with np.errstate(all="ignore"):
+        S64, D64 = kstep_sums_ref(params, act, trajs, kmax, np.float64)
+    return S, D, max(deviation(S64, S), deviation(D64, D))
+
+
+def deviation(a, ref):
+    """Largest relative deviation of `a` from the long-double `ref`, taken in long double."""
+    return float(np.max(np.abs(np.asarray(a, dtype=np.longdouble) / ref - 1)))
+
+
+def bound(cond):
+    """A device result against a host restatement: 100 x the host's own measured rounding, floor 1e-13
+    (linfit_cases.tolerance)."""
+    return max(1e-13, 100.0 * cond)
+
+
+# ---- the shape sweep: (nx, nu, hidden widths, activation) -------------------------------------------------------
+SWEEP = [(1, 1, [1], "relu"),                  # in 2: everything minimal, a one-unit layer
+         (15, 1, [15], "tanh"),                # in 16: one full block, no ragged block
+         (16, 1, [17, 31], "sigmoid"),         # in 17
+         (16, 16, [32, 33], "selu"),           # in 32: two full blocks
+         (17, 16, [48, 63, 64], "relu"),       # in 33: three blocks; hidden in 48 (odd, unragged), 63, 64
+         (32, 16, [65, 16], "tanh"),           # in 48; width 65: the waves take 2, 1, 1, 1 tiles
+         (48, 16, [129, 127, 128], "sigmoid"),  # in 64; three output tiles (wave 3 has none)
+         (63, 1, [193, 192], "selu"),          # in 64; 13 tiles: 4, 3, 3, 3
+         (64, 16, [241, 240, 255, 1], "relu"),  # in 80: the input limit, depth 4, four output tiles
+         (63, 16, [256, 15, 256], "tanh"),     # in 79
+         (2, 1, [64, 64, 64, 64], "selu"),     # depth 4, every hidden in unragged and even
+         (3, 2, [80, 112], "sigmoid"),         # hidden in 80 and 112: 5 and 7 blocks
+         (64, 16, [255], "selu"),
+         (64, 16, [16, 256, 16, 256], "tanh")]
+SWEEP_LENS = (18, 1, 2, 9, 6, 3)
+SWEEP_KMAX = 6
+# parameter seeds: 300 + case, but for case 0, whose one relu unit is dead on all of its data at seed 300 -- the sums
+# would then not depend on a weight (a kernel that skipped the first layer's only, ragged, block passed the case)
+SWEEP_SEEDS = {0: 504}
+# further models on the data of a sweep case, for the batches: (sweep case whose system and data they take, hidden, act)
+EXTRA = [(3, [48], "relu"), (3, [17, 31, 65], "sigmoid")]
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_data(i, lens=SWEEP_LENS):
+    nx, nu, _, _ = SWEEP[i]
+    return tuple(synthetic_trajs(make_system(nx, nu), lens, seed=20 + i))
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_params(i):
+    nx, nu, hidden, act = SWEEP[i]
+    return golden_params(nx, nu, hidden, act, SWEEP_SEEDS.get(i, 300 + i))
+
+
+@functools.lru_cache(maxsize=None)
+def extra_params(j):
+    i, hidden, act = EXTRA[j]
+    return golden_params(SWEEP[i][0], SWEEP[i][1], hidden, act, 400 + j)
+
+
+def first_layer_active(i):
+    """Per unit of sweep case i's first hidden layer: the share of the data's rows on which its pre-activation is
+    positive."""
+    p, trajs = sweep_params(i), sweep_data(i)
+    xu = np.concatenate([np.concatenate([t.obs, t.ctrls], axis=1) for t in trajs])
+    z = ((xu - p["xu_means"]) / p["xu_std"]) @ p["weights"][0].T + p["biases"][0]
+    return np.mean(z > 0, axis=0)
+
+
+def sweep_model(i):
+    nx, nu, hidden, act = SWEEP[i]
+    return mlp_of(sweep_data(i)[0].system, sweep_params(i), hidden, act)
+
+
+def extra_model(j):
+    i, hidden, act = EXTRA[j]
+    return mlp_of(sweep_data(i)[0].system, extra_params(j), hidden, act)
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_reference(i, lens=SWEEP_LENS, kmax=SWEEP_KMAX):
+    """(S, D, cond) of sweep case i on its data of `lens`; computed once per process, never modified."""
+    return reference(sweep_params(i), SWEEP[i][3], list(sweep_data(i, lens)), kmax)
+
+
+@functools.lru_cache(maxsize=None)
+def extra_reference(j):
+    i, _, act = EXTRA[j]
+    return reference(extra_params(j), act, list(sweep_data(i)), SWEEP_KMAX)
+
+
+# row and horizon edges, on the models of two sweep cases: (trajectory lengths, kmax)
+EDGE_MODELS = (3, 7)
+EDGE_DATA = [((17,), 6),                    # 16 start points: exactly one tile
+             ((18,), 6),                    # a tile plus one row
+             (SWEEP_LENS, 6),               # 33 start points
+             ((1, 18, 1), 6),               # one-row trajectories first and last: the last data row has no successor
+             ((18,), 1), ((18,), 17)]       # the shortest and the longest horizon of the data
+
+
+# the systems that hold three models: sweep cases and extra models on the data of the first
+BATCHES = {"16x16": ([3], [0, 1]), "64x16": ([8, 12, 13], [])}
+
+
+# ---- the select: a row whose uncounted continuation leaves f64 ---------------------------------------------------
+SELECT_CASE, SELECT_LENS, SELECT_GAIN = 4, (18, 2, 9), 8192.0
+
+
+def clamped_continuation(params, act, traj, kmax):
+    """What the kernel computes for the start point at row 0 of `traj`, in f64: the state rolled on for kmax steps with
+    the control and observation indices clamped into the trajectory, and every step's summed squared error."""
+    cast = _cast(params, np.float64)
+    obs, ctrls = np.asarray(traj.obs, dtype=np.float64), np.asarray(traj.ctrls, dtype=np.float64)
+    rem = len(traj) - 1
+    x, out = obs[:1], []
+    with np.errstate(all="ignore"):
+        for j in range(1, kmax + 1):
+            x = _step(cast, act, x, ctrls[min(j, rem) - 1][None])
+            out.append(float(np.sum((x - obs[min(j, rem)]) ** 2)))
+    return np.array(out)
+
+
+@functools.lru_cache(maxsize=None)
+def select_case():
+    """(params, act, trajs, scale): the relu sweep case with its output increments widened by SELECT_GAIN -- the sweep's
+    own models change a state by a few percent per step, which no scale of the data turns into an overflow within six
+    steps -- and data whose second trajectory has two rows, scaled by the largest power of ten at which the row's one
+    counted squared error stays below 1e300."""
+    from autompc_amd import Trajectory
+    nx, nu, hidden, act = SWEEP[SELECT_CASE]
+    system = make_system(nx, nu)
+    p = dict(sweep_params(SELECT_CASE))
+    p["dy_std"] = p["dy_std"] * SELECT_GAIN
+    base = synthetic_trajs(system, SELECT_LENS, seed=20 + SELECT_CASE)
+    for e in range(154, 100, -1):
+        t = base[1]
+        big = Trajectory(system, 2, t.obs * 10.0 ** e, t.ctrls.copy())
+        if clamped_continuation(p, act, big, 1)[0] < 1e300:
+            return p, act, (base[0], big, base[2]), 10.0 ** e
+    raise AssertionError("no scale keeps the counted step finite")

@@ -12,6 +12,11 @@ Tolerances.  1e-9 relative against the reference, the host loop and the per-shap
 test_gpu_model_metrics.py and test_gpu_kstep_sindy.py hold this quantity to.  A plain f64 evaluation with a reordered,
 16-blocked sum deviates from these goldens by at most 4.4e-16, so all of it is rounding allowance.  Bitwise claims are
 exact.
+
+The shape sweep (tests 8 to 10) is held tighter, against kstep_mlp_cases.kstep_sums_ref in long double: the raw sums S and
+D to max(1e-13, 100 x cond) relative, cond the deviation of the reference's own f64 run from its long-double run on
+that case (at most 3.0e-16 on the sweep, so the floor decides).  test_kstep_mlp_host.py holds the reference to the
+goldens (1.8e-16) and every case's cond to 1e-14.  Measured on the MI355X: DESIGN 6k.
 """
 import numpy as np
 import pytest
@@ -22,6 +27,7 @@ from autompc_amd.evaluation import HoldoutModelEvaluator, model_errors
 from autompc_amd.evaluation import model_metrics as MM
 from autompc_amd.tuning.configs import DictConfiguration
 from helpers import golden_params, make_system
+import kstep_mlp_cases as K
 from kstep_mlp_cases import TAGS, fixture_model, mlp_of, synthetic_trajs
 
 pytestmark = pytest.mark.gpu
@@ -294,3 +300,102 @@ def test_refusals():
     # and after the refusals the entry still scores
     _lib.check(call())
     assert np.all(np.isfinite(S)) and np.array_equal(S, MM.kstep_sums_mlp([a], trajs, 3)[0])
+
+
+# 8 ---------------------------------------------------------------------------------------------------------------
+def test_the_sweep_covers_what_it_claims():
+    ins = {nx + nu for nx, nu, _, _ in K.SWEEP}
+    hidden = {h for _, _, hs, _ in K.SWEEP for h in hs}
+    assert {16, 32, 48, 64, 80} <= ins and {2, 17, 33, 79} <= ins            # 1..5 blocks without a ragged one, and ragged
+    assert {1, 15, 16, 17, 32, 48, 63, 64} <= {nx for nx, *_ in K.SWEEP}
+    assert {-(-nx // 16) for nx, *_ in K.SWEEP} == {1, 2, 3, 4}               # output tiles: waves without one
+    assert {1, 2, 16} <= {nu for _, nu, _, _ in K.SWEEP}
+    assert {1, 15, 16, 17, 31, 32, 33, 63, 64, 65, 127, 128, 129, 192, 193, 240, 241, 255, 256} <= hidden
+    assert {48, 80, 112} <= hidden                                           # the next layer's unragged `in`, odd blocks
+    assert {-(-h // 16) % 4 for h in hidden} == {0, 1, 2, 3}                  # the waves' tile counts differ, or not
+    assert {(-(-h // 16) - w + 3) // 4 for h in hidden for w in range(min(4, -(-h // 16)))} == {1, 2, 3, 4}   # km_layer<NT>
+    assert {len(hs) for _, _, hs, _ in K.SWEEP} == {1, 2, 3, 4}
+    assert {a for *_, a in K.SWEEP} == {"relu", "tanh", "sigmoid", "selu"}
+    for act in ("relu", "tanh", "sigmoid", "selu"):                          # the error buffer: (n_layers - 1) & 1
+        assert {len(hs) & 1 for _, _, hs, a in K.SWEEP if a == act} == {0, 1}, act
+    # both exits of the two-block pipeline, in the first layer and behind a hidden one
+    assert {-(-i // 16) & 1 for i in ins} == {0, 1} and {-(-h // 16) & 1 for h in hidden} == {0, 1}
+    assert [K.SWEEP[i][:2] for i in K.BATCHES["64x16"][0]] == [(64, 16)] * 3
+    assert K.SWEEP[K.BATCHES["16x16"][0][0]][:2] == (16, 16) and all(K.EXTRA[j][0] == 3 for j in K.BATCHES["16x16"][1])
+
+
+def _held(what, S, D, ref):
+    """Device sums against the long-double reference: every figure printed, then held to the bound."""
+    S_ref, D_ref, cond = ref
+    tol = K.bound(cond)
+    dS, dD = K.deviation(S, S_ref), K.deviation(D, D_ref)
+    print("kstep mlp %s: S %.2e D %.2e from the long-double reference; cond %.2e, bound %.2e" % (what, dS, dD, cond, tol))
+    assert np.all(np.isfinite(S)) and np.all(np.isfinite(D))
+    assert dS <= tol and dD <= tol, (what, dS, dD, tol)
+
+
+@pytest.mark.parametrize("case", range(len(K.SWEEP)))
+def test_shape_sweep_against_the_long_double_reference(case):
+    m = K.sweep_model(case)
+    S, D = MM.kstep_sums_mlp([m], list(K.sweep_data(case)), K.SWEEP_KMAX, delta=True)
+    assert m._handle is None
+    _held("sweep %d %r" % (case, K.SWEEP[case]), S[0], D[0], K.sweep_reference(case))
+
+
+# 9 ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", K.EDGE_MODELS)
+def test_row_and_horizon_edges_against_the_long_double_reference(case):
+    m = K.sweep_model(case)
+    for lens, kmax in K.EDGE_DATA:
+        trajs = list(K.sweep_data(case, lens))
+        assert MM.row_counts(trajs, 1)[0] == sum(L - 1 for L in lens)
+        S, D = MM.kstep_sums_mlp([m], trajs, kmax, delta=True)
+        _held("sweep %d on lengths %r, kmax %d" % (case, lens, kmax), S[0], D[0], K.sweep_reference(case, lens, kmax))
+        S0, none = MM.kstep_sums_mlp([m], trajs, kmax)                      # without the delta sums: the same S
+        assert none is None and np.array_equal(S0, S)
+
+
+def test_rows_past_their_horizon_are_selected_away_not_multiplied_by_zero():
+    """A two-row trajectory at 1e149: its start point counts at horizon 1 only, with a squared error of 1.4e299; the
+    kernel rolls it on with clamped indices and its error leaves f64 from step 5 on (test_kstep_mlp_host.py asserts
+    both on an f64 emulation).  0 x inf would make every later sum NaN; the reference never forms those values.
+
+    The model is a synthetic one, not a sweep model: the relu sweep case's shape and weights with its dy_std widened
+    by 8192 (kstep_mlp_cases.select_case).  The sweep's models change a state by a few percent per step, so scaling the
+    observations alone, whatever the scale, overflows nothing within six steps."""
+    p, act, trajs, scale = K.select_case()
+    nx, nu, hidden, _ = K.SWEEP[K.SELECT_CASE]
+    m = mlp_of(trajs[0].system, p, hidden, act)
+    ref = K.reference(p, act, list(trajs), K.SWEEP_KMAX)
+    with np.errstate(all="ignore"):
+        S, D = MM.kstep_sums_mlp([m], list(trajs), K.SWEEP_KMAX, delta=True)
+    print("kstep mlp select: scale %g, S %s, D %s" % (scale, S[0], D[0]))
+    assert np.all(np.isfinite(S)) and np.all(np.isfinite(D)) and S[0, 0] > 1e298
+    _held("select, horizons 2..", S[0, 1:], D[0, 1:], (ref[0][1:], ref[1][1:], ref[2]))
+    _held("select, horizon 1", S[0, :1], D[0, :1], (ref[0][:1], ref[1][:1], ref[2]))
+
+
+# 10 --------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", sorted(K.BATCHES))
+def test_batches_at_the_new_shapes_are_the_same_bits_alone_in_any_order_and_again(name):
+    import itertools
+    cases, extras = K.BATCHES[name]
+    models = [K.sweep_model(i) for i in cases] + [K.extra_model(j) for j in extras]
+    trajs = list(K.sweep_data(cases[0]))
+    assert len(models) == 3 and len({MM.device_shape_key(m) for m in models}) == 3
+    S1, D1 = MM.kstep_sums_mlp(models, trajs, K.SWEEP_KMAX, delta=True)
+    S2, D2 = MM.kstep_sums_mlp(models, trajs, K.SWEEP_KMAX, delta=True)
+    assert np.array_equal(S1, S2) and np.array_equal(D1, D2)                # run to run
+    assert np.all(np.isfinite(S1)) and np.all(np.isfinite(D1)) and np.all(S1 > 0) and np.all(D1 > 0)
+    assert len({S1[i, 3] for i in range(3)}) == 3
+    for perm in itertools.permutations(range(3)):
+        Sp, Dp = MM.kstep_sums_mlp([models[i] for i in perm], trajs, K.SWEEP_KMAX, delta=True)
+        for pos, i in enumerate(perm):
+            assert np.array_equal(Sp[pos], S1[i]) and np.array_equal(Dp[pos], D1[i]), perm     # any order
+    for i, m in enumerate(models):
+        S, D = MM.kstep_sums_mlp([m], trajs, K.SWEEP_KMAX, delta=True)
+        assert np.array_equal(S[0], S1[i]) and np.array_equal(D[0], D1[i]), i                # one call of n = n calls
+    # and the batch's first model and the extra ones are what the reference says, on this data
+    _held("batch %s, model 0" % name, S1[0], D1[0], K.sweep_reference(cases[0]))
+    for pos, j in enumerate(extras):
+        _held("batch %s, extra model %d" % (name, j), S1[len(cases) + pos], D1[len(cases) + pos], K.extra_reference(j))

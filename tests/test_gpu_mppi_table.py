@@ -9,58 +9,15 @@ import numpy as np
 import pytest
 import torch  # noqa: F401  (before the library, as in test_gpu_kstep_mlp.py: the device fit runs on torch's GPU)
 
+import mppi_table_cases as C
 from conftest import golden
 from helpers import check_weights, golden_params, make_system, rel_err
 from oracle import mlp as omlp
-from oracle.costs import QuadCostOracle
-from oracle.mlp import MLPOracle
-from oracle.mppi import MPPIOracle
 
 pytestmark = pytest.mark.gpu
 
-# (hidden widths, activation, num_path, horizon)
-EDGES = [([16], "relu", 16, 2), ([17, 33], "tanh", 17, 5), ([256, 256], "relu", 40, 30), ([1, 40], "sigmoid", 5, 7),
-         ([64, 16, 48, 128], "selu", 33, 16), ([255], "sigmoid", 64, 29)]
-T = 4
-
-
-def _hip_model(system, p, precision="f64"):
-    from autompc_amd import MLP
-    m = MLP(system, n_hidden_layers=len(p["weights"]) - 1, nonlintype=p["activation"], precision=precision,
-            **{"hidden_size_%d" % (i + 1): w.shape[0] for i, w in enumerate(p["weights"][:-1])})
-    m.weights, m.biases = [w.copy() for w in p["weights"]], [b.copy() for b in p["biases"]]
-    m.xu_means, m.xu_std, m.dy_means, m.dy_std = p["xu_means"], p["xu_std"], p["dy_means"], p["dy_std"]
-    m.jit_kernels = False              # (as the models a tuner fits for one evaluation: no run-time kernel builds)
-    return m
-
-
-def _task(system, cost=None):
-    from autompc_amd import QuadCost, Task
-    nx, nu = system.obs_dim, system.ctrl_dim
-    task = Task(system)
-    task.set_cost(cost if cost is not None else QuadCost(system, np.eye(nx), 0.01 * np.eye(nu), 2.0 * np.eye(nx)))
-    task.set_ctrl_bounds(-np.ones(nu), np.ones(nu))
-    return task
-
-
-def _stack(nx, nu, edges, seed):
-    from autompc_amd.tuning import random_candidates
-    system = make_system(nx, nu)
-    params = [omlp.random_params(nx, nu, h, a, seed=seed + i) for i, (h, a, _, _) in enumerate(edges)]
-    p_sur = omlp.random_params(nx, nu, [128, 64], "tanh", seed=seed + 90)
-    cands = random_candidates(system, len(edges), seed=3)
-    for c, p, (_, _, n, hz) in zip(cands, params, edges):
-        c["num_path"], c["horizon"] = n, hz
-        c["Q"], c["R"], c["F"] = c["Q"] ** 0.1, c["R"] ** 0.1, c["F"] ** 0.1           # costs stay O(1)
-        c["model"] = _hip_model(system, p)
-    init = np.random.default_rng(0).uniform(-0.1, 0.1, size=nx)
-    return dict(system=system, params=params, p_sur=p_sur, cands=cands, init=init, task=_task(system),
-                own=_hip_model(system, params[0]), sur=_hip_model(system, p_sur))
-
-
-@functools.lru_cache(maxsize=None)
-def _six():
-    return _stack(17, 6, EDGES, seed=40)
+_hip_model, _task, _stack, _six, _fed_noise = C.hip_model, C.make_task, C.stack, C.six, C.fed_noise
+EDGES, T = C.EDGES, C.T
 
 
 def _evaluator(S, mode="table", **kw):
@@ -68,44 +25,19 @@ def _evaluator(S, mode="table", **kw):
     return CandidateEvaluator(S["system"], kw.pop("task", S["task"]), S["own"], surrogate=S["sur"], mlp_models=mode, **kw)
 
 
-def _fed_noise(cands, nu, steps, seed=9):
-    rng = np.random.default_rng(seed)
-    acts = [rng.normal(scale=np.sqrt(c["sigma"]), size=(c["horizon"], nu)) for c in cands]
-    eps = [[rng.normal(scale=np.sqrt(c["sigma"]), size=(c["num_path"], c["horizon"], nu)) for c in cands]
-           for _ in range(steps)]
-    return acts, eps
-
-
 def _against_the_oracle(S, ev, steps, what):
     """Every candidate's obs, ctrls and score against its own MPPIOracle + MLPOracle closed loop, fed the same noise
     (written as test_candidate_batch_matches_oracle_per_candidate writes it); returns the largest deviations."""
-    system, cands, init = S["system"], S["cands"], S["init"]
-    nx, nu = system.obs_dim, system.ctrl_dim
-    acts, eps = _fed_noise(cands, nu, steps)
+    cands, init = S["cands"], S["init"]
+    acts, eps = _fed_noise(cands, S["system"].ctrl_dim, steps)
     eps_all = np.concatenate([np.concatenate([e.ravel() for e in step]) for step in eps])
     scores, obs, ctrls = ev.evaluate(cands, n_steps=steps, init_obs=init, eps_all=eps_all,
                                      act_init=np.concatenate([a.ravel() for a in acts]), return_trajectories=True)
     assert ev.last_models == {"path": "table", "models": len(cands), "plans": 1}
-    sur = MLPOracle(system, S["p_sur"])
-    task_cost = QuadCostOracle(np.eye(nx), 0.01 * np.eye(nu), 2.0 * np.eye(nx), np.zeros(nx))
     worst = np.zeros(3)
     for b, c in enumerate(cands):
-        np.random.seed(0)
-        orc = MPPIOracle(MLPOracle(system, S["params"][b]),
-                         QuadCostOracle(np.diag(c["Q"]), np.diag(c["R"]), np.diag(c["F"]), np.zeros(nx)),
-                         np.tile([-1.0, 1.0], (nu, 1)), horizon=c["horizon"], num_path=c["num_path"],
-                         sigma=c["sigma"], lmda=c["lmda"])
-        orc.act_sequence = acts[b].copy()
-        x, cs = init.copy(), np.concatenate([init, np.zeros(nu)])
-        o_obs, o_ctl = [x.copy()], []
-        for s in range(steps):
-            u, cs = orc.run(cs, x, eps_nhu=eps[s][b])
-            x = sur.pred(x, u)
-            o_ctl.append(u)
-            o_obs.append(x.copy())
-        o_ctl.append(np.zeros(nu))
-        ref = task_cost.traj_cost(np.array(o_obs), np.array(o_ctl))
-        dev = np.array([rel_err(obs[b], np.array(o_obs)), rel_err(ctrls[b], np.array(o_ctl)),
+        o_obs, o_ctl, ref = C.oracle_loop(S, b, steps, acts, eps)
+        dev = np.array([rel_err(obs[b], o_obs), rel_err(ctrls[b], o_ctl),
                         abs(scores[b] - ref) / abs(ref)])
         print("%s, candidate %d: obs %.2e ctrls %.2e score %.2e" % (what, b, *dev))
         worst = np.maximum(worst, dev)
@@ -120,6 +52,17 @@ def test_six_edge_shapes_in_one_plan_match_the_oracle_per_candidate():
     oracle (a permutation of the hidden units) moves trajectories and scores by at most 7e-15 over the four steps."""
     S = _six()
     _against_the_oracle(S, _evaluator(S), T, "six edge shapes")
+
+
+@pytest.mark.parametrize("which", ["sixteen", "forty_eight"])
+def test_two_more_systems_in_one_plan_match_the_oracle_per_candidate(which):
+    """16 / 16 (in = 32, one output tile) and 48 / 16 (in = 64, three output tiles): four models each, widths 15, 65,
+    129, 193 and a depth-3 net, 5 / 16 / 17 / 33 samples, horizons 2 to 7.  1e-9 as above: on these candidates a
+    permutation of the oracle's hidden units moves trajectories and scores by less than 1e-12
+    (test_mppi_table_host.py)."""
+    S = getattr(C, which)()
+    assert {c["num_path"] for c in S["cands"]} == {5, 16, 17, 33} and len(S["cands"]) == 4
+    _against_the_oracle(S, _evaluator(S), T, "%d states / %d controls" % (S["system"].obs_dim, S["system"].ctrl_dim))
 
 
 # 2 ---------------------------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 """The host side of the mixed-shape MLP k-step path (ampc_kstep_errors_mlp, evaluation/model_metrics.py): the ABI, the
 grouping key ``mlp_batch_key``, the ``mlp_kstep`` option, the pointer table ``mlp_batch_args`` builds for host-resident
-parameters, and the default path left as it is.  No GPU."""
+parameters, the default path left as it is, and the extended-precision reference the GPU tests compare with (kstep_mlp_cases.py):
+its agreement with the reference project's goldens and the conditioning of every case it is used on.  No GPU."""
 import ctypes
 import os
 
@@ -10,6 +11,7 @@ import pytest
 from autompc_amd import MLP
 from autompc_amd.evaluation import model_metrics as MM
 from helpers import golden_params, make_system
+import kstep_mlp_cases as K
 from kstep_mlp_cases import TAGS, fixture_model, mlp_of
 from oracle.mlp import MLPOracle
 
@@ -169,3 +171,58 @@ def test_mlp_kstep_option_is_checked_and_the_default_is_untouched(monkeypatch):
     assert np.array_equal(c[1], a[0]) and r2.host_fallbacks == 1
     assert got == [[real, real]] and r2.mlp_batch_models == 2 and r2.mlp_batch_calls == 1
     assert seen[-1] == [wide] and r2.device_models == 1                  # over the limits: the per-shape path
+
+
+# ---- the reference of test_gpu_kstep_mlp.py's sweep ---------------------------------------------------------------
+@pytest.mark.parametrize("tag", TAGS)
+def test_long_double_reference_reproduces_the_fixture_goldens(tag):
+    """RMSE and RMSMENS from kstep_sums_ref's long-double sums against the goldens the reference project computed:
+    measured at most 1.8e-16 relative on the seven fixtures (x86 80-bit long double), held to 1e-14."""
+    m, trajs, g = fixture_model(tag)
+    hs = [int(h) for h in g["horizons"]]
+    p = dict(weights=m.weights, biases=m.biases, xu_means=m.xu_means, xu_std=m.xu_std, dy_means=m.dy_means,
+             dy_std=m.dy_std)
+    S, D = K.kstep_sums_ref(p, str(g["activation"]), trajs, max(hs), np.longdouble, horizons=hs)
+    N = MM.row_counts(trajs, max(hs)).astype(np.longdouble)
+    sel = [h - 1 for h in hs]
+    rmse, rmsmens = np.sqrt(S / N)[sel], np.sqrt(D / (N * int(g["nx"])))[sel]
+    print("kstep_sums_ref %s: rmse %.2e rmsmens %.2e from the goldens" % (tag, K.deviation(g["rmse"], rmse),
+                                                                          K.deviation(g["rmsmens"], rmsmens)))
+    assert K.deviation(g["rmse"], rmse) <= 1e-14 and K.deviation(g["rmsmens"], rmsmens) <= 1e-14
+
+
+def _well_conditioned(what, ref):
+    S, D, cond = ref
+    print("kstep mlp %s: f64 vs long double %.2e, S %.3g .. %.3g, D %.3g .. %.3g"
+          % (what, cond, float(S.min()), float(S.max()), float(D.min()), float(D.max())))
+    assert cond <= 1e-14, what
+    assert np.all(np.isfinite(S)) and np.all(np.isfinite(D)) and np.all(S > 0) and np.all(D > 0), what
+
+
+def test_every_sweep_case_is_well_conditioned():
+    """The f64 run of the reference deviates from its long-double run by at most 3.0e-16 on the sweep: no case
+    diverges, so 100 x that figure (floor 1e-13) is a bound a correct kernel meets and a wrong low-order term does
+    not."""
+    for i, case in enumerate(K.SWEEP):
+        _well_conditioned("sweep %d %r" % (i, case), K.sweep_reference(i))
+        if case[3] == "relu":          # no relu layer is dead or linear on its data: the sums depend on its weights
+            on = K.first_layer_active(i)
+            assert np.any((on > 0.1) & (on < 0.9)), (i, on)
+    for j, case in enumerate(K.EXTRA):
+        _well_conditioned("extra %d %r" % (j, case), K.extra_reference(j))
+    for i in K.EDGE_MODELS:
+        for lens, kmax in K.EDGE_DATA:
+            _well_conditioned("sweep %d on lengths %r, kmax %d" % (i, lens, kmax), K.sweep_reference(i, lens, kmax))
+
+
+def test_the_select_case_overflows_only_past_its_horizon():
+    p, act, trajs, scale = K.select_case()
+    assert [len(t) for t in trajs] == [18, 2, 9]
+    cont = K.clamped_continuation(p, act, trajs[1], K.SWEEP_KMAX)
+    print("select case: scale %g, the two-row trajectory's squared errors with clamped indices %s" % (scale, cont))
+    assert np.isfinite(cont[0]) and 0 < cont[0] < 1e300                     # its one counted step
+    assert not np.all(np.isfinite(cont[1:]))                                # the uncounted continuation leaves f64
+    S, D, cond = K.reference(p, act, list(trajs), K.SWEEP_KMAX)
+    print("select case: f64 vs long double %.2e, S %s" % (cond, np.asarray(S, dtype=np.float64)))
+    assert cond <= 1e-14 and np.all(np.isfinite(S)) and np.all(np.isfinite(D)) and np.all(S > 0) and np.all(D > 0)
+    assert float(S[0]) > 1e298 and float(S[1:].max()) < 1e30                # which the reference never forms

@@ -1,6 +1,7 @@
 """The host side of MPPI plans that hold MLP models of mixed shapes (ampc_mppi_plan_set_model_table,
 tuning/batch_eval.py: ``mlp_models="table"``): the ABI, the refusal that needs no device, the option and the pure-Python
-decision whether ONE plan takes a batch.  No GPU."""
+decision whether ONE plan takes a batch, and the conditioning of the candidates test_gpu_mppi_table.py holds to 1e-9
+against the oracle.  No GPU."""
 import ctypes
 import os
 
@@ -153,3 +154,26 @@ class _Sub:
 
     def evaluate(self, cands, **kw):
         return self._fn(self._ev, cands, **kw)
+
+
+@pytest.mark.parametrize("which", ["sixteen", "forty_eight"])
+def test_new_table_candidates_are_well_conditioned(which):
+    """What a rounding-level restatement of the oracle -- every hidden layer's units in another order, so every sum in
+    another order -- does to the closed loops test_gpu_mppi_table.py compares with at 1e-9: below 1e-12 on every
+    candidate of the two further systems, so the 1e-9 holds three orders of allowance and no candidate sits on a
+    switch of the softmin or of a clipped control."""
+    import mppi_table_cases as C
+    from helpers import rel_err
+    from ilqr_table_cases import permuted
+    S = getattr(C, which)()
+    nu = S["system"].ctrl_dim
+    acts, eps = C.fed_noise(S["cands"], nu, C.T)
+    worst = 0.0
+    for b in range(len(S["cands"])):
+        obs, ctl, score = C.oracle_loop(S, b, C.T, acts, eps)
+        obs_p, ctl_p, score_p = C.oracle_loop(S, b, C.T, acts, eps, p=permuted(S["params"][b]))
+        dev = max(rel_err(obs_p, obs), rel_err(ctl_p, ctl), abs(score_p - score) / abs(score))
+        print("%s, candidate %d: a permutation of the hidden units moves the oracle's loop by %.2e" % (which, b, dev))
+        assert np.all(np.isfinite(obs)) and np.any(np.abs(ctl[:-1]) < 1.0) and np.any(ctl[:-1] != 0.0)
+        worst = max(worst, dev)
+    assert worst < 1e-12
