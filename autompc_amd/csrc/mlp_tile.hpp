@@ -507,13 +507,21 @@ struct NoGroups {};     // layer_mma_static: no pinned fragment addresses, form 
 // APERM: A is an activation buffer (rows stored at act_row<T>()); false for the [x | u] operand.
 // `group_at(g)`, when given, is this lane's (pinned) address of the fragments of the g-th group in the
 // order the layer consumes them -- the rotation already applied; A and rot are then not used.
+// SWAP: the layer is computed TRANSPOSED, acc[nt] += Wpacked' * A' (the weight fragment is the MFMA's first
+// operand, the activation fragment its second: the two fragment layouts mirror each other, so registers and
+// addresses are the same) -- accumulator register r of tile nt then holds [unit 16 nt + 4 r + q][sample i],
+// which IS the activation fragment of k-step 4 nt + r of whatever consumes these units next (TileNet::CHAIN).
+// `own_at(kk)`, when given (OWN, MT = 1), is that fragment for k-step kk of the FIRST group, in a register: the
+// group the wave produced itself is not fetched from LDS.
 template <typename T, int NT, int MT, int KS, int G, bool PIPE = false, bool OWN = false, int SG = G,
-          bool APERM = false, typename Mid = NoSide, typename Groups = NoGroups>
+          bool APERM = false, bool SWAP = false, typename Mid = NoSide, typename Groups = NoGroups,
+          typename OwnFrag = NoGroups>
 __device__ __forceinline__ void layer_mma_static(const T* __restrict__ A, int a_stride,
                                                  rsrc_t wr, unsigned wl, int lane,
                                                  const T (&first)[G][NT],
                                                  typename Acc<T>::type (&acc)[MT][NT], int rot = 0,
-                                                 Mid&& mid = Mid(), Groups&& group_at = Groups()) {
+                                                 Mid&& mid = Mid(), Groups&& group_at = Groups(),
+                                                 OwnFrag&& own_at = OwnFrag()) {
   static_assert(KS % G == 0 && G % SG == 0, "group sizes must divide the k extent");
   constexpr int NG = KS / G;       // groups (the unit of the rotated k order)
   constexpr int NS = KS / SG;      // sub-groups (the unit of the weight stream)
@@ -521,6 +529,8 @@ __device__ __forceinline__ void layer_mma_static(const T* __restrict__ A, int a_
   static_assert(!OWN || (NG & (NG - 1)) == 0, "rotated k order needs a power-of-two group count");
   const int i = lane & 15, q = lane >> 4;
   constexpr bool PINNED = !std::is_same<typename std::decay<Groups>::type, NoGroups>::value;
+  constexpr bool REG0 = !std::is_same<typename std::decay<OwnFrag>::type, NoGroups>::value;
+  static_assert(!REG0 || (OWN && MT == 1), "register fragments: the wave's own group of a 16-row tile");
   const T* arow = A + (APERM ? act_row<T>(i) : i) * a_stride + q;        // (not used when PINNED)
   auto sub_group = [&](int g, int sub) {
     if constexpr (PINNED) return group_at(g) + 4 * SG * sub;
@@ -542,13 +552,17 @@ __device__ __forceinline__ void layer_mma_static(const T* __restrict__ A, int a_
     for (int kk = 0; kk < SG; ++kk) {
       T a[MT];
 #pragma unroll
-      for (int mt = 0; mt < MT; ++mt) a[mt] = ag[mt * 16 * a_stride + 4 * kk];
+      for (int mt = 0; mt < MT; ++mt) {
+        if constexpr (REG0) a[mt] = sgi < FS ? own_at(sgi * SG + kk) : ag[4 * kk];
+        else a[mt] = ag[mt * 16 * a_stride + 4 * kk];
+      }
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
           const T bv = (FS > 1 && sgi < FS) ? first[sgi * SG + kk][nt] : b[sgi & 1][kk][nt];
-          acc[mt][nt] = mfma16_x<(KS < 16 ? kRealL0 : kRealHid)>(a[mt], bv, acc[mt][nt]);
+          constexpr bool REAL = KS < 16 ? kRealL0 : kRealHid;
+          acc[mt][nt] = SWAP ? mfma16_x<REAL>(bv, a[mt], acc[mt][nt]) : mfma16_x<REAL>(a[mt], bv, acc[mt][nt]);
         }
     }
     // (8-wave tiles only; measured neutral-to-negative with one wave per SIMD)
@@ -607,6 +621,12 @@ __device__ __forceinline__ void layer_mma_static(const T* __restrict__ A, int a_
             __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
           }
         }
+      } else if (REG0 && sgi < FS) {     // operands in registers: no fragment reads to place
+#pragma unroll
+        for (int i = 0; i < SG / 2; ++i) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 2 * MT * NT, 0);
+          __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
+        }
       } else {
         __builtin_amdgcn_sched_group_barrier(0x100, 2 * MT, 0);
 #pragma unroll
@@ -664,6 +684,25 @@ struct TileNet {
   // layer: that layer starts on them before the barrier (see run()).  Host packing must agree
   // (own_first_packing() in api.cpp).
   static constexpr bool OWN = (16 * NT == 4 * GH) && (((KSH / GH) & (KSH / GH - 1)) == 0);
+  // Pinned LDS addresses (see ep_ .. below for what and why): f64, shape-specialised, run() in a loop.
+  static constexpr bool PIN = PINNED && SH::kStatic && sizeof(T) == 8;
+  // CHAIN (the pinned 16-row f64 tile): layer 0 and the hidden layers are computed TRANSPOSED (layer_mma_static,
+  // SWAP).  With D[row q + 4 r][col i] of v_mfma_f64_16x16x4_f64, register r of a wave's column tile nt holds
+  // [unit 16 NT w + 16 nt + 4 r + q][sample i] -- bit for bit the fragment act[row i][k = 4 ks + q] of k-step
+  // ks = 4 nt + r that the MFMAs consuming this wave's units take, as either operand.  The relu'd values
+  // therefore stay in registers (`own`): they feed the first (own) group of the next hidden layer, and ALL of
+  // this wave's k-slice of the output layer, which stays un-transposed (the fragment is its A operand as it was
+  // when it came from LDS, so the partials keep their conflict-free [row q + 4 r][col i] stores; transposed,
+  // the 16 lanes of a store group would hit one bank, rows being 32 doubles apart).  A hidden layer's values
+  // go to LDS only for the OTHER waves, i.e. never from the last hidden layer.  Every output element is the
+  // same k-ordered chain of the same products as before: results are bit-identical (the f32 MFMA's rows are
+  // 4 q + r, which is no fragment without re-packing K on the host; taller tiles have no registers for it).
+  static constexpr bool CHAIN = PIN && MT == 1 && !DERIV && !WIDE && LEAN == 0;
+  // Resident bias values per column tile: the unit of every accumulator register (CHAIN) / one column.  The
+  // four-wave tiles (narrow networks, up to four workgroups per CU) stay inside the 128 registers that takes
+  // only without them: they read the bias from its LDS copy (bq_), off the serial chain.
+  static constexpr int BR = (CHAIN && W == 8) ? 4 : 1;
+  static constexpr bool CHAIN_BIAS_LDS = CHAIN && BR == 1;
 
   // Layer 0's fragments are RESIDENT in registers for the kernel's lifetime whenever the layer is
   // at most KS0RES k-steps (all widths in f32; k1p <= 24, i.e. nx + nu <= 24, in f64 -- HalfCheetah
@@ -734,7 +773,8 @@ struct TileNet {
   // (the first kResBias hidden layers -- the reference's default network has two; deeper layers'
   // accumulators are seeded from the LDS copy of the bias instead, one read per column tile)
   static constexpr int kResBias = 2;
-  T bias_r[kResBias][NT];
+  // (CHAIN: the bias of the unit each accumulator register holds, [nt][r] -> unit 16 nt + 4 r + q)
+  T bias_r[kResBias][NT][BR];
   // Prefetch buffer: the first group of the next hidden layer (and, when they are not resident,
   // the output-layer fragments).  A member, not a local of run(): the first group of hidden layer 1
   // for the NEXT call is requested at the end of a call, together with layer 0's fragments, so it
@@ -749,8 +789,12 @@ struct TileNet {
   // Every other instantiation forms the addresses where it uses them.  f64 only: the f32 rollout (half the
   // MFMA time per k-step, 116 of the 128 VGPRs that two workgroups per CU allow) measured 1.6 % SLOWER per
   // single c3 solve with its addresses pinned (126 VGPRs) and 1 % faster at eight solves per launch; it
-  // stays as it was.
-  static constexpr bool PIN = PINNED && SH::kStatic && sizeof(T) == 8;
+  // stays as it was.  (PIN itself: defined above, with CHAIN.)
+  // CHAIN: ep_[b][0] is the lane's address act[row i][unit 16 NT w + q] (register r of tile nt at + 16 nt + 4 r: 16
+  // rows x one column per store group, the bank pattern of the fragment reads); rd_[b][0] of an OWN layer and ro_
+  // are not read; bq_ is the LDS copy of the bias of unit 16 NT w + q (hidden layers past the resident ones; every
+  // layer of a four-wave tile).
+  lds_ptr<const T> bq_;
   static constexpr int RS = sizeof(T) == 8 ? 4 : 1;   // acc_row(q, r) = acc_row(q, 0) + RS*r
   static constexpr int NGH = KSH / GH;                // k-groups of a hidden -> hidden layer
   lds_ptr<T> ep_[2][4];            // epilogue stores into activation buffer b: accumulator register r of tile (0, 0)
@@ -773,20 +817,29 @@ struct TileNet {
 #pragma unroll
       for (int b = 0; b < 2; ++b) {
         T* buf = lds + (b ? L.act2 : L.act);
-        const bool written = b == 0 || pingpong;
         const bool read = b == 0 ? m.n_hidden > 1 : (pingpong && m.n_hidden > 2);   // by a hidden layer
+        // (CHAIN: only a layer that a hidden layer reads stores at all)
+        const bool written = CHAIN ? read : (b == 0 || pingpong);
 #pragma unroll
-        for (int r = 0; r < 4; ++r)
-          ep_[b][r] = written ? lds_pin(buf + (act_row<T>(acc_row<T>(q, 0)) + RS * r) * as + 16 * NT * w + i) : ep_[0][r];
+        for (int r = 0; r < 4; ++r) {
+          if constexpr (CHAIN)
+            ep_[b][r] = (written && r == 0) ? lds_pin(buf + i * as + 16 * NT * w + q) : lds_ptr<T>(nullptr);
+          else
+            ep_[b][r] = written ? lds_pin(buf + (act_row<T>(acc_row<T>(q, 0)) + RS * r) * as + 16 * NT * w + i) : ep_[0][r];
+        }
 #pragma unroll
         for (int g = 0; g < NGH; ++g) {
           const T* grp = buf + act_row<T>(i) * as + q + 4 * GH * (OWN ? ((g + w) & (NGH - 1)) : g);
-          // (without the rotation the groups are constant offsets from the first)
-          rd_[b][g] = (read && (OWN || g == 0)) ? lds_pin(grp) : lds_ptr<const T>(nullptr);
+          // (without the rotation the groups are constant offsets from the first; CHAIN: an OWN layer takes
+          //  its first group from registers)
+          const bool used = OWN ? (g > 0 || !CHAIN) : g == 0;
+          rd_[b][g] = (read && used) ? lds_pin(grp) : lds_ptr<const T>(nullptr);
         }
       }
       const T* last = lds + ((pingpong && ((m.n_hidden - 1) & 1)) ? L.act2 : L.act);
-      ro_ = lds_pin(last + act_row<T>(i) * as + q + 4 * w * KSW);
+      ro_ = CHAIN ? lds_ptr<const T>(nullptr) : lds_pin(last + act_row<T>(i) * as + q + 4 * w * KSW);
+      bq_ = (CHAIN && (CHAIN_BIAS_LDS || m.n_hidden > kResBias)) ? lds_pin(static_cast<const T*>(lds + L.bias + 16 * NT * w + q))
+                                             : lds_ptr<const T>(nullptr);
       x0_ = lds_pin(static_cast<const T*>(lds + L.xu + i * L.xu_stride + q));
       const int ps = part_stride((int)sizeof(T), m.nxp);
       T* part = lds + L.part + w * M * ps;
@@ -804,7 +857,11 @@ struct TileNet {
     for (int l = 0; l < kResBias; ++l)
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt)
-        bias_r[l][nt] = (RESIDENT_BIAS && l < m.n_hidden) ? m.B(l)[16 * (NT * w + nt) + (lane & 15)] : T(0);
+#pragma unroll
+        for (int r = 0; r < BR; ++r) {
+          const int col = CHAIN ? 4 * r + (lane >> 4) : (lane & 15);
+          bias_r[l][nt][r] = (RESIDENT_BIAS && !CHAIN_BIAS_LDS && l < m.n_hidden) ? m.B(l)[16 * (NT * w + nt) + col] : T(0);
+        }
     wr = weight_rsrc(m.WB());
     if constexpr (RESIDENT_OUT) load_out(m, w, lane, wout);
     load0_all(m);
@@ -850,7 +907,9 @@ struct TileNet {
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = mfma16_x<kRealL0>(a[mt], pf0[ks][nt], acc[mt][nt]);
+        for (int nt = 0; nt < NT; ++nt)
+          acc[mt][nt] = CHAIN ? mfma16_x<kRealL0>(pf0[ks][nt], a[mt], acc[mt][nt])
+                              : mfma16_x<kRealL0>(a[mt], pf0[ks][nt], acc[mt][nt]);
     }
   }
 
@@ -952,7 +1011,7 @@ struct TileNet {
       T* d0 = dst + act_row<T>(acc_row<T>(q, 0)) * as + 16 * NT * w + i;   // (+ ro: bits 0-1 and >= 4 only)
       T* z0 = DERIV ? dz + (size_t)l * dz_layer_stride + (size_t)acc_row<T>(q, 0) * m.hpad + 16 * NT * w + i : nullptr;
       auto bias_of = [&](int nt) -> T {
-        if (RESIDENT_BIAS && l < kResBias) return (l == 0) ? bias_r[0][nt] : bias_r[kResBias - 1][nt];
+        if (RESIDENT_BIAS && l < kResBias) return (l == 0) ? bias_r[0][nt][0] : bias_r[kResBias - 1][nt][0];
         return bias[16 * nt];
       };
       auto emit = [&](int mt, int nt, int r, T bc) {
@@ -994,6 +1053,33 @@ struct TileNet {
         default: epilogue_k(l, acc, dst, db, std::integral_constant<int, 3>{}); break;
       }
     };
+    // CHAIN: the transposed accumulators.  Bias (of the unit a register holds) after the accumulation and the
+    // activation as above, the same arithmetic per element; the values stay in `own` as this wave's fragments
+    // and go to LDS (activation buffer db) only where another wave reads them (`store`).
+    T own[NT][4];
+    auto chain_k = [&](int l, acc_t (&acc)[MT][NT], int db, bool store, auto kind_tag) {
+      constexpr int KIND = decltype(kind_tag)::value;
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          T bc;
+          if (!CHAIN_BIAS_LDS && l < kResBias) bc = (l == 0) ? bias_r[0][nt][r % BR] : bias_r[kResBias - 1][nt][r % BR];
+          else bc = bq_[l * HP + 16 * nt + 4 * r];
+          const T v = act_apply<T>(KIND, acc[0][nt][r] + bc);
+          own[nt][r] = v;
+          if (store) (db ? ep_[1][0] : ep_[0][0])[16 * nt + 4 * r] = v;
+        }
+    };
+    auto epilogue_chain = [&](int l, acc_t (&acc)[MT][NT], int db, bool store) {
+      switch (m.act) {
+        case 0: chain_k(l, acc, db, store, std::integral_constant<int, 0>{}); break;
+        case 1: chain_k(l, acc, db, store, std::integral_constant<int, 1>{}); break;
+        case 2: chain_k(l, acc, db, store, std::integral_constant<int, 2>{}); break;
+        case 4: chain_k(l, acc, db, store, std::integral_constant<int, 4>{}); break;
+        default: chain_k(l, acc, db, store, std::integral_constant<int, 3>{}); break;
+      }
+    };
 
     bool side_done = false;
     // ---- layer 0: K = k1p (8, 16, .. 48), A = [x | u] ----------------------------------------
@@ -1030,29 +1116,35 @@ struct TileNet {
             break;
         }
       } else {
+        // (streamed in groups of two k-steps; CHAIN: transposed like the resident form)
+        auto layer0_streamed = [&](auto ks) {
+          layer_mma_static<T, NT, MT, decltype(ks)::value, 2, false, false, 2, false, CHAIN>(
+              A, L.xu_stride, wr, wl, lane, first0<2>(), acc);
+        };
         switch (m.k1p) {
-          case 8: layer_mma_static<T, NT, MT, 2, 2>(A, L.xu_stride, wr, wl, lane, first0<2>(), acc); break;
-          case 16: layer_mma_static<T, NT, MT, 4, 2>(A, L.xu_stride, wr, wl, lane, first0<2>(), acc); break;
-          case 24: layer_mma_static<T, NT, MT, 6, 2>(A, L.xu_stride, wr, wl, lane, first0<2>(), acc); break;
-          case 32: layer_mma_static<T, NT, MT, 8, 2>(A, L.xu_stride, wr, wl, lane, first0<2>(), acc); break;
-          case 40: layer_mma_static<T, NT, MT, 10, 2>(A, L.xu_stride, wr, wl, lane, first0<2>(), acc); break;
-          case 48: layer_mma_static<T, NT, MT, 12, 2>(A, L.xu_stride, wr, wl, lane, first0<2>(), acc); break;
+          case 8: layer0_streamed(std::integral_constant<int, 2>{}); break;
+          case 16: layer0_streamed(std::integral_constant<int, 4>{}); break;
+          case 24: layer0_streamed(std::integral_constant<int, 6>{}); break;
+          case 32: layer0_streamed(std::integral_constant<int, 8>{}); break;
+          case 40: layer0_streamed(std::integral_constant<int, 10>{}); break;
+          case 48: layer0_streamed(std::integral_constant<int, 12>{}); break;
           default:
             if constexpr (WIDE) {
               switch (m.k1p) {
-                case 56: layer_mma_static<T, NT, MT, 14, 2>(A, L.xu_stride, wr, wl, lane, first0<2>(), acc); break;
-                case 64: layer_mma_static<T, NT, MT, 16, 2>(A, L.xu_stride, wr, wl, lane, first0<2>(), acc); break;
-                case 72: layer_mma_static<T, NT, MT, 18, 2>(A, L.xu_stride, wr, wl, lane, first0<2>(), acc); break;
-                default: layer_mma_static<T, NT, MT, 20, 2>(A, L.xu_stride, wr, wl, lane, first0<2>(), acc); break;
+                case 56: layer0_streamed(std::integral_constant<int, 14>{}); break;
+                case 64: layer0_streamed(std::integral_constant<int, 16>{}); break;
+                case 72: layer0_streamed(std::integral_constant<int, 18>{}); break;
+                default: layer0_streamed(std::integral_constant<int, 20>{}); break;
               }
             } else {
-              layer_mma_static<T, NT, MT, 12, 2>(A, L.xu_stride, wr, wl, lane, first0<2>(), acc);
+              layer0_streamed(std::integral_constant<int, 12>{});
             }
             break;
         }
       }
       AMPC_MARK(2);
-      epilogue(0, acc, act, 0);
+      if constexpr (CHAIN) epilogue_chain(0, acc, 0, m.n_hidden > 1);
+      else epilogue(0, acc, act, 0);
     }
     // Barrier placement.  A layer's epilogue leaves wave w's columns in LDS.  The output layer is
     // K-split so that wave w consumes exactly those columns: no barrier before it.  A hidden
@@ -1077,22 +1169,30 @@ struct TileNet {
       auto mid = [&] {
         if (!Probe::side_late && l == 1) { side(); side_done = true; }
       };
-      if constexpr (PIN)
-        layer_mma_static<T, NT, MT, KSH, GH, (W == 8), OWN, SGH, true>(
-            act, as, wr, slice_h(m, l, w), lane, pfn, acc, w, mid, [&](int g) {
-              if constexpr (OWN) return cur ? rd_[1][g] : rd_[0][g];
-              else return (cur ? rd_[1][0] : rd_[0][0]) + 4 * GH * g;
-            });
+      auto pinned_group = [&](int g) {
+        if constexpr (OWN) return cur ? rd_[1][g] : rd_[0][g];
+        else return (cur ? rd_[1][0] : rd_[0][0]) + 4 * GH * g;
+      };
+      if constexpr (CHAIN && OWN)   // first group: the previous epilogue's registers (k-step kk = 4 nt + r)
+        layer_mma_static<T, NT, MT, KSH, GH, (W == 8), OWN, SGH, true, true>(
+            act, as, wr, slice_h(m, l, w), lane, pfn, acc, w, mid, pinned_group,
+            [&](int kk) { return own[kk >> 2][kk & 3]; });
+      else if constexpr (PIN)
+        layer_mma_static<T, NT, MT, KSH, GH, (W == 8), OWN, SGH, true, CHAIN>(
+            act, as, wr, slice_h(m, l, w), lane, pfn, acc, w, mid, pinned_group);
       else
         layer_mma_static<T, NT, MT, KSH, GH, (W == 8), OWN, SGH, true>(
             act, as, wr, slice_h(m, l, w), lane, pfn, acc, w, mid);
       AMPC_MARK(4);
       prefetch_next(l + 1);
+      // CHAIN: only a layer that another hidden layer reads stores its activations
+      const bool stores = !CHAIN || l + 1 < m.n_hidden;
       // single buffer: every wave must finish reading act before it is overwritten;
       // ping-pong: the epilogue writes the other buffer, no barrier needed here
-      if (!pingpong) lds_barrier();
+      if (!pingpong && stores) lds_barrier();
       AMPC_MARK(5);
-      epilogue(l, acc, act_other, pingpong ? cur ^ 1 : 0);
+      if constexpr (CHAIN) epilogue_chain(l, acc, pingpong ? cur ^ 1 : 0, stores);
+      else epilogue(l, acc, act_other, pingpong ? cur ^ 1 : 0);
       if (!OWN && l + 1 < m.n_hidden) lds_barrier();
       AMPC_MARK(6);
       { T* tmp = act; act = act_other; act_other = tmp; }
@@ -1113,12 +1213,17 @@ struct TileNet {
         if constexpr (PIN) return ro_;
         else return static_cast<const T*>(act) + act_row<T>(i) * as + q + 4 * w * KSW;
       }();
+      // this wave's k-slice of the last hidden layer's activations: from LDS, or (CHAIN) the epilogue's registers
+      auto afrag = [&](int mt, int ks) -> T {
+        if constexpr (CHAIN) return own[ks >> 2][ks & 3];
+        else return arow[mt * 16 * as + 4 * ks];
+      };
       if constexpr (WIDE) {
 #pragma unroll
         for (int ks = 0; ks < KSW; ++ks)
 #pragma unroll
           for (int mt = 0; mt < MT; ++mt) {
-            const T a = arow[mt * 16 * as + 4 * ks];
+            const T a = afrag(mt, ks);
 #pragma unroll
             for (int n = 0; n < NOMAX; ++n)
               if (n < no) oacc[mt][n] = mfma16_x<kRealOut>(a, wo(ks, n), oacc[mt][n]);
@@ -1128,13 +1233,13 @@ struct TileNet {
         for (int ks = 0; ks < KSW; ++ks)
 #pragma unroll
           for (int mt = 0; mt < MT; ++mt)
-            oacc[mt][0] = mfma16_x<kRealOut>(arow[mt * 16 * as + 4 * ks], wo(ks, 0), oacc[mt][0]);
+            oacc[mt][0] = mfma16_x<kRealOut>(afrag(mt, ks), wo(ks, 0), oacc[mt][0]);
       } else if (m.tail4) {
 #pragma unroll
         for (int ks = 0; ks < KSW; ++ks)
 #pragma unroll
           for (int mt = 0; mt < MT; ++mt) {
-            const T a = arow[mt * 16 * as + 4 * ks];
+            const T a = afrag(mt, ks);
             oacc[mt][0] = mfma16_x<kRealOut>(a, wo(ks, 0), oacc[mt][0]);
             tacc[mt] = kRealOut ? mfma4(a, wo(ks, 1), tacc[mt]) : tacc[mt] + a * wo(ks, 1);
           }
@@ -1143,7 +1248,7 @@ struct TileNet {
         for (int ks = 0; ks < KSW; ++ks)
 #pragma unroll
           for (int mt = 0; mt < MT; ++mt) {
-            const T a = arow[mt * 16 * as + 4 * ks];
+            const T a = afrag(mt, ks);
             oacc[mt][0] = mfma16_x<kRealOut>(a, wo(ks, 0), oacc[mt][0]);
             oacc[mt][1] = mfma16_x<kRealOut>(a, wo(ks, 1), oacc[mt][1]);
           }
