@@ -669,8 +669,9 @@ __device__ __forceinline__ void layer_mma_static(const T* __restrict__ A, int a_
 // Instantiated for the 64-wide tile only (W = 4, NT = 1: such models are linear, staged with a hidden
 // width equal to the state dimension); the output fragments are always resident there.
 // PINNED: the caller runs the tile in a loop and has called pin() -- see PIN below.
+// BIAS0K: the caller keeps 1.0 in the last pad column of the layer-0 operand -- see BIAS0_IN_K below.
 template <typename T, int NT, int MT, int W, bool DERIV = false, int LEAN = 0, typename SH = DynShape,
-          bool WIDE = false, bool PINNED = false>
+          bool WIDE = false, bool PINNED = false, bool BIAS0K = false>
 struct TileNet {
   using acc_t = typename Acc<T>::type;
   static constexpr int M = 16 * MT;
@@ -703,6 +704,20 @@ struct TileNet {
   // only without them: they read the bias from its LDS copy (bq_), off the serial chain.
   static constexpr int BR = (CHAIN && W == 8) ? 4 : 1;
   static constexpr bool CHAIN_BIAS_LDS = CHAIN && BR == 1;
+  // Layer 0's bias through the spare K column (the chained tile with resident layer-0 fragments, where the caller
+  // opts in and the padded K extent has a column to spare: nx + nu < k1p).  The caller keeps 1.0 in column
+  // k1p - 1 of every row of lds[L.xu]; init() puts B(0)[unit] into the matching weight row of the resident
+  // fragments (the packed model keeps its zero pad row: every other kernel sees it unchanged).  An f64 MFMA
+  // accumulates its k products as a k-ordered fma chain (tools/mfma44_probe.cpp), and column k1p - 1 is the last
+  // link of layer 0's last k-step: fma(b, 1.0, acc) = RN(acc + b), bit for bit the value of the separate
+  // v_add_f64 it replaces (earlier pad columns still contribute their exact zero products before it).  The
+  // epilogue of layer 0 then has no add and no resident bias.  Seeding the accumulators with the bias instead
+  // would round in another order.  The one representable difference: where b is exactly -0.0 and the chain
+  // before it is exactly -0, a single pad column gives fma(-0, 1, -0) = -0 where (+0 seed ..) + -0 gave +0;
+  // relu maps both to +0, the other activations see the sign of a zero.
+  // (f32: nobody has probed that MFMA's accumulation order; it keeps the add.)
+  // (CHAIN implies PIN, f64, MT == 1 and LEAN == 0; the rest of the condition is resident0() at compile time)
+  static constexpr bool BIAS0_IN_K = BIAS0K && CHAIN && !Probe::no_res0 && SH::k1p <= 24 && SH::nx + SH::nu < SH::k1p;
 
   // Layer 0's fragments are RESIDENT in registers for the kernel's lifetime whenever the layer is
   // at most KS0RES k-steps (all widths in f32; k1p <= 24, i.e. nx + nu <= 24, in f64 -- HalfCheetah
@@ -771,7 +786,8 @@ struct TileNet {
   // read.  (16-row tiles only: the taller tiles are register-bound and read the bias from LDS.)
   static constexpr bool RESIDENT_BIAS = LEAN < 1 && (MT == 1);
   // (the first kResBias hidden layers -- the reference's default network has two; deeper layers'
-  // accumulators are seeded from the LDS copy of the bias instead, one read per column tile)
+  // epilogues add the bias from its LDS copy instead: one read per column tile, bq_ per register when CHAIN;
+  // BIAS0_IN_K: layer 0's slot is neither loaded nor read)
   static constexpr int kResBias = 2;
   // (CHAIN: the bias of the unit each accumulator register holds, [nt][r] -> unit 16 nt + 4 r + q)
   T bias_r[kResBias][NT][BR];
@@ -860,11 +876,23 @@ struct TileNet {
 #pragma unroll
         for (int r = 0; r < BR; ++r) {
           const int col = CHAIN ? 4 * r + (lane >> 4) : (lane & 15);
-          bias_r[l][nt][r] = (RESIDENT_BIAS && !CHAIN_BIAS_LDS && l < m.n_hidden) ? m.B(l)[16 * (NT * w + nt) + col] : T(0);
+          if (BIAS0_IN_K && l == 0) bias_r[l][nt][r] = T(0);
+          else bias_r[l][nt][r] = (RESIDENT_BIAS && !CHAIN_BIAS_LDS && l < m.n_hidden) ? m.B(l)[16 * (NT * w + nt) + col] : T(0);
         }
     wr = weight_rsrc(m.WB());
     if constexpr (RESIDENT_OUT) load_out(m, w, lane, wout);
     load0_all(m);
+    if constexpr (BIAS0_IN_K) {
+      // weight row k1p - 1 (the packed zero pad row) <- layer 0's bias: k-step k1p / 4 - 1, lanes of k = 3; the
+      // fragment is the MFMA's first operand here (CHAIN), W[unit 16 (NT w + nt) + (lane & 15)][k = lane >> 4].
+      // (a select, not a branch: see load0_all on stores to pf0 from two paths)
+      constexpr int ksb = SH::k1p / 4 - 1;
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) {
+        const T b = m.B(0)[16 * (NT * w + nt) + (lane & 15)];
+        pf0[ksb][nt] = (lane >> 4) == 3 ? b : pf0[ksb][nt];
+      }
+    }
     // first group of hidden layer 1 for the FIRST call (later calls request it at the end of the
     // previous one): requested here so that run() has a single source for it -- a "first call"
     // branch in run() makes the prefetch buffer a phi of two register sets, i.e. 16 v_mov per call
@@ -890,6 +918,35 @@ struct TileNet {
       if (ks < ks0) load_frag<T, NT>(wr, wl + (unsigned)ks * 64u * NT, (unsigned)lane * NT, tmp);
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) pf0[ks][nt] = tmp[nt];
+    }
+  }
+
+  // relu of layer 0's raw MFMA results (BIAS0_IN_K: no add in between).  Written as z > 0 ? z : 0 it
+  // becomes v_max_f64 z, 0 behind a quieting v_max_f64 z, z -- the eight instructions the bias column saved --
+  // because the compiler cannot know that an MFMA result is never a signalling NaN.  So the instruction is
+  // written out: for a quiet NaN and for either zero it returns +0, like the comparison.  The compiler inserts
+  // no wait states between an MFMA and inline assembly that reads its result, so the block brings its own: a
+  // VALU read of a v_mfma_f64_16x16x4 result needs 19 (what hipcc puts in front of the v_add_f64 otherwise).
+  // One block for the wave's column tiles where there are two, so that the wait is paid once.  The results go to
+  // registers of their own (early-clobber outputs): what reads them next would otherwise still count as a reader
+  // of MFMA results, and hipcc would wait the 19 states a second time behind the block.  (The closing s_nop 1: an
+  // MFMA that reads the last result as an operand right behind the block -- hipcc keeps two states there.)
+  __device__ __forceinline__ static void relu0_raw(const acc_t (&a)[NT], T (&v)[NT][4]) {
+    if constexpr (NT == 2) {
+      asm("s_nop 15\n\ts_nop 2\n\t"
+          "v_max_f64 %0, %8, 0\n\tv_max_f64 %1, %9, 0\n\tv_max_f64 %2, %10, 0\n\tv_max_f64 %3, %11, 0\n\t"
+          "v_max_f64 %4, %12, 0\n\tv_max_f64 %5, %13, 0\n\tv_max_f64 %6, %14, 0\n\tv_max_f64 %7, %15, 0\n\ts_nop 1"
+          : "=&v"(v[0][0]), "=&v"(v[0][1]), "=&v"(v[0][2]), "=&v"(v[0][3]), "=&v"(v[1][0]), "=&v"(v[1][1]),
+            "=&v"(v[1][2]), "=&v"(v[1][3])
+          : "v"(a[0][0]), "v"(a[0][1]), "v"(a[0][2]), "v"(a[0][3]), "v"(a[1][0]), "v"(a[1][1]), "v"(a[1][2]),
+            "v"(a[1][3]));
+    } else {
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt)
+        asm("s_nop 15\n\ts_nop 2\n\t"
+            "v_max_f64 %0, %4, 0\n\tv_max_f64 %1, %5, 0\n\tv_max_f64 %2, %6, 0\n\tv_max_f64 %3, %7, 0\n\ts_nop 1"
+            : "=&v"(v[nt][0]), "=&v"(v[nt][1]), "=&v"(v[nt][2]), "=&v"(v[nt][3])
+            : "v"(a[nt][0]), "v"(a[nt][1]), "v"(a[nt][2]), "v"(a[nt][3]));
     }
   }
 
@@ -1059,14 +1116,23 @@ struct TileNet {
     T own[NT][4];
     auto chain_k = [&](int l, acc_t (&acc)[MT][NT], int db, bool store, auto kind_tag) {
       constexpr int KIND = decltype(kind_tag)::value;
+      T raw0[NT][4];                        // (BIAS0_IN_K, relu, layer 0 only)
+      if constexpr (BIAS0_IN_K && KIND == 0 && MT == 1)
+        if (l == 0) relu0_raw(acc[0], raw0);
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          T bc;
-          if (!CHAIN_BIAS_LDS && l < kResBias) bc = (l == 0) ? bias_r[0][nt][r % BR] : bias_r[kResBias - 1][nt][r % BR];
-          else bc = bq_[l * HP + 16 * nt + 4 * r];
-          const T v = act_apply<T>(KIND, acc[0][nt][r] + bc);
+          T v;
+          if (BIAS0_IN_K && l == 0) {       // the bias came in as the last link of the MFMA chain
+            if constexpr (KIND == 0) v = raw0[nt][r];
+            else v = act_apply<T>(KIND, acc[0][nt][r]);
+          } else {
+            T bc;
+            if (!CHAIN_BIAS_LDS && l < kResBias) bc = (l == 0) ? bias_r[0][nt][r % BR] : bias_r[kResBias - 1][nt][r % BR];
+            else bc = bq_[l * HP + 16 * nt + 4 * r];
+            v = act_apply<T>(KIND, acc[0][nt][r] + bc);
+          }
           own[nt][r] = v;
           if (store) (db ? ep_[1][0] : ep_[0][0])[16 * nt + 4 * r] = v;
         }

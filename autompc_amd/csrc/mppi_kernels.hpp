@@ -193,7 +193,8 @@ template <typename T, int NT, int MT, int W, typename SH = DynShape, bool WIDE =
 __global__ __launch_bounds__(64 * W) void mppi_rollout_kernel(const MppiArgs<T> args) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   T* lds = reinterpret_cast<T*>(smem_raw);
-  using Net = TileNet<T, NT, MT, W, false, 0, SH, WIDE, true>;   // (pinned addresses: run() in the time loop)
+  // (pinned addresses: run() in the time loop; layer 0's bias through the spare K column where the tile has one)
+  using Net = TileNet<T, NT, MT, W, false, 0, SH, WIDE, true, true>;
   constexpr int M = 16 * MT, NTHR = 64 * W;
   constexpr int TPS = NTHR / M;                 // threads per sample (32..4), all in one wave
   constexpr int EPT = (16 + TPS - 1) / TPS;     // noise elements per thread (nu <= 16)
@@ -276,6 +277,12 @@ __global__ __launch_bounds__(64 * W) void mppi_rollout_kernel(const MppiArgs<T> 
     const int row = i / nx, col = i - row * nx;
     xu[row * xs_ + col] = args.x0[p * nx + col];
   }
+  // Net::BIAS0_IN_K: 1.0 in the last pad column of [x | u | 0] for every row of the tile (rows past N too), the
+  // operand of layer 0's bias row.  Behind the barrier that published tile_load_constants' zeros and ahead of the
+  // one before the first run_side; nothing else writes this column for the kernel's lifetime -- actions() writes
+  // columns nx .. nx + nu - 1, the state update columns < nx -- and nothing but layer 0 reads it.
+  if constexpr (Net::BIAS0_IN_K)
+    for (int i = tid; i < M; i += NTHR) xu[i * xs_ + SH::k1p - 1] = T(1);
 
   // actions of step t: A = clip(eps + a), eps <- A - a, u = A * scale  (mppi.py:134-139)
   // (the thread's bounds / scale / R weight are loop invariants kept in registers: every LDS
@@ -449,7 +456,7 @@ template <typename T>
 __global__ __launch_bounds__(kWG) void mppi_combine_kernel(const MppiArgs<T> args, int tile_m,
                                                            const NoiseAhead<T> ahead) {
   __shared__ T scratch[kWaves];
-  __shared__ T red[kWaves][kMaxNu];
+  __shared__ T red[kWaves][kMaxNu + 1];           // [.][kMaxNu]: the waves' sums of scale_w s_w
   const int p = blockIdx.y, t = blockIdx.x, tid = threadIdx.x;
   const MppiProblem<T> pr = args.probs[p];
   if (t >= args.max_h) {
@@ -462,16 +469,36 @@ __global__ __launch_bounds__(kWG) void mppi_combine_kernel(const MppiArgs<T> arg
   const int nu = args.mlp.nu, H = pr.H;
   const int tiles = (pr.N + tile_m - 1) / tile_m;
   const T* st = args.tile_stat + 2 * (size_t)pr.tile0;
-  T vmin = st[0];
-  for (int i = tid; i < tiles; i += kWG) vmin = st[2 * i] < vmin ? st[2 * i] : vmin;
-  vmin = block_min(vmin, scratch);
   const T* tp = args.tile_part + (size_t)pr.tile0 * args.hnu_stride + t * nu;
+  // Everything the block reads is requested before the first reduction: the thread's first tile (minimum, weight
+  // sum, its nu partial sums of step t) and the warm start.  Whether the tile is live gates the USE of the values
+  // below, not the loads (a dead tile's sums are zeros inside the plan's buffers), so the kernel is one round trip
+  // to memory and not three in a chain.  Tiles past the first kWG are loaded where they are used, as before.
+  const bool has0 = tid < tiles;
+  const int i0 = has0 ? tid : 0;
+  const T m0 = st[2 * i0], s0 = st[2 * i0 + 1];
+  T row0[kMaxNu];
+#pragma unroll
+  for (int j = 0; j < kMaxNu; ++j) row0[j] = j < nu ? tp[(size_t)i0 * args.hnu_stride + j] : T(0);
+  const int ts = (t + 1 < H) ? t + 1 : H - 1;
+  const T a_in = tid < nu ? args.act_in[pr.a_off + ts * nu + tid] : T(0);
+  T vmin = st[0];
+  if (has0) vmin = m0 < vmin ? m0 : vmin;
+  for (int i = tid + kWG; i < tiles; i += kWG) vmin = st[2 * i] < vmin ? st[2 * i] : vmin;
+  vmin = block_min(vmin, scratch);
   T ssum = T(0);
   T acc[kMaxNu];
 #pragma unroll
   for (int j = 0; j < kMaxNu; ++j) acc[j] = T(0);
-  for (int i = tid; i < tiles; i += kWG) {
-    if (!(st[2 * i] < T(INFINITY))) continue;      // all-inf tile: weight 0 (its sums are zero too)
+  if (has0 && m0 < T(INFINITY)) {                    // all-inf tile: weight 0 (its sums are zero too)
+    const T sc = exp(pr.neg_inv_lambda * (m0 - vmin));
+    ssum += sc * s0;
+#pragma unroll
+    for (int j = 0; j < kMaxNu; ++j)
+      if (j < nu) acc[j] += sc * row0[j];
+  }
+  for (int i = tid + kWG; i < tiles; i += kWG) {
+    if (!(st[2 * i] < T(INFINITY))) continue;
     const T sc = exp(pr.neg_inv_lambda * (st[2 * i] - vmin));
     ssum += sc * st[2 * i + 1];
     const T* row = tp + (size_t)i * args.hnu_stride;
@@ -479,20 +506,24 @@ __global__ __launch_bounds__(kWG) void mppi_combine_kernel(const MppiArgs<T> arg
     for (int j = 0; j < kMaxNu; ++j)
       if (j < nu) acc[j] += sc * row[j];
   }
-  ssum = block_sum(ssum, scratch);
+  // one pass for the nu sums and the normaliser: each is a wave_sum, then the waves' values added in the order
+  // w = 0 .. kWaves - 1 (what block_sum does for the normaliser, with two barriers of its own)
 #pragma unroll
   for (int j = 0; j < kMaxNu; ++j)
     if (j < nu) {
       const T s = wave_sum(acc[j]);
       if ((tid & 63) == 0) red[tid >> 6][j] = s;
     }
+  {
+    const T s = wave_sum(ssum);
+    if ((tid & 63) == 0) red[tid >> 6][kMaxNu] = s;
+  }
   __syncthreads();
   if (tid < nu) {
-    T s = red[0][tid];
+    T s = red[0][tid], sw = red[0][kMaxNu];
 #pragma unroll
-    for (int w = 1; w < kWaves; ++w) s += red[w][tid];
-    const int ts = (t + 1 < H) ? t + 1 : H - 1;
-    const T a_new = args.act_in[pr.a_off + ts * nu + tid] + s / ssum;
+    for (int w = 1; w < kWaves; ++w) { s += red[w][tid]; sw += red[w][kMaxNu]; }
+    const T a_new = a_in + s / sw;
     args.act_out[pr.a_off + t * nu + tid] = a_new;
     if (t == 0) publish_u(args, p, nu, tid, a_new * args.bounds[2 * nu + tid]);
   }

@@ -1,8 +1,11 @@
 // Probe the lane layout and issue rate of v_mfma_f64_4x4x4_4b_f64 on this GPU (one-hot inputs), and the
-// swapped-operand ("transposed layer") use of it and of v_mfma_f64_16x16x4_f64 that TileNet::CHAIN relies on.
+// swapped-operand ("transposed layer") use of it and of v_mfma_f64_16x16x4_f64 that TileNet::CHAIN relies on, and the
+// bias as the last link of the 16x16x4's k chain (TileNet::BIAS0_IN_K): fma(b, 1.0, acc) against a separate add.
 // Build: hipcc --offload-arch=gfx950 -O2 tools/mfma44_probe.cpp -o variants/mfma44_probe
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <vector>
 
 __global__ void probe(const double* a, const double* b, double* d) {
@@ -52,6 +55,59 @@ static int check_swapped() {
   return bad;
 }
 
+// The bias through the last K column.  One block per trial; a = first operand [i = l%16][k = l/16], b = second operand
+// [k = l/16][j = l%16], c = the accumulator going in (register r of lane l = [row l/16 + 4 r][col l%16]).
+__global__ void bias_link(const double* a, const double* b, const double* c, double* d) {
+  const int l = threadIdx.x, t = blockIdx.x;
+  typedef double d4_t __attribute__((ext_vector_type(4)));
+  d4_t acc;
+  for (int i = 0; i < 4; ++i) acc[i] = c[256 * t + 4 * l + i];
+  acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[64 * t + l], b[64 * t + l], acc, 0, 0, 0);
+  for (int i = 0; i < 4; ++i) d[256 * t + 4 * l + i] = acc[i];
+}
+
+// Column k = 3 of one operand holds 1.0, of the other the bias of its row (weights first, TileNet::CHAIN's order) or
+// column (weights second).  Expected: the k-ordered fma chain over k = 0..2 on the incoming accumulator, then a
+// SEPARATE add of the bias -- what the epilogue's v_add_f64 gave.  Biases of 1e-8 .. 1e8 times the sum's magnitude.
+static int check_bias_link(bool weights_first) {
+  const int trials = 1024;
+  std::vector<double> ha(64 * trials), hb(64 * trials), hc(256 * trials), hd(256 * trials), bias(16 * trials);
+  srand(weights_first ? 1 : 2);
+  auto rnd = [] { return 2.0 * rand() / RAND_MAX - 1.0; };
+  for (int t = 0; t < trials; ++t) {
+    const double mag = pow(10.0, (t % 17) - 8);          // bias / sum: 1e-8 .. 1e8
+    for (int u = 0; u < 16; ++u) bias[16 * t + u] = mag * rnd();
+    for (int l = 0; l < 64; ++l) {
+      const int k = l / 16, n = l % 16;
+      const double w = k == 3 ? bias[16 * t + n] : rnd(), x = k == 3 ? 1.0 : rnd();
+      ha[64 * t + l] = weights_first ? w : x;
+      hb[64 * t + l] = weights_first ? x : w;
+    }
+    for (int e = 0; e < 256; ++e) hc[256 * t + e] = (t & 1) ? rnd() : 0.0;    // (layer 0's last k-step / its only one)
+  }
+  double *da, *db, *dc, *dd;
+  hipMalloc(&da, ha.size() * 8); hipMalloc(&db, hb.size() * 8); hipMalloc(&dc, hc.size() * 8); hipMalloc(&dd, hd.size() * 8);
+  hipMemcpy(da, ha.data(), ha.size() * 8, hipMemcpyHostToDevice); hipMemcpy(db, hb.data(), hb.size() * 8, hipMemcpyHostToDevice);
+  hipMemcpy(dc, hc.data(), hc.size() * 8, hipMemcpyHostToDevice);
+  bias_link<<<trials, 64>>>(da, db, dc, dd);
+  hipMemcpy(hd.data(), dd, hd.size() * 8, hipMemcpyDeviceToHost);
+  hipFree(da); hipFree(db); hipFree(dc); hipFree(dd);
+  int bad = 0;
+  for (int t = 0; t < trials; ++t)
+    for (int l = 0; l < 64; ++l)
+      for (int r = 0; r < 4; ++r) {
+        const int row = l / 16 + 4 * r, col = l % 16;     // D[row][col] = sum_k A[row][k] B[k][col]
+        volatile double s = hc[256 * t + 4 * l + r];
+        for (int k = 0; k < 3; ++k) s = __builtin_fma(ha[64 * t + 16 * k + row], hb[64 * t + 16 * k + col], s);
+        const volatile double b = bias[16 * t + (weights_first ? row : col)];
+        const volatile double want = s + b;               // the separate add
+        if (hd[256 * t + 4 * l + r] != want) ++bad;
+      }
+  printf("bias as the last link of the 16x16x4 k chain, weights as the %s operand: %d mismatches in %d values against "
+         "the k-ordered fma chain followed by a separate add\n", weights_first ? "first" : "second", bad, 256 * trials);
+  return bad;
+}
+
 __global__ void rate(double* out, int iters) {
   double a = 1.0 + threadIdx.x * 1e-9, b = 1.0 - threadIdx.x * 1e-9;
   double c0 = 0, c1 = 0, c2 = 0, c3 = 0, c4 = 0, c5 = 0, c6 = 0, c7 = 0;
@@ -70,6 +126,8 @@ __global__ void rate(double* out, int iters) {
 
 int main() {
   check_swapped();
+  check_bias_link(true);
+  check_bias_link(false);
   double *da, *db, *dd;
   hipMalloc(&da, 64 * 8); hipMalloc(&db, 64 * 8); hipMalloc(&dd, 64 * 8);
   // For every (la, lb): which output lanes see a[la]*b[lb]?
