@@ -24,6 +24,7 @@ class AmpcError(RuntimeError):
 
 
 MPPI_TABLE_NO_FIT = -3     # ampc_mppi_plan_set_model_table: the table kernel's LDS map exceeds 160 KB for this plan
+#                            (ampc_mppi_plan_set_sindy_models: an entry's LDS need does)
 ILQR_TABLE_NO_FIT = -3     # ampc_ilqr_plan_set_model_table: the same for the table iteration kernel
 
 
@@ -107,6 +108,7 @@ SIGNATURES = {
                                           _ip, POINTER(ctypes.c_longlong)]),
     "ampc_ilqr_plan_set_models": (c_int, [c_void_p, c_int, POINTER(c_void_p)]),
     "ampc_mppi_plan_set_models": (c_int, [c_void_p, c_int, POINTER(c_void_p), _ip]),
+    "ampc_mppi_plan_set_sindy_models": (c_int, [c_void_p, c_int, POINTER(c_void_p), _ip]),
     "ampc_mppi_plan_set_model_table": (c_int, [c_void_p, c_int, _ip, _ip, _ip, POINTER(c_void_p), POINTER(c_void_p),
                                                POINTER(c_void_p), _ip, _ip]),
     "ampc_ilqr_plan_set_model_table": (c_int, [c_void_p, c_int, _ip, _ip, _ip, POINTER(c_void_p), POINTER(c_void_p),
@@ -584,6 +586,18 @@ class MppiPlan:
             self._p, len(ms), iptr(args["n_hidden"]), iptr(args["dims"]), iptr(args["acts"]), vpp(args["weights"]),
             vpp(args["biases"]), vpp(args["norms"]), iptr(args["on_device"]), iptr(mi)))
         self._table_args = args            # (keeps the parameters the table points into alive)
+
+    def set_sindy_models(self, handles, model_index):
+        """SINDy models of any mix of feature libraries per problem (ampc_mppi_plan_set_sindy_models): `handles` hold
+        SINDy models (Handle.set_sindy) of the plan handle's dimensions, precision and device, model_index [B] names
+        each problem's.  The plan keeps the handles alive; re-staging one of them needs another call.  None / empty
+        handles: back to the plan handle's own model.  A refusal raises AmpcError; its ``code`` is MPPI_TABLE_NO_FIT when
+        an entry's LDS need exceeds 160 KB for the plan's horizon cap and cost block."""
+        hs = list(handles or [])
+        arr = (c_void_p * max(len(hs), 1))(*[h._h for h in hs])
+        mi = None if not hs else np.ascontiguousarray(np.broadcast_to(np.asarray(model_index, dtype=np.int32), (self.B,)))
+        check(self.lib.ampc_mppi_plan_set_sindy_models(self._p, len(hs), arr, iptr(mi)))
+        self._sindy_models = hs
 
     def solve(self):
         check(self.lib.ampc_mppi_solve(self._p))

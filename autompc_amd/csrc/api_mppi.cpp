@@ -9,6 +9,7 @@
 #include <mutex>
 #include "jit_host.hpp"                // shape plugins compiled at run time
 #include "mppi_table_host.hpp"         // ampc_mppi_plan_set_model_table: checks and packing without a device call
+#include "mppi_sindy_table_kernels.hpp"   // ampc_mppi_plan_set_sindy_models: the kernel's selection rule and LDS need
 
 extern template int pred_impl<double>(ampc_handle*, const double*, const double*, double*, double*, double*, int);
 extern template int pred_impl<float>(ampc_handle*, const double*, const double*, double*, double*, double*, int);
@@ -312,6 +313,8 @@ extern "C" int ampc_mppi_plan_destroy(ampc_mppi_plan* p) {
   for (DevBuf* b : bufs) b->release();
   p->mlp_tab.release(); p->tile_order.release();
   p->table_models.release(); p->table_stage.release();
+  p->sindy_tab.release();
+  for (ampc_handle* mh : p->sindy_models) handle_release(mh);
   for (ampc_handle* mh : p->models) handle_release(mh);
   for (hipEvent_t e : p->ev) (void)hipEventDestroy(e);
   ampc_handle* h = p->h;
@@ -350,6 +353,8 @@ extern "C" int ampc_mppi_plan_set_models(ampc_mppi_plan* p, int n_models, ampc_h
     return 0;
   }
   REQUIRE(n_models >= 1 && models && model_index, "ampc_mppi_plan_set_models: NULL argument");
+  REQUIRE(p->sindy_n == 0, "ampc_mppi_plan_set_models: the plan holds a table of SINDy models "
+                           "(ampc_mppi_plan_set_sindy_models); remove it first");
   REQUIRE(p->table_n == 0, "ampc_mppi_plan_set_models: the plan holds a table of MLP models of mixed shapes "
                            "(ampc_mppi_plan_set_model_table); remove it first");
   for (int i = 0; i < n_models; ++i)
@@ -883,6 +888,9 @@ extern "C" int ampc_mppi_plan_set_geometry(ampc_mppi_plan* p, int tile_rows, int
                                              : mppi_require_static<float>(p, "ampc_mppi_plan_set_geometry")) return rc;
     if (int rc = build_tile_order(p)) return rc;
   }
+  // (a table of SINDy models: its LDS need follows the horizon cap)
+  if (p->sindy_n > 0)
+    if (int rc = mppi_sindy_table_lds(p, "ampc_mppi_plan_set_geometry")) return rc;
   return redraw ? ampc_mppi_generate_eps(p, seed, stream) : 0;
 }
 
@@ -924,6 +932,8 @@ extern "C" int ampc_mppi_plan_set_model_table(ampc_mppi_plan* p, int n_models, c
     p->forced_mt = 0;
     return mppi_table_rebuild(p);
   }
+  if (p->sindy_n > 0)
+    return mppi_table_fail("the plan holds a table of SINDy models (ampc_mppi_plan_set_sindy_models); remove it first");
   MppiTablePlanView v;
   v.f64 = h->precision == AMPC_F64; v.has_mlp = h->has_mlp; v.nx = h->nx; v.nu = h->nu; v.obs_dim = h->obs_dim;
   v.n_ind = h->n_ind; v.lift_n = p->lift_n; v.n_shape_models = (int)p->models.size();
@@ -979,6 +989,105 @@ extern "C" int ampc_mppi_plan_set_model_table(ampc_mppi_plan* p, int n_models, c
   p->table_n = n_models;
   p->model_idx.assign(model_index, model_index + p->B);
   return mppi_table_rebuild(p);
+}
+
+// ---------------------------------------------------------------------------------------------
+// SINDy models of any mix of feature libraries in one plan (mppi_sindy_table_kernels.hpp)
+// ---------------------------------------------------------------------------------------------
+template <typename T> static int mppi_sindy_table_lds_impl(ampc_mppi_plan* p, const char* who) {
+  const ampc_handle* h = p->h;
+  const int hcap = (p->max_h * h->nu + 3) / 4 * 4;
+  size_t need = 0;
+  for (const ampc_handle* mh : p->sindy_models) {
+    const SindyDev<T> m = sindy_of<T>(mh);
+    const size_t b = sindy_table_spread<T>(m, hcap, h->cost_stride, p->sindy_fp, kLdsLimit)
+                         ? sindy_table_spread_bytes<T>(m, hcap, h->cost_stride)
+                         : sindy_table_thread_bytes<T>(m, h->cost_stride);
+    if (b > kLdsLimit) {
+      g_err = std::string(who) + ": a model's per-thread columns (2 nx + nu + table entries, 64 samples), cost block and "
+                                 "staged program need more than 160 KB of LDS";
+      p->sindy_lds = 0;                  // (a solve refuses the plan until a geometry that fits is set)
+      return -3;
+    }
+    need = std::max(need, b);
+  }
+  p->sindy_lds = need;
+  return 0;
+}
+
+int mppi_sindy_table_lds(ampc_mppi_plan* p, const char* who) {
+  return p->h->precision == AMPC_F64 ? mppi_sindy_table_lds_impl<double>(p, who)
+                                     : mppi_sindy_table_lds_impl<float>(p, who);
+}
+
+template <typename T> static int mppi_sindy_table_upload(ampc_mppi_plan* p) {
+  std::vector<SindyDev<T>> descs(p->sindy_models.size());
+  for (size_t i = 0; i < descs.size(); ++i) descs[i] = sindy_of<T>(p->sindy_models[i]);
+  HIP_OK(p->sindy_tab.reserve(descs.size() * sizeof(SindyDev<T>)));
+  HIP_OK(hipMemcpy(p->sindy_tab.p, descs.data(), descs.size() * sizeof(SindyDev<T>), hipMemcpyHostToDevice));
+  return 0;
+}
+
+static void mppi_sindy_table_drop(ampc_mppi_plan* p) {
+  for (ampc_handle* mh : p->sindy_models) handle_release(mh);
+  p->sindy_models.clear();
+  p->sindy_n = 0;
+  p->sindy_lds = 0;
+}
+
+extern "C" int ampc_mppi_plan_set_sindy_models(ampc_mppi_plan* p, int n_models, ampc_handle* const* models,
+                                               const int* model_index) {
+  static const char* const who = "ampc_mppi_plan_set_sindy_models";
+  const std::string w(who);
+  REQUIRE(p, w + ": NULL plan");
+  ampc_handle* h = p->h;
+  HIP_OK(hipSetDevice(h->device));
+  if (n_models == 0) {                               // back to the handle's own model
+    if (p->sindy_n == 0) return 0;
+    HIP_OK(hipStreamSynchronize(h->stream));
+    mppi_sindy_table_drop(p);
+    p->model_idx.clear();
+    return h->precision == AMPC_F64 ? mppi_set_noise_ids_impl<double>(p) : mppi_set_noise_ids_impl<float>(p);
+  }
+  REQUIRE(n_models >= 1 && models && model_index, w + ": NULL argument");
+  REQUIRE(h->has_sindy, w + ": the plan handle's model is not a SINDy model (ampc_set_sindy)");
+  REQUIRE(p->lift_n == 0, w + ": the plan has a state lift; the SINDy rollout runs on the observation");
+  REQUIRE(p->models.empty(), w + ": the plan holds per-problem models of one shape (ampc_mppi_plan_set_models); remove "
+                                 "them first");
+  REQUIRE(p->table_n == 0, w + ": the plan holds a table of MLP models (ampc_mppi_plan_set_model_table); remove it first");
+  for (int i = 0; i < n_models; ++i) {
+    const ampc_handle* m = models[i];
+    REQUIRE(m != nullptr, w + ": NULL model handle");
+    REQUIRE(m->has_sindy, w + ": a model handle holds no SINDy model (ampc_set_sindy)");
+    REQUIRE(m->device == h->device && m->precision == h->precision, w + ": models must share the plan's device and precision");
+    REQUIRE(m->nx == h->nx && m->nu == h->nu, w + ": models must have the plan handle's state and control dimensions");
+  }
+  for (int b = 0; b < p->B; ++b)
+    REQUIRE(model_index[b] >= 0 && model_index[b] < n_models, w + ": model_index out of range");
+  // (a running solve may read the table being replaced; the models' staging has finished before the rollout reads it)
+  HIP_OK(hipStreamSynchronize(h->stream));
+  for (int i = 0; i < n_models; ++i) HIP_OK(hipStreamSynchronize(models[i]->stream));
+  // the LDS need first, on the new handles: a refusal (-3) leaves the plan as it was
+  std::vector<ampc_handle*> old;
+  old.swap(p->sindy_models);
+  const int old_fp = p->sindy_fp;
+  const size_t old_lds = p->sindy_lds;
+  p->sindy_models.assign(models, models + n_models);
+  p->sindy_fp = env_int("AMPC_SINDY_FP", 1) != 0 ? 1 : 0;
+  int rc = mppi_sindy_table_lds(p, who);
+  if (rc == 0) rc = h->precision == AMPC_F64 ? mppi_sindy_table_upload<double>(p) : mppi_sindy_table_upload<float>(p);
+  if (rc) {
+    p->sindy_models.swap(old);
+    p->sindy_fp = old_fp;
+    p->sindy_lds = old_lds;
+    return rc;
+  }
+  for (ampc_handle* mh : p->sindy_models) mh->refs++;
+  for (ampc_handle* mh : old) handle_release(mh);
+  p->sindy_n = n_models;
+  p->model_idx.assign(model_index, model_index + p->B);
+  // the problems' descriptors carry the entry
+  return h->precision == AMPC_F64 ? mppi_set_noise_ids_impl<double>(p) : mppi_set_noise_ids_impl<float>(p);
 }
 
 extern "C" int ampc_mppi_plan_set_step_offset(ampc_mppi_plan* p, uint64_t first_step) {

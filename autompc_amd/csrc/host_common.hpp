@@ -479,7 +479,19 @@ struct ampc_mppi_plan {
   // problem's entry.  table_n > 0: the plan runs mppi_rollout_table_kernel in 16-row tiles (plan_build).
   int table_n = 0;
   DevBuf table_models, table_stage;
+  // SINDy models of any mix of feature libraries (ampc_mppi_plan_set_sindy_models): the device table of their
+  // descriptors (SindyDev<T>, pointers into the handles' buffers; the plan keeps the handles alive) -- model_idx names
+  // a problem's entry.  sindy_n > 0: the plan runs mppi_rollout_sindy_table_kernel (mppi_sindy_table_kernels.hpp) with
+  // sindy_lds bytes of LDS, the largest entry's need for the plan's horizon cap; sindy_fp: AMPC_SINDY_FP as it stood
+  // when the table was set (a plan constant of the kernel's selection rule).
+  int sindy_n = 0, sindy_fp = 1;
+  size_t sindy_lds = 0;
+  DevBuf sindy_tab;
+  std::vector<ampc_handle*> sindy_models;
 };
+
+// api_mppi.cpp: (re)compute sindy_lds for the plan's current horizon cap; -3 when an entry's need exceeds the limit
+int mppi_sindy_table_lds(ampc_mppi_plan* p, const char* who);
 
 // launch_mppi_table.cpp (f64 only, not part of a shape plugin)
 int mppi_table_lds_base();

@@ -2,6 +2,9 @@
 // Compiled once per precision (-DAMPC_T=double|float, csrc/build.py); the explicit instantiations
 // at the end are what api.cpp links against.
 #include "host_common.hpp"
+#ifndef AMPC_JIT_PLUGIN
+#include "mppi_sindy_table_kernels.hpp"   // (SINDy models of mixed libraries in one plan: not part of a shape plugin)
+#endif
 
 #ifndef AMPC_T
 #error "compile with -DAMPC_T=double or -DAMPC_T=float"
@@ -28,6 +31,13 @@ template <typename T> int mppi_solve_impl(ampc_mppi_plan* p) {
                 "indicator cost terms; the table kernel takes quadratic cost blocks only");
   if (p->table_n > 0 && p->lift_n > 0)
     return fail("ampc_mppi_solve: the plan holds a table of MLP models (ampc_mppi_plan_set_model_table) and a state lift");
+  // (a table of SINDy models -- ampc_mppi_plan_set_sindy_models -- runs mppi_rollout_sindy_table_kernel: the rollout is on
+  //  the observation, indicator terms included)
+  if (p->sindy_n > 0 && p->lift_n > 0)
+    return fail("ampc_mppi_solve: the plan holds a table of SINDy models (ampc_mppi_plan_set_sindy_models) and a state lift");
+  if (p->sindy_n > 0 && (!p->h->has_sindy || !p->sindy_tab.p || p->sindy_lds == 0))
+    return fail("ampc_mppi_solve: the plan's table of SINDy models (ampc_mppi_plan_set_sindy_models) has no valid LDS map: "
+                "the handle's model is no longer a SINDy model, or ampc_mppi_plan_set_geometry refused the horizon cap");
   if (p->jit) return jit_result(p->jit, p->jit->mppi_solve(p));     // same function, compiled for the shape
 #endif
   ampc_handle* h = p->h;
@@ -87,7 +97,20 @@ template <typename T> int mppi_solve_impl(ampc_mppi_plan* p) {
     if (sizeof(T) != 8) return fail("internal: four-row rollout in f32");      // (launched above)
   } else
 #ifndef AMPC_JIT_PLUGIN
-  if (p->table_n > 0) {           // MLP models of mixed shapes through a device table (mppi_table_kernels.hpp)
+  if (p->sindy_n > 0) {           // SINDy models of mixed libraries through a device table (mppi_sindy_table_kernels.hpp)
+    // sixteen workgroups per 64-sample tile: four samples each for a lane-spread entry, the first one alone for a
+    // one-thread entry; hcap as the single-model launch below forms it
+    const int hcap = (p->max_h * h->nu + 3) / 4 * 4;
+    const dim3 grid((unsigned)(p->n_tiles * kSindyTabSub));
+    auto launch = [&](auto kernel) -> int {
+      HIP_OK(allow_lds(kernel, p->sindy_lds));
+      hipLaunchKernelGGL(kernel, grid, dim3(64), p->sindy_lds, h->stream, a, (const SindyDev<T>*)p->sindy_tab.p, hcap,
+                         p->sindy_fp, (unsigned)kLdsLimit);
+      return 0;
+    };
+    if (int rc = h->n_ind > 0 ? launch(mppi_rollout_sindy_table_kernel<T, true>)
+                              : launch(mppi_rollout_sindy_table_kernel<T, false>)) return rc;
+  } else if (p->table_n > 0) {    // MLP models of mixed shapes through a device table (mppi_table_kernels.hpp)
     if constexpr (sizeof(T) == 8) {
       if (int rc = mppi_table_launch(p, &a)) return rc;
     } else {

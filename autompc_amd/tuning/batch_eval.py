@@ -163,6 +163,29 @@ def ilqr_table_decision(candidates, default, precision="f64", device=0, obs_dim=
     return ok, why
 
 
+def sindy_table_decision(candidates, default, precision="f64", device=0, lift=None):
+    """(True, "") when ONE MPPI plan with a table of SINDy models (MppiPlan.set_sindy_models) takes the whole batch,
+    else (False, why).  It does when every candidate's controller model (`default`, the evaluator's own, for a
+    candidate without a "model") is a ``sysid.SINDy`` of the evaluator's system, precision and device -- whatever its
+    feature library, coefficients and time mode -- and the controller model is not lifted.  Needs no GPU."""
+    from ..sysid.sindy import SINDy
+    if lift is not None:
+        return False, "the controller model's state is a lift of the observation"
+    system = getattr(default, "system", None)
+    for c in candidates:
+        m = c.get("model") if isinstance(c, dict) else None
+        m = default if m is None else m
+        if not isinstance(m, SINDy):
+            return False, "%s is not a SINDy model" % type(m).__name__
+        if system is not None and not (m.system == system):
+            return False, "a candidate's model belongs to another system than the evaluator's"
+        if m.precision != precision:
+            return False, "a candidate's model computes in %s, the evaluator in %s" % (m.precision, precision)
+        if int(m.device) != int(device):
+            return False, "a candidate's model lives on another device than the evaluator"
+    return True, ""
+
+
 def _needs_specialised_kernels(err):
     """The library's refusal of a model TABLE on a plan that runs the run-time-shape kernels (several models of one
     unregistered shape whose plugin is not built -- and, for one-evaluation models, never will be)."""
@@ -312,8 +335,14 @@ class CandidateEvaluator:
     accepts_global_ids = True          # evaluate(index_offset=<array of global indices>) is understood
 
     def __init__(self, system, task, model, surrogate=None, precision="f64", device=0,
-                 tile_rows=32, horizon_cap=30, term_check_every=8, mlp_models="shape"):
-        """mlp_models: "shape" -- candidates that carry controller models of different shapes run in one plan per
+                 tile_rows=32, horizon_cap=30, term_check_every=8, mlp_models="shape", sindy_models="single"):
+        """sindy_models: "single" -- a plan rolls out on ONE SINDy model: candidates that carry SINDy models of their own
+        are refused by the library -- or "table": one plan with a table of SINDy models of any mix of feature libraries
+        (MppiPlan.set_sindy_models, one rollout launch per control step) whenever ``sindy_table_decision`` allows it;
+        if the library declines the table (an entry's LDS need), one plan per model object.  ``last_models`` then
+        reads {"path": "sindy_table", "models": n, "plans": 1} or {"path": "model", ...}.
+
+        mlp_models: "shape" -- candidates that carry controller models of different shapes run in one plan per
         shape -- or "table": one plan with a model table for the whole batch (MppiPlan.set_model_table, 16-row tiles
         of one kernel) whenever ``table_decision`` allows it, the "shape" way otherwise.  ``last_models`` tells what
         the last evaluate() did: {"path": "table" | "shape", "models": n, "plans": n}.
@@ -328,8 +357,12 @@ class CandidateEvaluator:
         if mlp_models not in ("shape", "table"):
             raise ValueError('mlp_models must be "shape" or "table", not %r' % (mlp_models,))
         self.mlp_models = mlp_models
+        if sindy_models not in ("single", "table"):
+            raise ValueError('sindy_models must be "single" or "table", not %r' % (sindy_models,))
+        self.sindy_models = sindy_models
         self.last_models = None
         self._table = False
+        self._sindy_table = False
         if not hasattr(model, "stage_into"):
             raise TypeError("needs a device-stageable model (autompc_amd.sysid.MLP)")
         self.system, self.task, self.model = system, task, model
@@ -416,6 +449,31 @@ class CandidateEvaluator:
                         raise
                 finally:
                     _close_or_defer(self, opened)
+        if self.sindy_models == "table" and not self._sindy_table and not self._table:
+            ok, _why = sindy_table_decision(candidates, self.model, self.precision, self.device, self._lift)
+            if ok:
+                import copy
+                sub = copy.copy(self)
+                sub._sindy_table = True
+                opened = []
+                try:
+                    out = sub._evaluate(candidates, n_steps, seed, init_obs, eps_all, act_init, return_trajectories,
+                                        ids, opened, timing)
+                    self.last_lengths = sub.last_lengths
+                    self.last_models = {"path": "sindy_table", "models": n_models, "plans": 1}
+                    return out
+                except _lib.AmpcError as e:
+                    if e.code != _lib.MPPI_TABLE_NO_FIT:      # (an entry's LDS need: every model gets a plan of its own)
+                        raise
+                finally:
+                    _close_or_defer(self, opened)
+                if eps_all is not None or act_init is not None or timing is not None:
+                    raise ValueError("recorded noise / warm starts / kernel timing are laid out for ONE plan: evaluate "
+                                     "the candidates of each model separately")
+                by_model = _by_model(candidates, self.model)
+                self.last_models = {"path": "model", "models": n_models, "plans": len(by_model)}
+                return self._evaluate_shape_groups(by_model, candidates, ids, dict(
+                    n_steps=n_steps, seed=seed, init_obs=init_obs, return_trajectories=return_trajectories))
         shape_groups = _by_model_shape(candidates, self.model)
         self.last_models = {"path": "shape", "models": n_models,
                             "plans": 1 if shape_groups is None else len(shape_groups)}
@@ -462,6 +520,7 @@ class CandidateEvaluator:
             sub = copy.copy(self)
             sub._close_later = later
             sub.mlp_models = "shape"                      # (the batch was declined as a whole: every group goes the default way)
+            sub.sindy_models = "single"
             sub.model = candidates[idx[0]]["model"]       # the group's plan handle is staged with one of ITS models
             # (sub.surrogate stays the evaluator's simulation model: copy.copy kept the reference)
             return idx, sub, sub.evaluate([candidates[i] for i in idx], index_offset=ids[idx], **kw)
@@ -510,19 +569,28 @@ class CandidateEvaluator:
         h = _lib.Handle(self.device, self.precision,
                         jit=False if self._table else getattr(self.model, "jit_kernels", True))
         opened.append(h)
-        self.model.stage_into(h)
         # controller models the candidates carry (same shape as the evaluator's: evaluate() groups by shape):
         # one handle each, holding only the weights; the plan gets their table (ampc_mppi_plan_set_models)
         models, self._model_index = candidate_models(candidates, self.model)
+        # (a table of SINDy models needs a SINDy model on the plan handle too: the evaluator's own, else the batch's first)
+        plan_model = self.model
+        if self._sindy_table:
+            from ..sysid.sindy import SINDy
+            if not isinstance(self.model, SINDy):
+                plan_model = models[0]
+        plan_model.stage_into(h)
         self._model_handles = []
         self._table_models = models if self._table else None       # (no per-model handles: the plan reads a table)
-        if not self._table and (len(models) > 1 or models[0] is not self.model):
+        self._sindy_handles = []
+        if self._sindy_table:
+            self._sindy_handles = [model_handle(m, self.device, self.precision, opened) for m in models]
+        elif not self._table and (len(models) > 1 or models[0] is not self.model):
             self._model_handles = [model_handle(m, self.device, self.precision, opened) for m in models]
         blocks, _ = candidate_cost_blocks(candidates, self.goal, no, nu)
         h.set_cost_blocks(**blocks)
         h.set_ctrl_bounds(self.umin, self.umax)
         sur = None
-        if self.surrogate is not self.model:
+        if self.surrogate is not plan_model:
             sur = _lib.Handle(self.device, self.precision, jit=False) if self._table else \
                 _lib.Handle(self.device, self.precision)
             opened.append(sur)
@@ -539,6 +607,8 @@ class CandidateEvaluator:
         plan.set_geometry(16 if self._table else self.tile_rows, self.horizon_cap)
         if self._table:
             plan.set_model_table(self._table_models, self._model_index[np.asarray(which)])
+        if self._sindy_table:
+            plan.set_sindy_models(self._sindy_handles, self._model_index[np.asarray(which)])
         if self._lift is not None:
             plan.set_state_lift(*self._lift)
         plan.set_noise_ids(np.asarray(noise_ids)[which])

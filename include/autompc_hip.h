@@ -45,8 +45,8 @@ int ampc_version(void);   /* 100 * major + minor; 104: + ampc_mppi_run_legacy; 1
                            * 108: + ampc_kstep_errors; 109: + ampc_lqr_*; 110: + ampc_linfit_fit;
                            * 111: + ampc_kstep_errors_linear; 112: + ampc_kstep_errors_sindy;
                            * 113: + ampc_sindy_fit; 114: + ampc_lasso_fit; + ampc_stable_fit, + ampc_mlpfit_*, + ampc_kstep_errors_mlp,
-                           *      + ampc_mppi_plan_set_model_table, + ampc_ilqr_plan_set_model_table (no bump: callers detect them by
-                           *      their symbols) */
+                           *      + ampc_mppi_plan_set_model_table, + ampc_ilqr_plan_set_model_table, + ampc_mppi_plan_set_sindy_models
+                           *      (no bump: callers detect them by their symbols) */
 int ampc_device_count(void);
 
 /* ---- handle ------------------------------------------------------------------------------ */
@@ -468,6 +468,25 @@ int ampc_mppi_plan_set_model_table(ampc_mppi_plan* p, int n_models, const int* n
                                    const int* activations, const double* const* weights,
                                    const double* const* biases, const double* const* norms, const int* on_device,
                                    const int* model_index);
+/* SINDy models of ANY mix of feature libraries (trig basis and frequency, interaction terms, polynomial degree, cross
+ * terms), coefficients and time modes in one MPPI plan, f64 or f32: the rollout of every problem b runs on
+ * models[model_index[b]], one launch per solve for the whole plan (csrc/mppi_sindy_table_kernels.hpp).  models[n_models]:
+ * handles staged with ampc_set_sindy; the plan keeps a device table of their descriptors (and the handles alive) and
+ * waits for their streams.  Staging a new library or new coefficients into one of them afterwards needs another call.
+ * n_models = 0 removes the table: the plan runs on its handle's own model again.  Cost blocks (indicator terms
+ * included), bounds and the surrogate remain the plan handle's; ampc_mppi_solve, ampc_mppi_closed_loop and
+ * ampc_mppi_closed_loop_scored work on such a plan unchanged.  Per entry the kernel spreads the features over sixteen
+ * lanes per sample (entries staged in LDS with a product table and at most eight states; AMPC_SINDY_FP=0 at the time of
+ * this call switches it off) or runs one thread per sample; ampc_mppi_plan_set_geometry afterwards keeps the table.
+ * Refused with a message: a plan handle or a model handle without a SINDy model; models whose nx, nu, precision or device
+ * are not the plan handle's; a state lift on the plan (again at solve time if it is set later); a plan that holds
+ * per-problem models of one shape (ampc_mppi_plan_set_models) or a table of MLP models (ampc_mppi_plan_set_model_table)
+ * -- and those two calls on a plan that holds this table; a model_index out of range; and -- return code -3 instead of
+ * -1 -- an entry whose LDS need exceeds 160 KB for the plan's horizon cap and cost block.
+ * Deterministic: a problem's costs, clipped noise and controls are the same bits alone, in any plan of the same
+ * geometry, at any position of it -- the bits of a single-model plan on that model under AMPC_SINDY_G=16.  (Added
+ * without a version bump: callers detect it by its symbol.) */
+int ampc_mppi_plan_set_sindy_models(ampc_mppi_plan* p, int n_models, ampc_handle* const* models, const int* model_index);
 
 /* MLP models of ANY mix of depth, widths and activation in one f64 iLQR plan: the slot of a problem / episode runs on
  * the entry of a device table that model_index[n] of ampc_ilqr_solve_queue_var / ampc_ilqr_closed_loop_var names (range-
