@@ -26,6 +26,7 @@ class AmpcError(RuntimeError):
 MPPI_TABLE_NO_FIT = -3     # ampc_mppi_plan_set_model_table: the table kernel's LDS map exceeds 160 KB for this plan
 #                            (ampc_mppi_plan_set_sindy_models: an entry's LDS need does)
 ILQR_TABLE_NO_FIT = -3     # ampc_ilqr_plan_set_model_table: the same for the table iteration kernel
+#                            (ampc_ilqr_plan_set_sindy_models: an entry's LDS need does)
 
 
 _lib = None
@@ -109,6 +110,7 @@ SIGNATURES = {
     "ampc_ilqr_plan_set_models": (c_int, [c_void_p, c_int, POINTER(c_void_p)]),
     "ampc_mppi_plan_set_models": (c_int, [c_void_p, c_int, POINTER(c_void_p), _ip]),
     "ampc_mppi_plan_set_sindy_models": (c_int, [c_void_p, c_int, POINTER(c_void_p), _ip]),
+    "ampc_ilqr_plan_set_sindy_models": (c_int, [c_void_p, c_int, POINTER(c_void_p)]),
     "ampc_mppi_plan_set_model_table": (c_int, [c_void_p, c_int, _ip, _ip, _ip, POINTER(c_void_p), POINTER(c_void_p),
                                                POINTER(c_void_p), _ip, _ip]),
     "ampc_ilqr_plan_set_model_table": (c_int, [c_void_p, c_int, _ip, _ip, _ip, POINTER(c_void_p), POINTER(c_void_p),
@@ -833,6 +835,16 @@ class IlqrPlan:
             self._p, len(ms), iptr(args["n_hidden"]), iptr(args["dims"]), iptr(args["acts"]), vpp(args["weights"]),
             vpp(args["biases"]), vpp(args["norms"]), iptr(args["on_device"])))
         self._table_args = args            # (keeps the parameters the table points into alive)
+
+    def set_sindy_models(self, handles):
+        """SINDy models of any mix of feature libraries (ampc_ilqr_plan_set_sindy_models, f64): `handles` hold SINDy
+        models of the plan handle's state and control dimensions; solve_queue / closed_loop then take model_index
+        (entry 0 without it).  The plan keeps the handles alive.  None / empty handles: back to the plan handle's own
+        model.  A refusal raises AmpcError; its ``code`` is ILQR_TABLE_NO_FIT when an entry's LDS need exceeds 160 KB."""
+        hs = list(handles or [])
+        arr = (c_void_p * max(len(hs), 1))(*[h._h for h in hs])
+        check(self.lib.ampc_ilqr_plan_set_sindy_models(self._p, len(hs), arr))
+        self._sindy_models = hs             # (kept alive on this side as well)
 
     def _model_index(self, model_index, n):
         if model_index is None:

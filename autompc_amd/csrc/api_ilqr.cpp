@@ -5,6 +5,7 @@
 #include <mutex>
 #include "jit_host.hpp"                // shape plugins compiled at run time
 #include "ilqr_table_host.hpp"         // ampc_ilqr_plan_set_model_table: checks and the LDS map without a device call
+#include "ilqr_sindy_table_host.hpp"   // ampc_ilqr_plan_set_sindy_models: checks, the selection rule and the LDS maps
 
 extern template int pred_impl<double>(ampc_handle*, const double*, const double*, double*, double*, double*, int);
 extern template int pred_impl<float>(ampc_handle*, const double*, const double*, double*, double*, double*, int);
@@ -74,7 +75,9 @@ template <typename T> static int ilqr_plan_build(ampc_ilqr_plan* p) {
             "ilqr plan: the sweep's workspace for this state / observation dimension does not fit the 160 KB LDS");
   const size_t e = sizeof(T);
   HIP_OK(p->d_cost_idx.reserve(B * sizeof(int)));
-  HIP_OK(hipMemcpy(p->d_cost_idx.p, p->cost_idx.data(), B * sizeof(int), hipMemcpyHostToDevice));
+  // (initialisation goes through the plan's OWN stream: the handle's stream is non-blocking, so work on the null
+  //  stream -- shared by every host thread -- is not ordered against the plan's kernels and may land behind them)
+  HIP_OK(hipMemcpyAsync(p->d_cost_idx.p, p->cost_idx.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
   HIP_OK(p->states.reserve((size_t)B * (H + 1) * nx * e));
   HIP_OK(p->ctrls.reserve((size_t)B * H * nu * e));
   if (!h->has_lin) {              // (a linear model's Jacobians are the constant [A | B]: LinDev::jp)
@@ -85,17 +88,18 @@ template <typename T> static int ilqr_plan_build(ampc_ilqr_plan* p) {
   }
   HIP_OK(p->Ks.reserve((size_t)B * H * nu * nx * e));
   HIP_OK(p->ks.reserve((size_t)B * H * nu * e));
-  HIP_OK(hipMemset(p->Ks.p, 0, (size_t)B * H * nu * nx * e));
-  HIP_OK(hipMemset(p->ks.p, 0, (size_t)B * H * nu * e));
+  HIP_OK(hipMemsetAsync(p->Ks.p, 0, (size_t)B * H * nu * nx * e, h->stream));
+  HIP_OK(hipMemsetAsync(p->ks.p, 0, (size_t)B * H * nu * e, h->stream));
   HIP_OK(p->ls_states.reserve((size_t)B * p->ls_n * (H + 1) * nx * e));
   HIP_OK(p->ls_ctrls.reserve((size_t)B * p->ls_n * H * nu * e));
   HIP_OK(p->obj.reserve((size_t)B * e));
   HIP_OK(p->flags.reserve((size_t)9 * B * sizeof(int)));
-  HIP_OK(hipMemset(p->flags.p, 0, (size_t)9 * B * sizeof(int)));
+  HIP_OK(hipMemsetAsync(p->flags.p, 0, (size_t)9 * B * sizeof(int), h->stream));
   const int rows = B * H;
   const int n_pad = round_up(rows, 64);
   if (!h->has_sindy && !h->has_lin) HIP_OK(p->dz.reserve((size_t)m.n_hidden * n_pad * m.hpad * e));
   HIP_OK(p->ric.reserve((size_t)kRicStride * p->B * e));
+  HIP_OK(hipStreamSynchronize(h->stream));
   return 0;
 }
 
@@ -205,6 +209,8 @@ extern "C" int ampc_ilqr_plan_destroy(ampc_ilqr_plan* p) {
   for (DevBuf* b : bufs) b->release();
   p->mlp_tab.release(); p->slot_model.release(); p->slot_of.release();
   p->table_models.release(); p->table_stage.release(); p->table_dz.release();
+  p->sindy_tab.release();
+  for (ampc_handle* mh : p->sindy_models) handle_release(mh);
   for (ampc_handle* mh : p->models) handle_release(mh);
   for (hipEvent_t e : p->ev) (void)hipEventDestroy(e);
   if (p->poll_host) (void)hipHostFree(p->poll_host);
@@ -387,7 +393,9 @@ static int ilqr_solve_queue_impl(ampc_ilqr_plan* p, int P, const double* x0, con
     //  the slots' cost blocks are the plan's own again, as ampc_ilqr_solve expects them)
     ~Guard() {
       (void)hipStreamSynchronize(p->h->stream);
-      (void)hipMemcpy(p->d_cost_idx.p, p->cost_idx.data(), (size_t)p->B * sizeof(int), hipMemcpyHostToDevice);
+      (void)hipMemcpyAsync(p->d_cost_idx.p, p->cost_idx.data(), (size_t)p->B * sizeof(int), hipMemcpyHostToDevice,
+                           p->h->stream);
+      (void)hipStreamSynchronize(p->h->stream);
       p->queue_on = false; p->var_h = false; p->var_model = false; p->compact_on = false; p->ev_cur = nullptr;
       (void)hipHostFree(p->poll_host); p->poll_host = nullptr;
     }
@@ -496,9 +504,9 @@ static int check_horizons(const ampc_ilqr_plan* p, int n, const int* horizon, co
 
 static int check_models(const ampc_ilqr_plan* p, int n, const int* model_index, const char* who) {
   if (model_index) {
-    REQUIRE(!p->models.empty() || p->table_n > 0,
+    REQUIRE(!p->models.empty() || p->table_n > 0 || p->sindy_n > 0,
             std::string(who) + ": model_index given but the plan has no model table (ampc_ilqr_plan_set_models)");
-    const int n_models = p->table_n > 0 ? p->table_n : (int)p->models.size();
+    const int n_models = p->table_n > 0 ? p->table_n : p->sindy_n > 0 ? p->sindy_n : (int)p->models.size();
     for (int j = 0; j < n; ++j)
       REQUIRE(model_index[j] >= 0 && model_index[j] < n_models, std::string(who) + ": bad model_index");
   }
@@ -517,6 +525,8 @@ extern "C" int ampc_ilqr_plan_set_models(ampc_ilqr_plan* p, int n_models, ampc_h
   REQUIRE(n_models >= 1 && models, "ampc_ilqr_plan_set_models: NULL argument");
   REQUIRE(p->table_n == 0, "ampc_ilqr_plan_set_models: the plan holds a table of MLP models of mixed shapes "
                            "(ampc_ilqr_plan_set_model_table); remove it first");
+  REQUIRE(p->sindy_n == 0, "ampc_ilqr_plan_set_models: the plan holds a table of SINDy models "
+                           "(ampc_ilqr_plan_set_sindy_models); remove it first");
   for (int i = 0; i < n_models; ++i)
     if (int rc = check_same_shape(p->h, models[i], "ampc_ilqr_plan_set_models")) return rc;
   if (p->static_shape < 0) {
@@ -553,6 +563,8 @@ extern "C" int ampc_ilqr_plan_set_model_table(ampc_ilqr_plan* p, int n_models, c
     p->table_models.release(); p->table_stage.release(); p->table_dz.release();
     return ilqr_plan_build<double>(p);               // (the kernel choices of the handle's shape)
   }
+  if (p->sindy_n > 0)
+    return ilqr_table_fail("the plan holds a table of SINDy models (ampc_ilqr_plan_set_sindy_models); remove it first");
   IlqrTablePlanView v;
   v.f64 = h->precision == AMPC_F64;
   v.has_mlp = h->has_mlp && !h->has_sindy && !h->has_lin && h->lin_n == 0;    // (a small linear model is staged as a network)
@@ -617,6 +629,72 @@ extern "C" int ampc_ilqr_plan_set_model_table(ampc_ilqr_plan* p, int n_models, c
   // (the run-time-shape sweep serves every model of the table; no shape-specialised kernel or plugin is involved:
   //  static_shape / jit were cleared above)
   p->table_n = n_models; p->table_wmax = wmax; p->table_hidden = hmax;
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// SINDy models of any mix of feature libraries in one plan (ilqr_sindy_table_kernels.hpp)
+// ---------------------------------------------------------------------------------------------
+static IlqrSindyView ilqr_sindy_view(const ampc_handle* h) {
+  IlqrSindyView v;
+  v.f64 = h->precision == AMPC_F64; v.has_sindy = h->has_sindy ? 1 : 0; v.device = h->device;
+  v.nx = h->nx; v.nu = h->nu; v.obs_dim = h->obs_dim;
+  v.n_feat = h->s_nfeat; v.n_trig = h->s_ntrig; v.n_pow = h->s_npow; v.n_mon = h->s_nmon; v.n_pool = h->s_npool;
+  v.n_tab = h->s_ntab;
+  v.stage = (h->has_sindy && v.f64 && sindy_stage_bytes<double>(h) > 0) ? 1 : 0;
+  return v;
+}
+
+static void ilqr_sindy_table_drop(ampc_ilqr_plan* p) {
+  for (ampc_handle* mh : p->sindy_models) handle_release(mh);
+  p->sindy_models.clear();
+  p->sindy_n = 0;
+  p->sindy_lds = 0;
+}
+
+extern "C" int ampc_ilqr_plan_set_sindy_models(ampc_ilqr_plan* p, int n_models, ampc_handle* const* models) {
+  if (!p) return ilqr_sindy_table_fail("NULL plan");
+  ampc_handle* h = p->h;
+  if (n_models == 0) {                               // back to the handle's own model and its kernels
+    if (p->sindy_n == 0) return 0;
+    HIP_OK(hipSetDevice(h->device));
+    HIP_OK(hipStreamSynchronize(h->stream));
+    ilqr_sindy_table_drop(p);
+    return 0;
+  }
+  if (n_models < 1 || !models) return ilqr_sindy_table_fail("NULL argument");
+  const IlqrSindyView pv = ilqr_sindy_view(h);
+  std::vector<IlqrSindyView> views((size_t)n_models);
+  std::vector<const IlqrSindyView*> vp((size_t)n_models, nullptr);
+  for (int i = 0; i < n_models; ++i)
+    if (models[i]) { views[i] = ilqr_sindy_view(models[i]); vp[i] = &views[i]; }
+  size_t need = 0;
+  if (int rc = ilqr_sindy_table_check(pv, h->cost_stride, (int)p->models.size(), p->table_n, n_models, vp.data(), kLdsLimit,
+                                      &need))
+    return rc;
+  for (int i = 0; i < n_models; ++i) {
+    const IlqrSindyView& v = views[i];
+    if (v.stage && ilqr_sindy_prog_elems(v.nx, v.n_feat, v.n_trig, v.n_pow, v.n_mon, v.n_pool) * 8 <
+                       sindy_stage_bytes<double>(models[i]))
+      return ilqr_sindy_table_fail("internal: the staged program's size");
+  }
+  HIP_OK(hipSetDevice(h->device));
+  // (a running solve may read the table being replaced; the models' staging has finished before a kernel reads it)
+  HIP_OK(hipStreamSynchronize(h->stream));
+  for (int i = 0; i < n_models; ++i) HIP_OK(hipStreamSynchronize(models[i]->stream));
+  // From here on the plan holds NO table until the new one is complete: a failure below leaves the plan on its
+  // handle's own model.
+  ilqr_sindy_table_drop(p);
+  std::vector<SindyDev<double>> descs((size_t)n_models);
+  for (int i = 0; i < n_models; ++i) descs[i] = sindy_of<double>(models[i]);
+  HIP_OK(p->sindy_tab.reserve(descs.size() * sizeof(SindyDev<double>)));
+  HIP_OK(hipMemcpyAsync(p->sindy_tab.p, descs.data(), descs.size() * sizeof(SindyDev<double>), hipMemcpyHostToDevice,
+                        h->stream));
+  HIP_OK(hipStreamSynchronize(h->stream));           // (descs lives until here)
+  p->sindy_models.assign(models, models + n_models);
+  for (ampc_handle* mh : p->sindy_models) mh->refs++;
+  p->sindy_n = n_models;
+  p->sindy_lds = need;
   return 0;
 }
 
@@ -709,7 +787,9 @@ static int ilqr_closed_loop_impl(ampc_ilqr_plan* p, ampc_handle* sur, int C, con
     ampc_ilqr_plan* p;
     ~Guard() {
       (void)hipStreamSynchronize(p->h->stream);
-      (void)hipMemcpy(p->d_cost_idx.p, p->cost_idx.data(), (size_t)p->B * sizeof(int), hipMemcpyHostToDevice);
+      (void)hipMemcpyAsync(p->d_cost_idx.p, p->cost_idx.data(), (size_t)p->B * sizeof(int), hipMemcpyHostToDevice,
+                           p->h->stream);
+      (void)hipStreamSynchronize(p->h->stream);
       p->queue_on = false; p->var_h = false; p->var_model = false; p->compact_on = false; p->ev_cur = nullptr;
       (void)hipHostFree(p->poll_host); p->poll_host = nullptr;
     }

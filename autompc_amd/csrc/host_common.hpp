@@ -618,12 +618,23 @@ struct ampc_ilqr_plan {
   // names its entry (ampc_ilqr_*_var), the slot carries it.  (Behind everything a shape plugin reads.)
   int table_n = 0, table_wmax = 0, table_hidden = 0;
   DevBuf table_models, table_stage, table_dz;
+  // SINDy models of any mix of feature libraries (ampc_ilqr_plan_set_sindy_models, f64): the device table of their
+  // SindyDev descriptors (pointers into the handles' buffers; the plan keeps the handles alive) and the LDS bytes of
+  // its largest entry.  sindy_n > 0: the line search and the Jacobians are ilqr_sindy_table_kernels.hpp's, on the
+  // run-time-shape sweep; a queue problem / episode names its entry (ampc_ilqr_*_var), the slot carries it.
+  int sindy_n = 0;
+  size_t sindy_lds = 0;
+  std::vector<ampc_handle*> sindy_models;
+  DevBuf sindy_tab;
 };
 
 // launch_ilqr_table.cpp (f64 only, not part of a shape plugin)
 int ilqr_table_lds_base();
 int ilqr_table_launch_iter(ampc_ilqr_plan* p, const void* args);
 int ilqr_table_refresh(ampc_ilqr_plan* p);
+// launch_ilqr_sindy_table.cpp (f64 only, not part of a shape plugin)
+int ilqr_sindy_table_launch_iter(ampc_ilqr_plan* p, const void* args);
+int ilqr_sindy_table_refresh(ampc_ilqr_plan* p);
 
 template <typename T> static IlqrArgs<T> make_ilqr_args(ampc_ilqr_plan* p, int mode) {
   ampc_handle* h = p->h;

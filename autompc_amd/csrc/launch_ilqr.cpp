@@ -9,7 +9,7 @@
 
 template <typename T> int ilqr_launch_iter(ampc_ilqr_plan* p, int mode) {
 #ifndef AMPC_JIT_PLUGIN
-  if (p->var_model && p->table_n == 0 && p->static_shape < 0 && !p->jit)
+  if (p->var_model && p->table_n == 0 && p->sindy_n == 0 && p->static_shape < 0 && !p->jit)
     return fail("iLQR plan: per-slot controller models need the shape-specialised kernels (the run-time-shape kernels "
                 "take one model per plan); call ampc_ilqr_plan_set_models on a plan of a registered / compiled shape");
   if (p->jit) return jit_result(p->jit, p->jit->ilqr_iter(p, mode));
@@ -106,6 +106,16 @@ template <typename T> int ilqr_launch_iter(ampc_ilqr_plan* p, int mode) {
       return 0;
     }
     return fail("internal: a model table on an f32 iLQR plan");
+  }
+  // a table of SINDy models of mixed libraries (ampc_ilqr_plan_set_sindy_models): the line search of
+  // ilqr_sindy_table_kernels.hpp behind the run-time-shape sweep above
+  if (p->sindy_n > 0) {
+    if constexpr (sizeof(T) == 8) {
+      if (int rc = ilqr_sindy_table_launch_iter(p, &a)) return rc;
+      if (e) HIP_OK(hipEventRecord(e[2], h->stream));
+      return 0;
+    }
+    return fail("internal: a table of SINDy models on an f32 iLQR plan");
   }
   if (h->has_sindy) {
     auto k = ilqr_iter_kernel<T, 1, 4, 1>;

@@ -76,6 +76,7 @@ int pred_impl(ampc_handle* h, const double* states, const double* ctrls, double*
 template <typename T> int ilqr_refresh_jacobians(ampc_ilqr_plan* p) {
 #ifndef AMPC_JIT_PLUGIN
   if (p->table_n > 0) return ilqr_table_refresh(p);       // (a table of MLP models of mixed shapes: launch_ilqr_table.cpp)
+  if (p->sindy_n > 0) return ilqr_sindy_table_refresh(p); // (a table of SINDy models: launch_ilqr_sindy_table.cpp)
   if (p->jit) return jit_result(p->jit, p->jit->ilqr_refresh(p));
 #endif
   ampc_handle* h = p->h;

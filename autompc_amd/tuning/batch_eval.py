@@ -163,6 +163,39 @@ def ilqr_table_decision(candidates, default, precision="f64", device=0, obs_dim=
     return ok, why
 
 
+def ilqr_sindy_table_decision(candidates, default, precision="f64", device=0, obs_dim=None, ctrl_dim=None):
+    """(True, "") when ONE iLQR plan with a table of SINDy models (IlqrPlan.set_sindy_models) takes the whole batch, else
+    (False, why): ``sindy_table_decision`` -- every candidate's controller model (`default`, the evaluator's own, for a
+    candidate without a "model") is a ``sysid.SINDy`` of the evaluator's system, precision and device -- in f64 (the
+    table kernels' and the evaluator's only precision) within the sweep's limit of 63 states + controls.  Needs no
+    GPU."""
+    if precision != "f64":
+        return False, "the table kernels are f64 only"
+    ok, why = sindy_table_decision(candidates, default, precision, device)
+    if ok and obs_dim is not None and ctrl_dim is not None and int(obs_dim) + int(ctrl_dim) > 63:
+        return False, "state dim + ctrl dim exceeds 63, the iLQR sweep's limit"
+    return ok, why
+
+
+def ilqr_sindy_table_body(model):
+    """Which body of ilqr_iter_sindy_table_kernel an f64 SINDy model's table entry takes: "spread" (sixteen lanes per
+    line-search row) or "thread" (one).  Restates the library's rule from the model's feature library alone --
+    ampc_set_sindy's product table (two entries per distinct trig argument, one per distinct power and per monomial, a
+    constant; none beyond 160 entries), the 48 KB staging limit and ilqr_sindy_table_spread (csrc/
+    ilqr_sindy_table_host.hpp): a product table, at most eight states, a staged program.  Needs no GPU."""
+    kind, a0, a1, par, pair_var, _ = (np.asarray(a) for a in model.library)
+    nx, nf = int(model.system.obs_dim), int(kind.shape[0])
+    trig = {(int(a0[k] if kind[k] <= 2 else a1[k]), float(par[k])) for k in range(nf) if 1 <= kind[k] <= 4}
+    pows = {(int(a0[k]), float(par[k])) for k in range(nf) if kind[k] == 5}
+    n_trig, n_pow, n_mon = len(trig), len(pows), int(np.sum(kind == 6))
+    n_tab = 2 * n_trig + n_pow + n_mon + 1
+    if n_tab > 160:
+        return "thread"                                  # direct evaluation: no table, nothing staged
+    ints = 2 * nf + n_trig + n_pow + 2 * n_mon + 2 * int(pair_var.shape[0])
+    staged = (nf * nx + n_trig + n_pow + (ints * 4 + 7) // 8 + 2) * 8 <= 48 * 1024
+    return "spread" if (nx <= 8 and staged) else "thread"
+
+
 def sindy_table_decision(candidates, default, precision="f64", device=0, lift=None):
     """(True, "") when ONE MPPI plan with a table of SINDy models (MppiPlan.set_sindy_models) takes the whole batch,
     else (False, why).  It does when every candidate's controller model (`default`, the evaluator's own, for a
@@ -799,7 +832,7 @@ class IlqrCandidateEvaluator:
     accepts_global_ids = True
 
     def __init__(self, system, task, model, surrogate=None, precision="f64", device=0, device_resident=True,
-                 max_slots=1024, max_threads=32, one_plan=True, mlp_models="shape"):
+                 max_slots=1024, max_threads=32, one_plan=True, mlp_models="shape", sindy_models="single"):
         """device_resident: episodes of known length run entirely on the device (ampc_ilqr_closed_loop_var;
         a user termination condition is asked on the host, one queue of solves per control step);
         max_slots: problems solved side by side (one workgroup each);
@@ -810,7 +843,13 @@ class IlqrCandidateEvaluator:
         shape (the default); "table" -- they run in ONE plan on a device table of their parameters
         (IlqrPlan.set_model_table: the line search, forward pass and Jacobian chain of csrc/ilqr_table_kernels.hpp)
         whenever ``ilqr_table_decision`` allows it, the "shape" way otherwise (one_plan=False: refused).  ``last_models`` tells
-        what the last evaluate() did: {"path": "table" | "shape", "models": distinct models, "plans": plans built}."""
+        what the last evaluate() did: {"path": "table" | "shape", "models": distinct models, "plans": plans built}.
+        sindy_models: "single" -- one SINDy model per plan: a batch whose candidates carry different SINDy models is
+        refused by the library (the default); "table" -- such a batch runs in ONE plan on a device table of the models'
+        own handles (IlqrPlan.set_sindy_models: the line search and the Jacobians of
+        csrc/ilqr_sindy_table_kernels.hpp) whenever ``ilqr_sindy_table_decision`` allows it, the default way
+        otherwise; a plan whose table does not fit the kernel's LDS runs one plan per model (one_plan=False:
+        refused).  ``last_models`` then reads {"path": "sindy_table", "models": n, "plans": 1} or {"path": "model", ...}."""
         self.device_resident, self.max_slots, self.max_threads = bool(device_resident), int(max_slots), max(1, int(max_threads))
         self.one_plan = bool(one_plan)
         if mlp_models not in ("shape", "table"):
@@ -818,8 +857,14 @@ class IlqrCandidateEvaluator:
         if mlp_models == "table" and not self.one_plan:
             raise ValueError('mlp_models="table" puts every candidate into one plan: it needs one_plan=True')
         self.mlp_models = mlp_models
+        if sindy_models not in ("single", "table"):
+            raise ValueError('sindy_models must be "single" or "table", not %r' % (sindy_models,))
+        if sindy_models == "table" and not self.one_plan:
+            raise ValueError('sindy_models="table" puts every candidate into one plan: it needs one_plan=True')
+        self.sindy_models = sindy_models
         self.last_models = None
         self._table = False
+        self._sindy_table = False
         if not hasattr(model, "stage_into"):
             raise TypeError("needs a device-stageable model (autompc_amd.sysid.MLP)")
         if precision != "f64":
@@ -873,6 +918,31 @@ class IlqrCandidateEvaluator:
                         raise
                 finally:
                     _close_or_defer(self, opened)
+        if self.sindy_models == "table" and not self._sindy_table and not self._table:
+            ok, _why = ilqr_sindy_table_decision(candidates, self.model, self.precision, self.device,
+                                                 self.system.obs_dim, self.system.ctrl_dim)
+            if ok:
+                import copy
+                sub = copy.copy(self)
+                sub._sindy_table = True
+                opened = []
+                try:
+                    out = sub._evaluate(candidates, n_steps, init_obs, return_trajectories, int(max_iter), opened)
+                    self.last_lengths = sub.last_lengths
+                    if hasattr(sub, "last_iterations"):
+                        self.last_iterations = sub.last_iterations
+                    self.last_models = {"path": "sindy_table", "models": n_models, "plans": 1}
+                    return out
+                except _lib.AmpcError as e:
+                    if e.code != _lib.ILQR_TABLE_NO_FIT:      # (an entry's LDS need: every model gets a plan of its own)
+                        raise
+                finally:
+                    _close_or_defer(self, opened)
+                by_model = _by_model(candidates, self.model)
+                self.last_models = {"path": "model", "models": n_models, "plans": len(by_model)}
+                return CandidateEvaluator._evaluate_shape_groups(
+                    self, by_model, candidates, global_ids(index_offset, B),
+                    dict(n_steps=n_steps, init_obs=init_obs, return_trajectories=return_trajectories, max_iter=max_iter))
         shape_groups = _by_model_shape(candidates, self.model)
         self.last_models = {"path": "shape", "models": n_models,
                             "plans": 1 if shape_groups is None else len(shape_groups)}
@@ -921,19 +991,27 @@ class IlqrCandidateEvaluator:
         models, model_index = candidate_models(candidates, self.model)
         model_handles = []
         table = self._table                   # ONE plan on a table of the models' parameters: no handle per model
-        if not table and (len(models) > 1 or models[0] is not self.model):
+        sindy_table = self._sindy_table       # ONE plan on a table of the SINDy models' own handles
+        if sindy_table:
+            model_handles = [model_handle(m, self.device, self.precision, opened) for m in models]
+        elif not table and (len(models) > 1 or models[0] is not self.model):
             if not self.one_plan:
                 raise ValueError("candidates that carry their own model need the one-plan evaluator (one_plan=True)")
             model_handles = [model_handle(m, self.device, self.precision, opened) for m in models]
         for H, idx in groups.items():
             # (table: the handle gives the plan its dimensions, costs and sweep -- no shape-specialised kernel runs)
-            h = _lib.Handle(self.device, self.precision, jit=False if table else getattr(self.model, "jit_kernels", True))
+            h = _lib.Handle(self.device, self.precision,
+                            jit=False if (table or sindy_table) else getattr(self.model, "jit_kernels", True))
             opened.append(h)
             base = self.model
             if table:
                 # (the evaluator's own model when it is an MLP of the table's kind, else the first candidate's)
                 from ..evaluation.model_metrics import mlp_batch_key
                 base = self.model if mlp_batch_key(self.model, no) is not None else models[0]
+            if sindy_table:
+                # (the evaluator's own model when it is a SINDy, else the batch's first: the plan's dimensions and sweep)
+                from ..sysid.sindy import SINDy
+                base = self.model if isinstance(self.model, SINDy) else models[0]
             base.stage_into(h)
             blocks, term_goal = candidate_cost_blocks([candidates[i] for i in idx], self.goal, no, nu)
             h.set_cost_blocks(**blocks)
@@ -943,7 +1021,9 @@ class IlqrCandidateEvaluator:
             plan = _lib.IlqrPlan(h, slots, H, self.system.dt, cost_index=np.arange(slots),
                                  clip_to_bounds=self.bounded, terminal_goal=term_goal)
             opened.append(plan)
-            if model_handles:
+            if sindy_table:
+                plan.set_sindy_models(model_handles)
+            elif model_handles:
                 plan.set_models(model_handles)
             if table:
                 plan.set_model_table(models)

@@ -45,7 +45,8 @@ int ampc_version(void);   /* 100 * major + minor; 104: + ampc_mppi_run_legacy; 1
                            * 108: + ampc_kstep_errors; 109: + ampc_lqr_*; 110: + ampc_linfit_fit;
                            * 111: + ampc_kstep_errors_linear; 112: + ampc_kstep_errors_sindy;
                            * 113: + ampc_sindy_fit; 114: + ampc_lasso_fit; + ampc_stable_fit, + ampc_mlpfit_*, + ampc_kstep_errors_mlp,
-                           *      + ampc_mppi_plan_set_model_table, + ampc_ilqr_plan_set_model_table, + ampc_mppi_plan_set_sindy_models
+                           *      + ampc_mppi_plan_set_model_table, + ampc_ilqr_plan_set_model_table, + ampc_mppi_plan_set_sindy_models,
+                           *      + ampc_ilqr_plan_set_sindy_models
                            *      (no bump: callers detect them by their symbols) */
 int ampc_device_count(void);
 
@@ -507,6 +508,23 @@ int ampc_mppi_plan_set_sindy_models(ampc_mppi_plan* p, int n_models, ampc_handle
 int ampc_ilqr_plan_set_model_table(ampc_ilqr_plan* p, int n_models, const int* n_hidden, const int* dims,
                                    const int* activations, const double* const* weights,
                                    const double* const* biases, const double* const* norms, const int* on_device);
+
+/* SINDy models of ANY mix of feature libraries, coefficients and time modes in one f64 iLQR plan: the slot of a problem /
+ * episode runs on models[model_index[n]] of ampc_ilqr_solve_queue_var / ampc_ilqr_closed_loop_var (range-checked against
+ * this table; NULL, and the entries without that argument, run models[0]).  models[n_models]: handles staged with
+ * ampc_set_sindy; the call waits for their streams, builds a device array of their descriptors (pointers into the
+ * handles' buffers) and keeps the handles alive until n_models = 0 removes the table or the plan is destroyed.  The
+ * plan keeps its run-time-shape sweep; the line search and the Jacobians are csrc/ilqr_sindy_table_kernels.hpp's: per
+ * entry a lane-spread body (a product table, <= 8 states, the program staged in LDS) or one thread per line-search
+ * row, chosen from the entry alone.
+ * Refused with a message: NULL arguments; an f32 plan; a plan handle or a model handle without a SINDy model; models
+ * whose state / control dimensions, precision or device are not the plan handle's; an observation dimension other
+ * than the state dimension; a plan that holds ampc_ilqr_plan_set_models handles or an MLP table (and those two calls
+ * on a plan that holds this table); a model_index past the table; and -- return code -3 instead of -1 -- an entry
+ * whose LDS need exceeds 160 KB.  A call that replaces a table takes the old one out first and installs the new one
+ * only once it is complete.  Deterministic: a problem's results are the same bits alone, in any plan, in any slot, at
+ * any position of the table.  (Added without a version bump: callers detect it by its symbol.) */
+int ampc_ilqr_plan_set_sindy_models(ampc_ilqr_plan* p, int n_models, ampc_handle* const* models);
 
 /* simulate() with IterativeLQR controllers, device resident (utils/simulation.py:44-63 as eval_cfg drives it,
  * pipeline_tuner.py:222-231; IterativeLQR.run, ilqr.py:267-295: every control step is a full solve from a zero
