@@ -24,7 +24,8 @@ class AmpcError(RuntimeError):
 
 
 MPPI_TABLE_NO_FIT = -3     # ampc_mppi_plan_set_model_table: the table kernel's LDS map exceeds 160 KB for this plan
-#                            (ampc_mppi_plan_set_sindy_models: an entry's LDS need does)
+#                            (ampc_mppi_plan_set_sindy_models: an entry's LDS need does;
+#                             ampc_mppi_plan_set_linear_models: the widest entry's does)
 ILQR_TABLE_NO_FIT = -3     # ampc_ilqr_plan_set_model_table: the same for the table iteration kernel
 #                            (ampc_ilqr_plan_set_sindy_models: an entry's LDS need does)
 
@@ -110,6 +111,9 @@ SIGNATURES = {
     "ampc_ilqr_plan_set_models": (c_int, [c_void_p, c_int, POINTER(c_void_p)]),
     "ampc_mppi_plan_set_models": (c_int, [c_void_p, c_int, POINTER(c_void_p), _ip]),
     "ampc_mppi_plan_set_sindy_models": (c_int, [c_void_p, c_int, POINTER(c_void_p), _ip]),
+    "ampc_mppi_plan_set_linear_models": (c_int, [c_void_p, c_int, POINTER(c_void_p), _ip, _ip, _ip, _ip, _dp]),
+    "ampc_mppi_closed_loop_linear": (c_int, [c_void_p, c_void_p, _dp, _dp, c_int, c_uint64, _dp, c_int, _ip, _dp, _dp,
+                                             _dp, _dp]),
     "ampc_ilqr_plan_set_sindy_models": (c_int, [c_void_p, c_int, POINTER(c_void_p)]),
     "ampc_mppi_plan_set_model_table": (c_int, [c_void_p, c_int, _ip, _ip, _ip, POINTER(c_void_p), POINTER(c_void_p),
                                                POINTER(c_void_p), _ip, _ip]),
@@ -483,7 +487,7 @@ class MppiPlan:
         return a
 
     def upload(self, x0=None, act_seq=None, eps=None):
-        x0 = self._flat(x0, self.B * self.handle.nx, "x0")
+        x0 = self._flat(x0, getattr(self, "_linear_x0", None) or self.B * self.handle.nx, "x0")
         act_seq = self._flat(act_seq, self.sum_hnu, "act_seq")
         eps = self._flat(eps, self.sum_nhnu, "eps")
         check(self.lib.ampc_mppi_upload(self._p, dptr(x0), dptr(act_seq), dptr(eps)))
@@ -600,6 +604,70 @@ class MppiPlan:
         mi = None if not hs else np.ascontiguousarray(np.broadcast_to(np.asarray(model_index, dtype=np.int32), (self.B,)))
         check(self.lib.ampc_mppi_plan_set_sindy_models(self._p, len(hs), arr, iptr(mi)))
         self._sindy_models = hs
+
+    def set_linear_models(self, handles, model_index, rules=None, lifts=None):
+        """Linear models of mixed state dimension per problem (ampc_mppi_plan_set_linear_models): `handles` hold linear
+        models (Handle.set_linear, either staging form) of the plan handle's controls, precision and device,
+        model_index [B] names each problem's.  ``upload``'s x0 is then ragged: the concatenation of the problems' states
+        (``linear_x0_sizes``), in plan order.  rules [n_models]: the closed loop's controller-state rule per model (0 the
+        observation, 1 the ARX shift, 2 a lift -- ``LqrPlan.set_loop``'s meaning); None: plain solves only.  lifts
+        [n_models]: None or (kinds, params) for a rule-2 model.  None / empty handles: removes the table.  A refusal
+        raises AmpcError; its ``code`` is MPPI_TABLE_NO_FIT when the widest entry's LDS map exceeds 160 KB."""
+        hs = list(handles or [])
+        arr = (c_void_p * max(len(hs), 1))(*[h._h for h in hs])
+        if not hs:
+            check(self.lib.ampc_mppi_plan_set_linear_models(self._p, 0, arr, None, None, None, None, None))
+            self._linear_models, self._linear_x0, self.linear_x0_sizes = [], None, None
+            return
+        mi = np.ascontiguousarray(np.broadcast_to(np.asarray(model_index, dtype=np.int32), (self.B,)))
+        ru = nb = lk = lp = None
+        if rules is not None:
+            ru = np.ascontiguousarray(rules, dtype=np.int32)
+            if ru.shape != (len(hs),):
+                raise ValueError("rules has %d entries, expected one per model (%d)" % (ru.size, len(hs)))
+            lifts = list(lifts) if lifts is not None else [None] * len(hs)
+            nb = np.zeros(len(hs), dtype=np.int32)
+            kinds, params = [], []
+            for i, lf in enumerate(lifts):
+                if ru[i] == 2:
+                    if lf is None:
+                        raise ValueError("model %d has rule 2 (lift) and no lift" % i)
+                    nb[i] = len(lf[0])
+                    kinds.extend(int(k) for k in lf[0])
+                    params.extend(float(q) for q in lf[1])
+            lk = np.ascontiguousarray(kinds + [0], dtype=np.int32)
+            lp = as_f64(params + [0.0])
+        check(self.lib.ampc_mppi_plan_set_linear_models(self._p, len(hs), arr, iptr(mi), iptr(ru), iptr(nb), iptr(lk),
+                                                        dptr(lp)))
+        self._linear_models = hs            # (kept alive on this side as well)
+        ok = all(0 <= int(i) < len(hs) for i in mi)
+        self.linear_x0_sizes = np.array([hs[int(i)].nx for i in mi], dtype=np.int64) if ok else None
+        self._linear_x0 = int(self.linear_x0_sizes.sum())
+
+    def closed_loop_linear(self, surrogate, n_steps, init_states=None, init_sim=None, terms=None, seed=0, eps_all=None,
+                           return_trajectories=True):
+        """simulate() for every problem of a plan on a table of linear models (ampc_mppi_closed_loop_linear), device
+        resident: per control step every controller state follows its model's rule, one rollout launch solves every
+        problem, `surrogate` advances.  init_states: the concatenated model states (each model's traj_to_state of the
+        one-row trajectory), init_sim [B, surrogate nx]; both None: continue from where the previous call stopped.
+        Returns (scores or None, traj_obs [B, n_steps+1, surrogate nx] or None, traj_ctrls or None)."""
+        nu, snx = self.handle.nu, surrogate.nx
+        if (init_states is None) != (init_sim is None):
+            raise ValueError("init_states and init_sim are given together or not at all")
+        init_states = self._flat(init_states, getattr(self, "_linear_x0", None) or 0, "init_states")
+        init_sim = self._flat(init_sim, self.B * snx, "init_sim")
+        eps_all = self._flat(eps_all, n_steps * self.sum_nhnu, "eps_all")
+        kinds = params = scores = None
+        if terms is not None:
+            kinds = np.ascontiguousarray(terms[0], dtype=np.int32)
+            params = as_f64(terms[1])
+            scores = np.empty(self.B)
+        obs = np.empty((self.B, n_steps + 1, snx)) if return_trajectories else None
+        ctl = np.empty((self.B, n_steps + 1, nu)) if return_trajectories else None
+        check(self.lib.ampc_mppi_closed_loop_linear(
+            self._p, surrogate._h, dptr(init_states), dptr(init_sim), int(n_steps), int(seed), dptr(eps_all),
+            0 if kinds is None else len(kinds), iptr(kinds), dptr(params), dptr(scores), dptr(obs), dptr(ctl)))
+        return scores, obs, ctl
 
     def solve(self):
         check(self.lib.ampc_mppi_solve(self._p))

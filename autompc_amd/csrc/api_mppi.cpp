@@ -3,6 +3,7 @@
 // Part of the C ABI of libautompc_hip.so (include/autompc_hip.h); see api.cpp for the map of the translation units.
 // Built with hipcc for gfx950 only.
 #include "host_common.hpp"
+#include "mppi_linear_table_kernels.hpp"
 #include "legacy_rng_kernels.hpp"      // (non-template kernels: this translation unit only)
 #include <link.h>                      // dl_iterate_phdr: the C library's log() tables (host_log_mode)
 #include <atomic>
@@ -94,7 +95,10 @@ template <typename T> static int plan_build(ampc_mppi_plan* p) {
   // a table of MLP models of mixed shapes (ampc_mppi_plan_set_model_table): 16-row tiles of mppi_rollout_table_kernel,
   // its own LDS map, no static shape and no plugin
   const bool table = p->table_n > 0;
-  if (!table && sizeof(T) == 8 && h->has_mlp && q4_supported(m.hpad, m.n_hidden, m.nxp, m.k1p)) {
+  // a table of linear models of mixed state dimension (ampc_mppi_plan_set_linear_models): 16-row tiles of
+  // linear_table_rollout_kernel, the [x | u] region of the widest entry, no static shape and no plugin
+  const bool lint = p->lint_n > 0;
+  if (!table && !lint && sizeof(T) == 8 && h->has_mlp && q4_supported(m.hpad, m.n_hidden, m.nxp, m.k1p)) {
     long long tiles16 = 0;
     for (int b = 0; b < p->B; ++b) tiles16 += (p->N[b] + 15) / 16;
     const int mode = env_int("AMPC_QUAD", -1);
@@ -109,6 +113,10 @@ template <typename T> static int plan_build(ampc_mppi_plan* p) {
   if (p->quad) {
     p->mt = 0;
   } else if (table) {
+    p->mt = 1;
+  } else if (lint) {
+    REQUIRE(p->forced_mt <= 1, "ampc_mppi_plan_set_geometry: a plan that holds a table of linear models "
+                               "(ampc_mppi_plan_set_linear_models) rolls out in 16-row tiles: tile_rows must be 0 or 16");
     p->mt = 1;
   } else if (h->has_sindy) {
     p->mt = 4;
@@ -136,6 +144,10 @@ template <typename T> static int plan_build(ampc_mppi_plan* p) {
   } else if (table) {
     std::memset(&p->L, 0, sizeof(p->L));
     p->L.extra = mppi_table_lds_base();            // act[2][16][257], xu[16][81], norm[288] (mppi_table_kernels.hpp)
+  } else if (lint) {
+    std::memset(&p->L, 0, sizeof(p->L));
+    p->L.xu_stride = lin_xs(p->lint_kp, (int)sizeof(T));
+    p->L.extra = lin_lds_base(p->lint_kp, (int)sizeof(T));      // [x | u] twice, at the widest entry's stride
   } else if (h->has_sindy) {
     std::memset(&p->L, 0, sizeof(p->L));
     p->L.extra = (2 * nx + nu + h->s_ntab) * 64;   // per-thread columns: [x|u], next x, value table
@@ -160,7 +172,7 @@ template <typename T> static int plan_build(ampc_mppi_plan* p) {
   {  // fused update: keep the tile's clipped noise [max_h][M][nu] (+ 2M reduction slots) in LDS
     const int e0 = round_up(p->lds_aseq + p->max_h * nu, 4);
     const size_t bytes = ((size_t)e0 + (size_t)p->max_h * M * nu + 2 * M) * sizeof(T);
-    if (!h->has_sindy && bytes <= kLdsLimit && env_int("AMPC_FUSED_UPDATE", 1) != 0) {
+    if ((!h->has_sindy || lint) && bytes <= kLdsLimit && env_int("AMPC_FUSED_UPDATE", 1) != 0) {
       p->lds_eps = e0;
       p->lds_red = e0 + p->max_h * M * nu;
       p->lds_bytes = bytes;
@@ -171,7 +183,7 @@ template <typename T> static int plan_build(ampc_mppi_plan* p) {
   p->static_shape = -1;
   p->jit = nullptr;
   // (indicator cost terms live in the run-time-shape kernels only: mppi_kernels.hpp)
-  const bool ext = h->n_ind > 0 || table;
+  const bool ext = h->n_ind > 0 || table || lint;
   if (ext) {
   } else if (p->quad && env_int("AMPC_STATIC", 1) != 0) {          // (the four-row kernel has one LDS map)
     int sid = static_shape_of<T>(h, m);
@@ -217,7 +229,9 @@ template <typename T> static int plan_build(ampc_mppi_plan* p) {
   HIP_OK(hipMemcpy(p->probs.p, pr.data(), pr.size() * sizeof(MppiProblem<T>), hipMemcpyHostToDevice));
   HIP_OK(p->tile_prob.reserve(tile_prob.size() * sizeof(int)));
   HIP_OK(hipMemcpy(p->tile_prob.p, tile_prob.data(), tile_prob.size() * sizeof(int), hipMemcpyHostToDevice));
-  HIP_OK(p->x0.reserve((size_t)p->B * nx * sizeof(T)));
+  // (a table of linear models: x0 is ragged, problem b owns its entry's state dimension)
+  const size_t x0_elems = lint ? (size_t)p->lint_sum_nx : (size_t)p->B * nx;
+  HIP_OK(p->x0.reserve(x0_elems * sizeof(T)));
   for (int i = 0; i < 2; ++i) {
     HIP_OK(p->act[i].reserve((size_t)p->sum_hnu * sizeof(T)));
     HIP_OK(hipMemset(p->act[i].p, 0, (size_t)p->sum_hnu * sizeof(T)));
@@ -240,7 +254,8 @@ template <typename T> static int plan_build(ampc_mppi_plan* p) {
     p->fused_combine = p->quad && p->lds_eps >= 0 && env_int("AMPC_FUSED_COMBINE", 0) != 0 &&
                        (size_t)(2 * max_tiles + 256) * sizeof(T) <= p->lds_bytes;
   }
-  HIP_OK(hipMemset(p->x0.p, 0, (size_t)p->B * nx * sizeof(T)));
+  HIP_OK(hipMemset(p->x0.p, 0, x0_elems * sizeof(T)));
+  p->lint_cont = false;
   return 0;
 }
 
@@ -314,6 +329,9 @@ extern "C" int ampc_mppi_plan_destroy(ampc_mppi_plan* p) {
   p->mlp_tab.release(); p->tile_order.release();
   p->table_models.release(); p->table_stage.release();
   p->sindy_tab.release();
+  p->lint_buf.release(); p->lint_tab.release(); p->lint_xoff.release(); p->lint_desc.release();
+  p->lint_prog.release(); p->lint_uprev.release();
+  for (ampc_handle* mh : p->lint_models) handle_release(mh);
   for (ampc_handle* mh : p->sindy_models) handle_release(mh);
   for (ampc_handle* mh : p->models) handle_release(mh);
   for (hipEvent_t e : p->ev) (void)hipEventDestroy(e);
@@ -357,6 +375,8 @@ extern "C" int ampc_mppi_plan_set_models(ampc_mppi_plan* p, int n_models, ampc_h
                            "(ampc_mppi_plan_set_sindy_models); remove it first");
   REQUIRE(p->table_n == 0, "ampc_mppi_plan_set_models: the plan holds a table of MLP models of mixed shapes "
                            "(ampc_mppi_plan_set_model_table); remove it first");
+  REQUIRE(p->lint_n == 0, "ampc_mppi_plan_set_models: the plan holds a table of linear models "
+                          "(ampc_mppi_plan_set_linear_models); remove it first");
   for (int i = 0; i < n_models; ++i)
     if (int rc = check_same_shape(p->h, models[i], "ampc_mppi_plan_set_models")) return rc;
   for (int b = 0; b < p->B; ++b)
@@ -377,7 +397,9 @@ template <typename T>
 static int mppi_upload_impl(ampc_mppi_plan* p, const double* x0, const double* act_seq,
                             const double* eps) {
   ampc_handle* h = p->h;
-  if (x0) HIP_OK(upload_converted<T>(p->x0.p, x0, (size_t)p->B * h->nx, h->stream));
+  // (a table of linear models: x0 is the concatenation of the problems' states, ampc_mppi_plan_set_linear_models)
+  if (x0) HIP_OK(upload_converted<T>(p->x0.p, x0, p->lint_n > 0 ? (size_t)p->lint_sum_nx : (size_t)p->B * h->nx, h->stream));
+  if (x0) p->lint_cont = false;
   if (act_seq) HIP_OK(upload_converted<T>(p->act[p->cur].p, act_seq, (size_t)p->sum_hnu, h->stream));
   if (eps) {
     legacy_predraw_drop(p);
@@ -851,11 +873,27 @@ extern "C" int ampc_mppi_legacy_normal(ampc_mppi_plan* p, const uint32_t* key, i
              : legacy_normal_impl<float>(p, key, pos, has_gauss, cached, key_out, pos_out, has_gauss_out, cached_out);
 }
 
+// LDS bytes of a plan on a table of linear models without the fused update's noise region (plan_build): the [x | u]
+// ping-pong of the widest entry, cost block + bounds, shifted sequence
+static size_t mppi_linear_table_lds_bytes(int kp, int cost_stride, int nu, int max_h, int esz) {
+  return ((size_t)round_up(lin_lds_base(kp, esz) + cost_stride + 3 * nu, 4) + (size_t)max_h * nu) * esz;
+}
+
 extern "C" int ampc_mppi_plan_set_geometry(ampc_mppi_plan* p, int tile_rows, int horizon_cap) {
   REQUIRE(p, "ampc_mppi_plan_set_geometry: NULL plan");
   REQUIRE(tile_rows == 0 || tile_rows == 4 || tile_rows == 16 || tile_rows == 32 || tile_rows == 64,
           "ampc_mppi_plan_set_geometry: tile_rows must be 0 (automatic), 4, 16, 32 or 64");
   REQUIRE(horizon_cap >= 0, "ampc_mppi_plan_set_geometry: horizon_cap < 0");
+  REQUIRE(p->lint_n == 0 || tile_rows == 0 || tile_rows == 16,
+          "ampc_mppi_plan_set_geometry: a plan that holds a table of linear models (ampc_mppi_plan_set_linear_models) rolls "
+          "out in 16-row tiles: tile_rows must be 0 or 16");
+  if (p->lint_n > 0) {
+    int mh = horizon_cap;
+    for (int hb : p->H) mh = hb > mh ? hb : mh;
+    mh = p->max_h > mh ? p->max_h : mh;
+    REQUIRE(mppi_linear_table_lds_bytes(p->lint_kp, p->h->cost_stride, p->h->nu, mh, (int)p->h->esz()) <= kLdsLimit,
+            "ampc_mppi_plan_set_geometry: this horizon cap needs more than 160 KB of LDS with the widest linear model");
+  }
   REQUIRE(p->table_n == 0 || tile_rows == 0 || tile_rows == 16,
           "ampc_mppi_plan_set_geometry: a plan that holds a table of MLP models (ampc_mppi_plan_set_model_table) rolls "
           "out in 16-row tiles: tile_rows must be 0 or 16");
@@ -906,7 +944,7 @@ void kstep_mlp_pack_model(void* dst, int n_layers, int act, const int* dims, con
 // (ampc_mppi_plan_set_geometry).
 static int mppi_table_rebuild(ampc_mppi_plan* p) {
   p->forced_quad = false;
-  p->forced_mt = p->table_n > 0 ? 1 : p->forced_mt;
+  p->forced_mt = (p->table_n > 0 || p->lint_n > 0) ? 1 : p->forced_mt;
   p->lds_eps = -1;
   p->lds_red = 0;
   const bool redraw = p->eps_from_generator;
@@ -934,6 +972,8 @@ extern "C" int ampc_mppi_plan_set_model_table(ampc_mppi_plan* p, int n_models, c
   }
   if (p->sindy_n > 0)
     return mppi_table_fail("the plan holds a table of SINDy models (ampc_mppi_plan_set_sindy_models); remove it first");
+  if (p->lint_n > 0)
+    return mppi_table_fail("the plan holds a table of linear models (ampc_mppi_plan_set_linear_models); remove it first");
   MppiTablePlanView v;
   v.f64 = h->precision == AMPC_F64; v.has_mlp = h->has_mlp; v.nx = h->nx; v.nu = h->nu; v.obs_dim = h->obs_dim;
   v.n_ind = h->n_ind; v.lift_n = p->lift_n; v.n_shape_models = (int)p->models.size();
@@ -1050,6 +1090,7 @@ extern "C" int ampc_mppi_plan_set_sindy_models(ampc_mppi_plan* p, int n_models, 
     return h->precision == AMPC_F64 ? mppi_set_noise_ids_impl<double>(p) : mppi_set_noise_ids_impl<float>(p);
   }
   REQUIRE(n_models >= 1 && models && model_index, w + ": NULL argument");
+  REQUIRE(p->lint_n == 0, w + ": the plan holds a table of linear models (ampc_mppi_plan_set_linear_models); remove it first");
   REQUIRE(h->has_sindy, w + ": the plan handle's model is not a SINDy model (ampc_set_sindy)");
   REQUIRE(p->lift_n == 0, w + ": the plan has a state lift; the SINDy rollout runs on the observation");
   REQUIRE(p->models.empty(), w + ": the plan holds per-problem models of one shape (ampc_mppi_plan_set_models); remove "
@@ -1325,6 +1366,8 @@ extern "C" int ampc_mppi_run_legacy(ampc_mppi_plan* p, const double* x0, const d
                                     double* u) {
   REQUIRE(p && x0 && u && key && key_out && pos_out && has_gauss_out && cached_out,
           "ampc_mppi_run_legacy: NULL argument");
+  REQUIRE(p->lint_n == 0, "ampc_mppi_run_legacy: the plan holds a table of linear models (ampc_mppi_plan_set_linear_models): "
+                          "its x0 is ragged, not [B][nx]; use ampc_mppi_upload and ampc_mppi_solve");
   REQUIRE(pos >= 0 && pos <= kMtN, "ampc_mppi_run_legacy: pos must be in [0, 624]");
   REQUIRE(p->sum_nhnu > 0, "ampc_mppi_run_legacy: empty plan");
   HIP_OK(hipSetDevice(p->h->device));
@@ -1336,6 +1379,8 @@ extern "C" int ampc_mppi_run_legacy(ampc_mppi_plan* p, const double* x0, const d
 extern "C" int ampc_mppi_run(ampc_mppi_plan* p, const double* x0, const double* act_seq, int noise,
                              uint64_t seed, uint64_t stream, double* u) {
   REQUIRE(p && x0 && u, "ampc_mppi_run: NULL argument");
+  REQUIRE(p->lint_n == 0, "ampc_mppi_run: the plan holds a table of linear models (ampc_mppi_plan_set_linear_models): "
+                          "its x0 is ragged, not [B][nx]; use ampc_mppi_upload and ampc_mppi_solve");
   REQUIRE(noise == 0 || noise == 1, "ampc_mppi_run: noise must be 0 (resident) or 1 (Philox)");
   HIP_OK(hipSetDevice(p->h->device));
   return p->h->precision == AMPC_F64 ? mppi_run_impl<double>(p, x0, act_seq, noise, seed, stream, u)
@@ -1344,6 +1389,8 @@ extern "C" int ampc_mppi_run(ampc_mppi_plan* p, const double* x0, const double* 
 
 extern "C" int ampc_mppi_set_x0_dev(ampc_mppi_plan* p, const void* x0_dev) {
   REQUIRE(p && x0_dev, "ampc_mppi_set_x0_dev: NULL argument");
+  REQUIRE(p->lint_n == 0, "ampc_mppi_set_x0_dev: the plan holds a table of linear models (ampc_mppi_plan_set_linear_models): "
+                          "its x0 is ragged, not [B][nx]; use ampc_mppi_upload");
   HIP_OK(hipSetDevice(p->h->device));
   HIP_OK(hipMemcpyAsync(p->x0.p, x0_dev, (size_t)p->B * p->h->nx * p->h->esz(),
                         hipMemcpyDeviceToDevice, p->h->stream));
@@ -1569,6 +1616,8 @@ static int closed_loop_impl(ampc_mppi_plan* p, ampc_handle* sur, const double* i
 // Which surrogate a plan's closed loop accepts: the controller model's dimensions -- or, with a state
 // lift, any model with the same controls whose state starts with the observation.
 static int closed_loop_check(const ampc_mppi_plan* p, const ampc_handle* sur, const char* who) {
+  REQUIRE(p->lint_n == 0, std::string(who) + ": the plan holds a table of linear models (ampc_mppi_plan_set_linear_models); "
+                                             "its closed loop is ampc_mppi_closed_loop_linear");
   const bool ok = sur->has_model() && sur->nu == p->h->nu &&
                   (p->lift_n > 0 ? sur->nx >= p->h->obs_dim : sur->nx == p->h->nx);
   if (!ok) return fail(std::string(who) + ": surrogate model must have the controller model's dimensions (with a "
@@ -1582,6 +1631,8 @@ extern "C" int ampc_mppi_plan_set_state_lift(ampc_mppi_plan* p, int n_basis, con
   REQUIRE(p, "ampc_mppi_plan_set_state_lift: NULL plan");
   if (n_basis <= 0) { p->lift_n = 0; return 0; }
   REQUIRE(kinds && params, "ampc_mppi_plan_set_state_lift: NULL argument");
+  REQUIRE(p->lint_n == 0, "ampc_mppi_plan_set_state_lift: the plan holds a table of linear models "
+                          "(ampc_mppi_plan_set_linear_models), whose lifts are per model");
   REQUIRE(p->h->obs_dim >= 1 && n_basis * p->h->obs_dim == p->h->nx,
           "ampc_mppi_plan_set_state_lift: n_basis * obs_dim must be the model's state dimension");
   std::vector<double> prog(2 * (size_t)n_basis);
@@ -1631,6 +1682,270 @@ extern "C" int ampc_mppi_closed_loop_scored(ampc_mppi_plan* p, ampc_handle* surr
   return p->h->precision == AMPC_F64
              ? closed_loop_impl<double>(p, sur, init_obs, n_steps, seed, eps_all, traj_obs, traj_ctrls, &sp, scores)
              : closed_loop_impl<float>(p, sur, init_obs, n_steps, seed, eps_all, traj_obs, traj_ctrls, &sp, scores);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Linear models of mixed state dimension in one plan (mppi_linear_table_kernels.hpp)
+// ---------------------------------------------------------------------------------------------
+struct LintState {            // what a replacing call puts back when the new table cannot be installed
+  int n, kp; long long sum_nx; bool loop;
+  std::vector<ampc_handle*> models;
+  std::vector<int> nx, rule, nbasis, lift_off, model_idx;
+  std::vector<double> prog;
+};
+static LintState lint_take(ampc_mppi_plan* p) {
+  LintState o{p->lint_n, p->lint_kp, p->lint_sum_nx, p->lint_loop, {}, {}, {}, {}, {}, p->model_idx, {}};
+  o.models.swap(p->lint_models); o.nx.swap(p->lint_nx); o.rule.swap(p->lint_rule); o.nbasis.swap(p->lint_nbasis);
+  o.lift_off.swap(p->lint_lift_off); o.prog.swap(p->lint_prog_host);
+  p->lint_n = 0; p->lint_kp = 0; p->lint_sum_nx = 0; p->lint_loop = false; p->lint_cont = false;
+  p->model_idx.clear();
+  return o;
+}
+static void lint_put(ampc_mppi_plan* p, LintState& o) {
+  p->lint_n = o.n; p->lint_kp = o.kp; p->lint_sum_nx = o.sum_nx; p->lint_loop = o.loop; p->lint_cont = false;
+  p->lint_models.swap(o.models); p->lint_nx.swap(o.nx); p->lint_rule.swap(o.rule); p->lint_nbasis.swap(o.nbasis);
+  p->lint_lift_off.swap(o.lift_off); p->lint_prog_host.swap(o.prog);
+  p->model_idx = o.model_idx;
+}
+
+// Pack the entries (fragments of [A | B] as set_linear_wide lays them out, then the plain rows) from the handles' exact
+// f64 copies, build the LinDev table, the ragged x0 offsets and the closed loop's rule records, and upload them.
+template <typename T> static int lint_upload(ampc_mppi_plan* p) {
+  const ampc_handle* h = p->h;
+  const int nu = h->nu, n = p->lint_n;
+  std::vector<size_t> off(n + 1, 0);
+  for (int i = 0; i < n; ++i) {
+    const int nx = p->lint_nx[i], k = nx + nu, ntile = round_up(nx, 16) / 16, ksn = round_up(k, 4) / 4;
+    off[i + 1] = off[i] + (size_t)ntile * ksn * 64 + (size_t)round_up(nx * k, 4);
+  }
+  std::vector<T> buf(off[n], T(0));
+  HIP_OK(p->lint_buf.reserve(buf.size() * sizeof(T)));
+  std::vector<LinDev<T>> tab(n);
+  for (int i = 0; i < n; ++i) {
+    const std::vector<double>& ab = p->lint_models[i]->lin_ab_host;
+    const int nx = p->lint_nx[i], k = nx + nu, nxp = round_up(nx, 16), kp = round_up(k, 4), ntile = nxp / 16, ksn = kp / 4;
+    T* wf = buf.data() + off[i];
+    auto Mat = [&](int row, int col) -> double { return (row >= nx || col >= k) ? 0.0 : ab[(size_t)row * k + col]; };
+    for (int nt = 0; nt < ntile; ++nt)
+      for (int ks = 0; ks < ksn; ++ks)
+        for (int l = 0; l < 64; ++l) wf[((size_t)nt * ksn + ks) * 64 + l] = (T)Mat(16 * nt + (l & 15), 4 * ks + (l >> 4));
+    T* plain = wf + (size_t)ntile * ksn * 64;
+    for (size_t e = 0; e < (size_t)nx * k; ++e) plain[e] = (T)ab[e];
+    LinDev<T>& m = tab[i];
+    m.nx = nx; m.nu = nu; m.nxp = nxp; m.kp = kp; m.ntile = ntile; m.ksn = ksn;
+    m.wf = (const T*)p->lint_buf.p + off[i];
+    m.plain = m.wf + (size_t)ntile * ksn * 64;
+    m.jp = nullptr; m.ldj = 0;               // (the iLQR sweep's padded Jacobian: not part of an MPPI table)
+  }
+  std::vector<int> xoff(p->B);
+  std::vector<LinCtrlDesc> desc(p->B);
+  int x = 0;
+  for (int b = 0; b < p->B; ++b) {
+    const int mi = p->model_idx[b];
+    xoff[b] = x;
+    desc[b] = LinCtrlDesc{p->lint_nx[mi], p->lint_loop ? p->lint_rule[mi] : 0, p->lint_loop ? p->lint_nbasis[mi] : 0, mi,
+                          x, p->lint_loop ? p->lint_lift_off[mi] : 0};
+    x += p->lint_nx[mi];
+  }
+  std::vector<T> prog(p->lint_prog_host.begin(), p->lint_prog_host.end());
+  HIP_OK(p->lint_tab.reserve(tab.size() * sizeof(LinDev<T>)));
+  HIP_OK(p->lint_xoff.reserve(xoff.size() * sizeof(int)));
+  HIP_OK(p->lint_desc.reserve(desc.size() * sizeof(LinCtrlDesc)));
+  HIP_OK(p->lint_prog.reserve((prog.size() + 2) * sizeof(T)));
+  HIP_OK(p->lint_uprev.reserve((size_t)p->B * nu * sizeof(T)));
+  HIP_OK(hipMemcpy(p->lint_buf.p, buf.data(), buf.size() * sizeof(T), hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(p->lint_tab.p, tab.data(), tab.size() * sizeof(LinDev<T>), hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(p->lint_xoff.p, xoff.data(), xoff.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(p->lint_desc.p, desc.data(), desc.size() * sizeof(LinCtrlDesc), hipMemcpyHostToDevice));
+  if (!prog.empty()) HIP_OK(hipMemcpy(p->lint_prog.p, prog.data(), prog.size() * sizeof(T), hipMemcpyHostToDevice));
+  return 0;
+}
+
+extern "C" int ampc_mppi_plan_set_linear_models(ampc_mppi_plan* p, int n_models, ampc_handle* const* models,
+                                                const int* model_index, const int* rules, const int* n_basis,
+                                                const int* lift_kinds, const double* lift_params) {
+  static const char* const who = "ampc_mppi_plan_set_linear_models";
+  const std::string w(who);
+  REQUIRE(p, w + ": NULL plan");
+  ampc_handle* h = p->h;
+  HIP_OK(hipSetDevice(h->device));
+  if (n_models == 0) {                               // back to the handle's own model and the automatic geometry
+    if (p->lint_n == 0) return 0;
+    HIP_OK(hipStreamSynchronize(h->stream));
+    LintState old = lint_take(p);
+    for (ampc_handle* mh : old.models) handle_release(mh);
+    p->forced_mt = 0;
+    return mppi_table_rebuild(p);
+  }
+  REQUIRE(n_models >= 1 && models && model_index, w + ": NULL argument");
+  REQUIRE(h->lin_n > 0 && h->lin_n == h->nx, w + ": the plan handle's model is not a linear model (ampc_set_linear)");
+  REQUIRE(p->lift_n == 0, w + ": the plan has a state lift (ampc_mppi_plan_set_state_lift); lifts of a table are per model");
+  REQUIRE(p->models.empty(), w + ": the plan holds per-problem models of one shape (ampc_mppi_plan_set_models); remove "
+                                 "them first");
+  REQUIRE(p->table_n == 0, w + ": the plan holds a table of MLP models (ampc_mppi_plan_set_model_table); remove it first");
+  REQUIRE(p->sindy_n == 0, w + ": the plan holds a table of SINDy models (ampc_mppi_plan_set_sindy_models); remove it first");
+  const int no = h->obs_dim;
+  int n_lift = 0, kp = 0;
+  std::vector<int> lift_off(n_models, 0);
+  for (int i = 0; i < n_models; ++i) {
+    const ampc_handle* m = models[i];
+    REQUIRE(m != nullptr, w + ": NULL model handle");
+    REQUIRE(m->lin_n > 0 && m->lin_n == m->nx && (int)m->lin_ab_host.size() == m->nx * (m->nx + m->nu),
+            w + ": a model handle holds no linear model (ampc_set_linear)");
+    REQUIRE(m->device == h->device && m->precision == h->precision, w + ": models must share the plan's device and precision");
+    REQUIRE(m->nu == h->nu, w + ": models must have the plan handle's control dimension");
+    REQUIRE(m->nx >= no, w + ": a model has fewer states than the cost's observation (nx < obs_dim)");
+    kp = std::max(kp, round_up(m->nx + m->nu, 4));
+    if (!rules) continue;
+    REQUIRE(rules[i] >= 0 && rules[i] <= 2, w + ": rule must be 0 observation, 1 ARX shift, 2 lift");
+    REQUIRE(rules[i] != 0 || m->nx == no, w + ": rule 0 (state = observation) needs nx == obs_dim");
+    if (rules[i] == 2) {
+      REQUIRE(n_basis && lift_kinds && lift_params, w + ": rule 2 needs n_basis, lift_kinds and lift_params");
+      REQUIRE(n_basis[i] >= 1 && no >= 1 && n_basis[i] * no == m->nx,
+              w + ": n_basis * obs_dim must be the model's state dimension");
+      lift_off[i] = 2 * n_lift;
+      for (int k = n_lift; k < n_lift + n_basis[i]; ++k) {
+        REQUIRE(lift_kinds[k] >= 0 && lift_kinds[k] <= 3, w + ": lift kind must be 0 identity, 1 power, 2 sin, 3 cos");
+        REQUIRE(lift_kinds[k] != 1 || (lift_params[k] >= 0 && lift_params[k] <= 64 && lift_params[k] == std::floor(lift_params[k])),
+                w + ": powers must be integers in 0..64");
+      }
+      n_lift += n_basis[i];
+    }
+  }
+  for (int b = 0; b < p->B; ++b)
+    REQUIRE(model_index[b] >= 0 && model_index[b] < n_models, w + ": model_index out of range");
+  if (mppi_linear_table_lds_bytes(kp, h->cost_stride, h->nu, p->max_h, (int)h->esz()) > kLdsLimit) {
+    g_err = w + ": the widest model's [x | u] rows (2 x 16 x (nx + nu)), cost block and horizon cap need more than 160 KB "
+                "of LDS";
+    return -3;
+  }
+  // (a running solve may read the table being replaced)
+  HIP_OK(hipStreamSynchronize(h->stream));
+  // the old table out first; the new one in only once it is complete
+  LintState old = lint_take(p);
+  const int old_mt = p->forced_mt;
+  const bool old_quad = p->forced_quad;
+  p->lint_n = n_models; p->lint_kp = kp; p->lint_loop = rules != nullptr;
+  p->lint_models.assign(models, models + n_models);
+  p->model_idx.assign(model_index, model_index + p->B);
+  for (int i = 0, k = 0; i < n_models; ++i) {
+    p->lint_nx.push_back(models[i]->nx);
+    p->lint_rule.push_back(rules ? rules[i] : 0);
+    const int nb = rules && rules[i] == 2 ? n_basis[i] : 0;
+    p->lint_nbasis.push_back(nb);
+    p->lint_lift_off.push_back(lift_off[i]);
+    for (int j = 0; j < nb; ++j, ++k) { p->lint_prog_host.push_back(lift_kinds[k]); p->lint_prog_host.push_back(lift_params[k]); }
+  }
+  for (int b = 0; b < p->B; ++b) p->lint_sum_nx += p->lint_nx[model_index[b]];
+  int rc = h->precision == AMPC_F64 ? lint_upload<double>(p) : lint_upload<float>(p);
+  if (rc == 0) rc = mppi_table_rebuild(p);           // (forces 16-row tiles; x0 becomes ragged)
+  if (rc) {
+    const std::string msg = g_err;
+    LintState failed = lint_take(p);
+    lint_put(p, old);
+    p->forced_mt = old_mt; p->forced_quad = old_quad;
+    if (p->lint_n > 0) (void)(h->precision == AMPC_F64 ? lint_upload<double>(p) : lint_upload<float>(p));
+    (void)mppi_table_rebuild(p);
+    g_err = msg;
+    return rc;
+  }
+  for (ampc_handle* mh : p->lint_models) mh->refs++;
+  for (ampc_handle* mh : old.models) handle_release(mh);
+  return 0;
+}
+
+// simulate() (utils/simulation.py:44-63) with MPPI.run (mppi.py:154-168) for every problem of a plan on a table of linear
+// models: per control step the controller states follow their rules, one rollout launch and the update solve every
+// problem, the surrogate advances.
+template <typename T>
+static int closed_loop_linear_impl(ampc_mppi_plan* p, ampc_handle* sur, const double* init_state, const double* init_sim,
+                                   int n_steps, uint64_t seed, const double* eps_all, double* traj_obs,
+                                   double* traj_ctrls, const ScoreSpec* score, double* scores) {
+  ampc_handle* h = p->h;
+  const int nu = h->nu, B = p->B, T1 = n_steps + 1, snx = sur->nx;
+  legacy_predraw_drop(p);
+  DevBuf &d_obs = p->cl_obs, &d_ctl = p->cl_ctl, &d_next = p->cl_next, &d_sim = p->cl_sim;
+  HIP_OK(d_obs.reserve((size_t)B * T1 * snx * sizeof(T)));
+  HIP_OK(d_ctl.reserve((size_t)B * T1 * nu * sizeof(T)));
+  HIP_OK(d_next.reserve((size_t)B * snx * sizeof(T)));
+  if (init_state) {
+    HIP_OK(d_sim.reserve((size_t)B * snx * sizeof(T)));
+    HIP_OK(upload_converted<T>(p->x0.p, init_state, (size_t)p->lint_sum_nx, h->stream));
+    HIP_OK(upload_converted<T>(d_sim.p, init_sim, (size_t)B * snx, h->stream));
+    HIP_OK(hipMemsetAsync(p->lint_uprev.p, 0, (size_t)B * nu * sizeof(T), h->stream));
+    p->lint_snx = snx;
+  }
+  p->lint_cont = false;                                // (valid again only when this call completes)
+  HIP_OK(hipMemsetAsync(d_ctl.p, 0, (size_t)B * T1 * nu * sizeof(T), h->stream));
+  HIP_OK(hipStreamSynchronize(h->stream));
+  // traj_obs[:, 0, :] = the surrogate states this call starts from
+  HIP_OK(hipMemcpy2DAsync(d_obs.p, (size_t)T1 * snx * sizeof(T), d_sim.p, (size_t)snx * sizeof(T),
+                          (size_t)snx * sizeof(T), B, hipMemcpyDeviceToDevice, h->stream));
+  int rc = 0;
+  for (int s = 0; s < n_steps && rc == 0; ++s) {
+    hipLaunchKernelGGL(linear_ctrl_state_kernel<T>, dim3(B), dim3(kLinCtrlThreads), 0, h->stream,
+                       (const LinCtrlDesc*)p->lint_desc.p, (const LinDev<T>*)p->lint_tab.p, (T*)p->x0.p,
+                       (const T*)d_sim.p, snx, h->obs_dim, nu, (const T*)p->lint_uprev.p, (const T*)p->lint_prog.p);
+    HIP_OK(hipGetLastError());
+    if (eps_all) {
+      rc = mppi_upload_impl<T>(p, nullptr, nullptr, eps_all + (size_t)s * p->sum_nhnu);
+    } else {
+      rc = mppi_generate_impl<T>(p, seed, p->step_offset + (uint64_t)s);
+    }
+    if (rc) break;
+    rc = mppi_solve_impl<T>(p);
+    if (rc) break;
+    HIP_OK(hipMemcpyAsync(p->lint_uprev.p, p->u_out.p, (size_t)B * nu * sizeof(T), hipMemcpyDeviceToDevice, h->stream));
+    rc = surrogate_step<T>(h, sur, d_sim.p, p->u_out.p, d_next.p, B);
+    if (rc) break;
+    const int n = B * (snx > nu ? snx : nu);
+    hipLaunchKernelGGL(closed_loop_record_kernel<T>, dim3((n + 255) / 256), dim3(256), 0, h->stream,
+                       (const T*)d_next.p, (const T*)p->u_out.p, (T*)d_sim.p, (T*)d_obs.p, (T*)d_ctl.p, B, snx, nu, T1, s);
+    HIP_OK(hipGetLastError());
+  }
+  if (rc == 0) {
+    if (traj_obs) rc = download_converted<T>(traj_obs, d_obs.p, (size_t)B * T1 * snx, h->stream) == hipSuccess ? 0 : fail("closed loop: download failed");
+    if (rc == 0 && traj_ctrls) rc = download_converted<T>(traj_ctrls, d_ctl.p, (size_t)B * T1 * nu, h->stream) == hipSuccess ? 0 : fail("closed loop: download failed");
+  }
+  if (rc == 0 && score && scores)
+    rc = score_device<T>(h, d_obs.p, d_ctl.p, B, T1, snx, nu, h->obs_dim, *score, scores);
+  (void)hipStreamSynchronize(h->stream);
+  p->step_offset = 0;      // one-shot: ampc_mppi_plan_set_step_offset names the NEXT closed loop's first step
+  p->lint_cont = rc == 0;
+  return rc;
+}
+
+extern "C" int ampc_mppi_closed_loop_linear(ampc_mppi_plan* p, ampc_handle* surrogate, const double* init_state,
+                                            const double* init_sim, int n_steps, uint64_t seed, const double* eps_all,
+                                            int n_terms, const int* kinds, const double* params, double* scores,
+                                            double* traj_obs, double* traj_ctrls) {
+  static const std::string w = "ampc_mppi_closed_loop_linear";
+  REQUIRE(p && surrogate, w + ": NULL argument");
+  REQUIRE(p->lint_n > 0, w + ": the plan holds no table of linear models (ampc_mppi_plan_set_linear_models)");
+  REQUIRE(p->lint_loop, w + ": the table was set without rules (plain solves only)");
+  REQUIRE(n_steps >= 1, w + ": n_steps < 1");
+  REQUIRE((init_state == nullptr) == (init_sim == nullptr), w + ": init_state and init_sim are given together or not at all");
+  const ampc_handle* h = p->h;
+  REQUIRE(surrogate->has_model() && surrogate->nu == h->nu && surrogate->nx >= h->obs_dim,
+          w + ": the surrogate must have the plan's controls and a state that starts with the observation");
+  REQUIRE(surrogate->precision == h->precision && surrogate->device == h->device,
+          w + ": surrogate must share the plan's device and precision");
+  REQUIRE(init_state || (p->lint_cont && p->lint_snx == surrogate->nx),
+          w + ": nothing to continue from: the plan keeps no states of a previous call with this surrogate");
+  ScoreSpec sp;
+  sp.n_terms = n_terms; sp.kinds = kinds; sp.params = params;
+  const bool scored = n_terms > 0 && scores;
+  if (scored) {
+    std::vector<int> offs;
+    int total = 0;
+    if (int rc = score_spec_check(sp, h->obs_dim, h->nu, &offs, &total)) return rc;
+  }
+  HIP_OK(hipSetDevice(h->device));
+  return h->precision == AMPC_F64
+             ? closed_loop_linear_impl<double>(p, surrogate, init_state, init_sim, n_steps, seed, eps_all, traj_obs,
+                                               traj_ctrls, scored ? &sp : nullptr, scores)
+             : closed_loop_linear_impl<float>(p, surrogate, init_state, init_sim, n_steps, seed, eps_all, traj_obs,
+                                              traj_ctrls, scored ? &sp : nullptr, scores);
 }
 
 extern "C" int ampc_mppi_plan_set_outputs(ampc_mppi_plan* p, int keep_eps_out) {

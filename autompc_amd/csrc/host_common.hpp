@@ -488,6 +488,20 @@ struct ampc_mppi_plan {
   size_t sindy_lds = 0;
   DevBuf sindy_tab;
   std::vector<ampc_handle*> sindy_models;
+  // Linear models of mixed state dimension (ampc_mppi_plan_set_linear_models): lint_buf holds every entry's
+  // fragment-order [A | B] and plain copy in the plan's precision, lint_tab the device table of their LinDev<T>,
+  // lint_xoff [B] each problem's offset into the ragged x0 (lint_sum_nx values) -- model_idx names a problem's entry.
+  // lint_n > 0: the plan runs linear_table_rollout_kernel (mppi_linear_table_kernels.hpp) in 16-row tiles with the
+  // [x | u] region of the widest entry (lint_kp).  The plan keeps the handles alive.  With rules (lint_loop) the
+  // closed loop ampc_mppi_closed_loop_linear is allowed: lint_desc [B] per-problem rule records, lint_prog the lift
+  // programs; lint_cont: the plan holds the states, u_prev and surrogate states (width lint_snx) of a previous call.
+  int lint_n = 0, lint_kp = 0, lint_snx = 0;
+  long long lint_sum_nx = 0;
+  bool lint_loop = false, lint_cont = false;
+  std::vector<ampc_handle*> lint_models;
+  std::vector<int> lint_nx, lint_rule, lint_nbasis, lint_lift_off;   // per entry
+  std::vector<double> lint_prog_host;                                  // (kind, parameter) pairs of every lifted entry
+  DevBuf lint_buf, lint_tab, lint_xoff, lint_desc, lint_prog, lint_uprev;
 };
 
 // api_mppi.cpp: (re)compute sindy_lds for the plan's current horizon cap; -3 when an entry's need exceeds the limit

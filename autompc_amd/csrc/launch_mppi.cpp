@@ -4,6 +4,7 @@
 #include "host_common.hpp"
 #ifndef AMPC_JIT_PLUGIN
 #include "mppi_sindy_table_kernels.hpp"   // (SINDy models of mixed libraries in one plan: not part of a shape plugin)
+#include "mppi_linear_table_kernels.hpp"  // (linear models of mixed state dimension in one plan: likewise)
 #endif
 
 #ifndef AMPC_T
@@ -33,6 +34,8 @@ template <typename T> int mppi_solve_impl(ampc_mppi_plan* p) {
     return fail("ampc_mppi_solve: the plan holds a table of MLP models (ampc_mppi_plan_set_model_table) and a state lift");
   // (a table of SINDy models -- ampc_mppi_plan_set_sindy_models -- runs mppi_rollout_sindy_table_kernel: the rollout is on
   //  the observation, indicator terms included)
+  if (p->lint_n > 0 && p->lift_n > 0)
+    return fail("ampc_mppi_solve: the plan holds a table of linear models (ampc_mppi_plan_set_linear_models) and a state lift");
   if (p->sindy_n > 0 && p->lift_n > 0)
     return fail("ampc_mppi_solve: the plan holds a table of SINDy models (ampc_mppi_plan_set_sindy_models) and a state lift");
   if (p->sindy_n > 0 && (!p->h->has_sindy || !p->sindy_tab.p || p->sindy_lds == 0))
@@ -97,7 +100,11 @@ template <typename T> int mppi_solve_impl(ampc_mppi_plan* p) {
     if (sizeof(T) != 8) return fail("internal: four-row rollout in f32");      // (launched above)
   } else
 #ifndef AMPC_JIT_PLUGIN
-  if (p->sindy_n > 0) {           // SINDy models of mixed libraries through a device table (mppi_sindy_table_kernels.hpp)
+  if (p->lint_n > 0) {            // linear models of mixed state dimension through a device table (mppi_linear_table_kernels.hpp)
+    HIP_OK(allow_lds(linear_table_rollout_kernel<T>, p->lds_bytes));
+    hipLaunchKernelGGL(linear_table_rollout_kernel<T>, dim3(p->n_tiles), dim3(64 * kLinW), p->lds_bytes, h->stream, a,
+                       (const LinDev<T>*)p->lint_tab.p, (const int*)p->lint_xoff.p);
+  } else if (p->sindy_n > 0) {    // SINDy models of mixed libraries through a device table (mppi_sindy_table_kernels.hpp)
     // sixteen workgroups per 64-sample tile: four samples each for a lane-spread entry, the first one alone for a
     // one-thread entry; hcap as the single-model launch below forms it
     const int hcap = (p->max_h * h->nu + 3) / 4 * 4;

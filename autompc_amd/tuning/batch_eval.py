@@ -219,6 +219,38 @@ def sindy_table_decision(candidates, default, precision="f64", device=0, lift=No
     return True, ""
 
 
+def linear_table_decision(candidates, default, precision="f64", device=0, obs_dim=None):
+    """(True, "") when ONE MPPI plan with a table of linear models (MppiPlan.set_linear_models) takes the whole batch,
+    else (False, why).  It does when every candidate's controller model (`default`, the evaluator's own, for a candidate
+    without a "model") is a trained ``sysid.ARX`` or ``sysid.Koopman`` of the evaluator's system, precision and device
+    with at most 256 states whose controller-state rule the device has (``lqr_eval.device_rule``: a Koopman lift
+    without product terms) -- whatever its history or basis.  Needs no GPU."""
+    from ..sysid.linear import ARX, Koopman
+    from .lqr_eval import MAX_DEVICE_STATES, device_rule
+    system = getattr(default, "system", None)
+    no = int(obs_dim) if obs_dim is not None else (int(system.obs_dim) if system is not None else None)
+    for c in candidates:
+        m = c.get("model") if isinstance(c, dict) else None
+        m = default if m is None else m
+        if not isinstance(m, (ARX, Koopman)):
+            return False, "%s is not an ARX or Koopman model" % type(m).__name__
+        if m.A is None or m.B is None:
+            return False, "a candidate's %s model is not trained" % type(m).__name__
+        if system is not None and not (m.system == system):
+            return False, "a candidate's model belongs to another system than the evaluator's"
+        if m.precision != precision:
+            return False, "a candidate's model computes in %s, the evaluator in %s" % (m.precision, precision)
+        if int(m.device) != int(device):
+            return False, "a candidate's model lives on another device than the evaluator"
+        if int(m.state_dim) > MAX_DEVICE_STATES:
+            return False, "a candidate's model has %d states, more than %d" % (int(m.state_dim), MAX_DEVICE_STATES)
+        if isinstance(m, Koopman) and m.device_lift() is None:
+            return False, "a candidate's Koopman model has product terms, which the device lift cannot express"
+        if device_rule(m, no if no is not None else int(m.system.obs_dim)) is None:
+            return False, "the device has no controller-state rule for a candidate's %s model" % type(m).__name__
+    return True, ""
+
+
 def _needs_specialised_kernels(err):
     """The library's refusal of a model TABLE on a plan that runs the run-time-shape kernels (several models of one
     unregistered shape whose plugin is not built -- and, for one-evaluation models, never will be)."""
@@ -368,8 +400,16 @@ class CandidateEvaluator:
     accepts_global_ids = True          # evaluate(index_offset=<array of global indices>) is understood
 
     def __init__(self, system, task, model, surrogate=None, precision="f64", device=0,
-                 tile_rows=32, horizon_cap=30, term_check_every=8, mlp_models="shape", sindy_models="single"):
-        """sindy_models: "single" -- a plan rolls out on ONE SINDy model: candidates that carry SINDy models of their own
+                 tile_rows=32, horizon_cap=30, term_check_every=8, mlp_models="shape", sindy_models="single",
+                 linear_models="shape"):
+        """linear_models: "shape" -- ARX / Koopman controller models share a plan only with models of their class and
+        state dimension, a Koopman model needs one lift per plan and an ARX model a surrogate that is itself -- or
+        "table": one plan with a table of linear models of any mix of state dimensions (MppiPlan.set_linear_models, one
+        rollout launch per control step, every model's own update_state rule on the device, any surrogate) whenever
+        ``linear_table_decision`` allows it.  ``last_models`` then reads {"path": "linear_table", "models": n,
+        "plans": 1}; if the library declines the table (the widest entry's LDS need), the "shape" way takes the batch.
+
+        sindy_models: "single" -- a plan rolls out on ONE SINDy model: candidates that carry SINDy models of their own
         are refused by the library -- or "table": one plan with a table of SINDy models of any mix of feature libraries
         (MppiPlan.set_sindy_models, one rollout launch per control step) whenever ``sindy_table_decision`` allows it;
         if the library declines the table (an entry's LDS need), one plan per model object.  ``last_models`` then
@@ -398,6 +438,9 @@ class CandidateEvaluator:
         self._sindy_table = False
         if not hasattr(model, "stage_into"):
             raise TypeError("needs a device-stageable model (autompc_amd.sysid.MLP)")
+        if linear_models not in ("shape", "table"):
+            raise ValueError('linear_models must be "shape" or "table", not %r' % (linear_models,))
+        self.linear_models = linear_models
         self.system, self.task, self.model = system, task, model
         self.surrogate = surrogate if surrogate is not None else model
         # The device loop hands the surrogate's predicted STATE to the next solve.  That is
@@ -408,13 +451,18 @@ class CandidateEvaluator:
         # device its basis functions instead (device_lift): the loop then carries the surrogate's own
         # state and re-lifts the observation before every solve (ampc_mppi_plan_set_state_lift).
         self._lift = model.device_lift() if hasattr(model, "device_lift") else None
+        # (with linear_models="table" the table's closed loop runs every model's own rule: evaluate() raises this
+        #  for a batch that does not take the table)
+        self._no_device_loop = None
         if model.state_dim != system.obs_dim and self._lift is None:
             if not (getattr(model, "device_closed_loop", False) and self.surrogate is model):
-                raise TypeError(
+                self._no_device_loop = (
                     "%s keeps a model state that is not the observation and rebuilds it from every new "
                     "observation (update_state) in a way the device-resident closed loop cannot represent; "
                     "score such candidates with simulate() and the drop-in controller"
                     % type(model).__name__)
+                if linear_models != "table":
+                    raise TypeError(self._no_device_loop)
         # width of the state the loop carries and records
         self._snx = self.surrogate.state_dim if self._lift is not None else model.state_dim
         self.precision, self.device = precision, device
@@ -507,6 +555,22 @@ class CandidateEvaluator:
                 self.last_models = {"path": "model", "models": n_models, "plans": len(by_model)}
                 return self._evaluate_shape_groups(by_model, candidates, ids, dict(
                     n_steps=n_steps, seed=seed, init_obs=init_obs, return_trajectories=return_trajectories))
+        if self.linear_models == "table" and not self._table and not self._sindy_table:
+            ok, _why = linear_table_decision(candidates, self.model, self.precision, self.device, self.system.obs_dim)
+            if ok:
+                opened = []
+                try:
+                    out = self._evaluate_linear_table(candidates, n_steps, seed, init_obs, eps_all, act_init,
+                                                      return_trajectories, ids, opened, timing)
+                    self.last_models = {"path": "linear_table", "models": n_models, "plans": 1}
+                    return out
+                except _lib.AmpcError as e:
+                    if e.code != _lib.MPPI_TABLE_NO_FIT:      # (the widest entry's LDS need: the "shape" way takes the batch)
+                        raise
+                finally:
+                    _close_or_defer(self, opened)
+        if self._no_device_loop is not None:
+            raise TypeError(self._no_device_loop)
         shape_groups = _by_model_shape(candidates, self.model)
         self.last_models = {"path": "shape", "models": n_models,
                             "plans": 1 if shape_groups is None else len(shape_groups)}
@@ -554,6 +618,7 @@ class CandidateEvaluator:
             sub._close_later = later
             sub.mlp_models = "shape"                      # (the batch was declined as a whole: every group goes the default way)
             sub.sindy_models = "single"
+            sub.linear_models = "shape"
             sub.model = candidates[idx[0]]["model"]       # the group's plan handle is staged with one of ITS models
             # (sub.surrogate stays the evaluator's simulation model: copy.copy kept the reference)
             return idx, sub, sub.evaluate([candidates[i] for i in idx], index_offset=ids[idx], **kw)
@@ -708,6 +773,131 @@ class CandidateEvaluator:
         if timing is not None:
             timing["timing"] = plan.timing()
         return (scores, obs, ctrls) if return_trajectories else scores
+
+    def _evaluate_linear_table(self, candidates, n_steps, seed, init_obs, eps_all, act_init, return_trajectories,
+                               index_offset, opened, timing=None):
+        """The whole batch in ONE plan on a table of the candidates' ARX / Koopman models (MppiPlan.set_linear_models):
+        the plan handle is staged with the batch's first model, the table comes from the models' own handles, every
+        controller state starts from its model's traj_to_state and follows its model's update_state rule on the device
+        (MppiPlan.closed_loop_linear), the surrogate is the evaluator's.  With a termination condition the episode runs
+        in segments of ``term_check_every`` control steps that continue where the previous one stopped; a candidate that
+        has ended stays in the plan (its later rows are dropped), so every kept row is that of an unsegmented run."""
+        from ..trajectory import Trajectory
+        from .lqr_eval import device_rule
+        nu, no = self.system.ctrl_dim, self.system.obs_dim
+        snx = int(self.surrogate.state_dim)
+        B = len(candidates)
+        if n_steps is not None:
+            n_ctl, term_cond = int(n_steps), None
+        else:
+            max_steps, term_cond = episode_of(self.task)
+            n_ctl = default_episode_controls(self.task) if term_cond is None else max_steps
+        init_obs = np.asarray(self.task.get_init_obs() if init_obs is None else init_obs, dtype=np.float64)
+        models, index = candidate_models(candidates, self.model)
+        h = _lib.Handle(self.device, self.precision, jit=False)
+        opened.append(h)
+        models[0].stage_into(h)
+        handles = [model_handle(m, self.device, self.precision, opened) for m in models]
+        blocks, _ = candidate_cost_blocks(candidates, self.goal, no, nu)
+        h.set_cost_blocks(**blocks)
+        h.set_ctrl_bounds(self.umin, self.umax)
+        sur = _lib.Handle(self.device, self.precision)
+        opened.append(sur)
+        self.surrogate.stage_into(sur)
+        Hs = [int(c["horizon"]) for c in candidates]
+        if act_init is None:                # (as _evaluate: keyed by (seed, global candidate index))
+            act_init = np.concatenate([
+                np.random.default_rng([int(seed), int(index_offset[i])]).normal(
+                    scale=np.sqrt(c["sigma"]), size=Hs[i] * nu)
+                for i, c in enumerate(candidates)])
+        act_init = np.asarray(act_init, dtype=np.float64).ravel()
+        try:
+            terms = cost_terms(self.task.get_cost(), no, nu)
+        except TypeError:
+            terms = None
+        # the states of the one-row trajectory simulate() starts from (simulation.py:44-47)
+        one_row = Trajectory(self.system, 1, init_obs[None, :no].copy(), np.zeros((1, nu)))
+        if init_obs.shape == (snx,) and snx != no:
+            sim0 = init_obs
+        else:
+            sim0 = np.asarray(self.surrogate.traj_to_state(one_row), dtype=np.float64)
+        per_model = [np.asarray(m.traj_to_state(one_row), dtype=np.float64) for m in models]
+        states0 = np.concatenate([per_model[int(k)] for k in index])
+        sim0 = np.tile(sim0, (B, 1))
+        self.last_lengths = np.full(B, n_ctl + 1)
+        if timing is not None:
+            timing["control_steps"] = n_ctl
+        if n_ctl == 0:                    # max_steps = 0: the one-row trajectory is scored as is
+            obs, ctrls = sim0[:, None, :].copy(), np.zeros((B, 1, nu))
+            scores = self._score(h, terms, obs, ctrls)
+            return (scores, obs, ctrls) if return_trajectories else scores
+        plan = _lib.MppiPlan(h, [int(c["num_path"]) for c in candidates], Hs, [float(c["sigma"]) for c in candidates],
+                             [float(c["lmda"]) for c in candidates], cost_index=np.arange(B))
+        opened.append(plan)
+        plan.set_geometry(16, self.horizon_cap)
+        rules = [device_rule(m, no) for m in models]
+        plan.set_linear_models(handles, index, [r[0] for r in rules], [r[1] for r in rules])
+        plan.set_noise_ids(np.asarray(index_offset))
+        plan.upload(act_seq=act_init)
+        if timing is not None:
+            plan.set_timing(True)
+        if term_cond is None:
+            want = return_trajectories or terms is None
+            scores, obs, ctrls = plan.closed_loop_linear(sur, n_ctl, states0, sim0, terms=terms, seed=seed,
+                                                         eps_all=eps_all, return_trajectories=want)
+            if terms is None:
+                scores = self._score(h, None, obs, ctrls)
+            if timing is not None:
+                timing["timing"] = plan.timing()
+            return (scores, obs, ctrls) if return_trajectories else scores
+        # ---- a termination condition only the host can evaluate: segments, continued on the device
+        if eps_all is not None:
+            eps_all = np.asarray(eps_all, dtype=np.float64).reshape(-1, plan.sum_nhnu)
+            if eps_all.shape[0] < n_ctl:
+                raise ValueError("eps_all holds %d control steps, the episode may run %d" % (eps_all.shape[0], n_ctl))
+        obs = np.full((B, n_ctl + 1, snx), np.nan)
+        ctl = np.full((B, n_ctl + 1, nu), np.nan)
+        obs[:, 0] = sim0
+        lengths = np.full(B, n_ctl + 1)
+        alive, step0 = list(range(B)), 0
+        while step0 < n_ctl and alive:
+            k = min(self.term_check_every, n_ctl - step0)
+            plan.set_step_offset(step0)
+            first = step0 == 0
+            _, o, c = plan.closed_loop_linear(sur, k, states0 if first else None, sim0 if first else None, seed=seed,
+                                              eps_all=None if eps_all is None else eps_all[step0:step0 + k].ravel())
+            obs[:, step0 + 1:step0 + k + 1] = o[:, 1:]
+            ctl[:, step0:step0 + k] = c[:, :k]
+            still = []
+            for i in alive:
+                done = False
+                for t in range(step0 + 1, step0 + k + 1):      # rows 0..t exist, control row t is zero
+                    rows_c = ctl[i, :t + 1].copy()
+                    rows_c[t] = 0.0
+                    if term_cond(Trajectory(self.system, t + 1, obs[i, :t + 1, :no].copy(), rows_c)):
+                        lengths[i], done = t + 1, True
+                        break
+                if not done:
+                    still.append(i)
+            alive = still
+            step0 += k
+        if timing is not None:
+            timing["timing"] = plan.timing()
+            timing["control_steps"] = int(step0)
+        lengths = np.minimum(lengths, step0 + 1)
+        scores = np.empty(B)
+        for L in np.unique(lengths):
+            idx = np.nonzero(lengths == L)[0]
+            o, c = obs[idx, :L].copy(), ctl[idx, :L].copy()
+            c[:, L - 1] = 0.0                                  # simulate()'s trailing zero control row
+            scores[idx] = self._score(h, terms, o, c)
+            obs[idx, L:], ctl[idx, L - 1] = np.nan, 0.0
+            ctl[idx, L:] = np.nan
+        self.last_lengths = lengths
+        if return_trajectories:
+            Lmax = int(lengths.max())
+            return scores, obs[:, :Lmax], ctl[:, :Lmax]
+        return scores
 
     def _score(self, h, terms, obs, ctrls):
         no = self.system.obs_dim

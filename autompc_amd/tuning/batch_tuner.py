@@ -176,8 +176,16 @@ class BatchPipelineTuner:
                 c["model_cfg"] = draw_cfg(rng)
         elif self.model_factory is not None:
             draw_cfg = getattr(self.model_factory, "sample_configuration", None)
+            default = sample_mlp_config
+            if draw_cfg is None and getattr(self.evaluator, "linear_models", None) == "table":
+                # an MPPI evaluator that runs ARX / Koopman models of mixed sizes in one plan: their own sub-spaces
+                from ..sysid.linear import ARXFactory, KoopmanFactory
+                if isinstance(self.model_factory, ARXFactory):
+                    default = sample_arx_config
+                elif isinstance(self.model_factory, KoopmanFactory):
+                    default = sample_koopman_config
             for c in cands:
-                c["model_cfg"] = dict(draw_cfg(rng)) if draw_cfg else sample_mlp_config(rng)
+                c["model_cfg"] = dict(draw_cfg(rng)) if draw_cfg else default(rng)
         return cands
 
     # -- the model axis: fit what a shard asks for (pipeline.py:138-145) ---------------------------------

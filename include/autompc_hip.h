@@ -46,7 +46,7 @@ int ampc_version(void);   /* 100 * major + minor; 104: + ampc_mppi_run_legacy; 1
                            * 111: + ampc_kstep_errors_linear; 112: + ampc_kstep_errors_sindy;
                            * 113: + ampc_sindy_fit; 114: + ampc_lasso_fit; + ampc_stable_fit, + ampc_mlpfit_*, + ampc_kstep_errors_mlp,
                            *      + ampc_mppi_plan_set_model_table, + ampc_ilqr_plan_set_model_table, + ampc_mppi_plan_set_sindy_models,
-                           *      + ampc_ilqr_plan_set_sindy_models
+                           *      + ampc_ilqr_plan_set_sindy_models, + ampc_mppi_plan_set_linear_models, + ampc_mppi_closed_loop_linear
                            *      (no bump: callers detect them by their symbols) */
 int ampc_device_count(void);
 
@@ -488,6 +488,51 @@ int ampc_mppi_plan_set_model_table(ampc_mppi_plan* p, int n_models, const int* n
  * geometry, at any position of it -- the bits of a single-model plan on that model under AMPC_SINDY_G=16.  (Added
  * without a version bump: callers detect it by its symbol.) */
 int ampc_mppi_plan_set_sindy_models(ampc_mppi_plan* p, int n_models, ampc_handle* const* models, const int* model_index);
+/* Linear models x' = A x + B u of ANY mix of state dimensions (ARX histories, Koopman lifts; 1..256 states) in one MPPI
+ * plan, f64 or f32: the rollout of every problem b runs on models[model_index[b]], one launch per solve for the whole
+ * plan (linear_table_rollout_kernel, csrc/mppi_linear_table_kernels.hpp: 16 samples x 8 waves per workgroup, the K-tiled
+ * MFMA step of the wide linear models).  models[n_models]: handles staged with ampc_set_linear, in either staging form;
+ * the call packs every entry's fragment-order [A | B] and a plain copy in the plan's precision from the handle's exact f64
+ * matrices, keeps them in the plan and keeps the handles alive.  Staging new matrices into one of them afterwards needs
+ * another call.  rules / n_basis / lift_kinds / lift_params are PER MODEL and have the meaning of ampc_lqr_plan_set_loop:
+ * rules[k] 0 the state is the observation, 1 the ARX shift (A s + B u_prev, then the observation slot overwritten), 2 a
+ * lift of the observation with n_basis[k] functions, whose (kind, parameter) pairs follow each other in lift_kinds /
+ * lift_params in model order (kinds as ampc_mppi_plan_set_state_lift).  n_basis and lift_* may be NULL without rule 2;
+ * rules may be NULL: plain solves only, ampc_mppi_closed_loop_linear is refused.
+ * The call rebuilds the plan's geometry to 16-row tiles and makes x0 RAGGED: problem b owns nx[model_index[b]] values, in
+ * plan order, and ampc_mppi_upload's x0 is that concatenation.  ampc_mppi_solve and ampc_mppi_download are unchanged.
+ * Cost blocks (indicator terms included) and bounds remain the plan handle's.  n_models = 0 removes the table: the plan
+ * runs on its handle's own model and the automatic geometry again.  A replacing call takes the old table out first and
+ * installs the new one only once it is complete.
+ * Refused with a message: NULL arguments; a plan handle or a model handle without a linear model; models whose nu,
+ * precision or device are not the plan handle's; an entry with nx < obs_dim; rule 0 with nx != obs_dim; rule 2 with
+ * n_basis * obs_dim != nx or a bad kind or power; a plan with a state lift, per-problem models of one shape
+ * (ampc_mppi_plan_set_models), a table of MLP models or a table of SINDy models -- and those calls on a plan that holds
+ * this table; ampc_mppi_plan_set_geometry with tile_rows other than 0 or 16 afterwards; ampc_mppi_run, _run_legacy,
+ * ampc_mppi_set_x0_dev, ampc_mppi_closed_loop and _closed_loop_scored on such a plan (they assume x0 [B][nx]); a
+ * model_index out of range; and -- return code -3 instead of -1 -- a widest entry whose LDS map (2 x 16 rows of [x | u],
+ * cost block, shifted sequence) exceeds 160 KB for the plan's horizon cap.
+ * Deterministic: a problem's costs, clipped noise, sequence and control are the same bits alone, in any plan of the same
+ * horizon cap and update mode (fused or not), at any position of it -- the bits of a single-model plan on
+ * linear_rollout_kernel for that model (one staged with more than 64 states or under AMPC_LINEAR_WIDE=1).  (Added without
+ * a version bump: callers detect it by its symbol.) */
+int ampc_mppi_plan_set_linear_models(ampc_mppi_plan* p, int n_models, ampc_handle* const* models,
+                                     const int* model_index, const int* rules, const int* n_basis,
+                                     const int* lift_kinds, const double* lift_params);
+/* simulate() with MPPI.run for every problem of a plan that holds a table of linear models with rules.  Per control step:
+ * state_b <- rule_b(state_b, u_prev_b, sim_b[:obs_dim]) before every solve, the first included; the noise (eps_all
+ * [n_steps][sum N H nu], or Philox(seed, step offset + step) when NULL; ampc_mppi_plan_set_step_offset is honoured and
+ * reset); one rollout launch and the update; sim <- surrogate.pred(sim, u); the step is recorded.  init_state
+ * [sum_b nx_b]: each model's state of the one-row trajectory; init_sim [B][surrogate nx]; u_prev starts at 0.
+ * init_state == init_sim == NULL continues from the states, u_prev and sim the plan kept from its previous call (an
+ * episode in segments).  surrogate: any model with the plan's controls, precision and device whose state starts with the
+ * observation.  traj_obs [B][n_steps+1][surrogate nx] (row 0: the sim states the call starts from), traj_ctrls
+ * [B][n_steps+1][nu] (last row zero) -- either may be NULL; n_terms / kinds / params / scores as
+ * ampc_mppi_closed_loop_scored, n_terms = 0 or scores = NULL skips scoring.  (Added without a version bump.) */
+int ampc_mppi_closed_loop_linear(ampc_mppi_plan* p, ampc_handle* surrogate, const double* init_state,
+                                 const double* init_sim, int n_steps, uint64_t seed, const double* eps_all,
+                                 int n_terms, const int* kinds, const double* params, double* scores,
+                                 double* traj_obs, double* traj_ctrls);
 
 /* MLP models of ANY mix of depth, widths and activation in one f64 iLQR plan: the slot of a problem / episode runs on
  * the entry of a device table that model_index[n] of ampc_ilqr_solve_queue_var / ampc_ilqr_closed_loop_var names (range-
