@@ -27,7 +27,8 @@ MPPI_TABLE_NO_FIT = -3     # ampc_mppi_plan_set_model_table: the table kernel's 
 #                            (ampc_mppi_plan_set_sindy_models: an entry's LDS need does;
 #                             ampc_mppi_plan_set_linear_models: the widest entry's does)
 ILQR_TABLE_NO_FIT = -3     # ampc_ilqr_plan_set_model_table: the same for the table iteration kernel
-#                            (ampc_ilqr_plan_set_sindy_models: an entry's LDS need does)
+#                            (ampc_ilqr_plan_set_sindy_models: an entry's LDS need does;
+#                             ampc_ilqr_plan_set_linear_models: the widest entry's does)
 
 
 _lib = None
@@ -115,6 +116,11 @@ SIGNATURES = {
     "ampc_mppi_closed_loop_linear": (c_int, [c_void_p, c_void_p, _dp, _dp, c_int, c_uint64, _dp, c_int, _ip, _dp, _dp,
                                              _dp, _dp]),
     "ampc_ilqr_plan_set_sindy_models": (c_int, [c_void_p, c_int, POINTER(c_void_p)]),
+    "ampc_ilqr_plan_set_linear_models": (c_int, [c_void_p, c_int, POINTER(c_void_p), _ip, _ip, _ip, _dp]),
+    "ampc_ilqr_linear_table_layout": (c_int, [c_int, _ip, c_int, c_int, c_int, c_int, c_int, POINTER(ctypes.c_longlong),
+                                              POINTER(ctypes.c_longlong)]),
+    "ampc_ilqr_closed_loop_linear": (c_int, [c_void_p, c_void_p, c_int, _dp, _dp, _ip, _ip, _ip, c_int, c_int, _dp, _dp,
+                                             _ip, _ip, POINTER(ctypes.c_longlong)]),
     "ampc_mppi_plan_set_model_table": (c_int, [c_void_p, c_int, _ip, _ip, _ip, POINTER(c_void_p), POINTER(c_void_p),
                                                POINTER(c_void_p), _ip, _ip]),
     "ampc_ilqr_plan_set_model_table": (c_int, [c_void_p, c_int, _ip, _ip, _ip, POINTER(c_void_p), POINTER(c_void_p),
@@ -914,6 +920,116 @@ class IlqrPlan:
         check(self.lib.ampc_ilqr_plan_set_sindy_models(self._p, len(hs), arr))
         self._sindy_models = hs             # (kept alive on this side as well)
 
+    def set_linear_models(self, handles, rules=None, lifts=None):
+        """Linear models of mixed state dimension (ampc_ilqr_plan_set_linear_models, f64): `handles` hold linear models
+        (Handle.set_linear, either staging form) of the plan handle's controls, precision and device, at most 128
+        states each; solve_queue then takes model_index and a ragged x0, closed_loop_linear runs episodes.  rules
+        [n_models]: the closed loop's controller-state rule per model (0 the observation, 1 the ARX shift, 2 a lift --
+        ``MppiPlan.set_linear_models``' meaning); None: solves only.  lifts [n_models]: None or (kinds, params) for a
+        rule-2 model.  None / empty handles: removes the table.  A refusal raises AmpcError; its ``code`` is
+        ILQR_TABLE_NO_FIT when the widest entry's LDS need exceeds 160 KB."""
+        hs = list(handles or [])
+        arr = (c_void_p * max(len(hs), 1))(*[h._h for h in hs])
+        if not hs:
+            check(self.lib.ampc_ilqr_plan_set_linear_models(self._p, 0, arr, None, None, None, None))
+            self._linear_models, self.linear_nx = [], None
+            return
+        ru = nb = lk = lp = None
+        if rules is not None:
+            ru = np.ascontiguousarray(rules, dtype=np.int32)
+            if ru.shape != (len(hs),):
+                raise ValueError("rules has %d entries, expected one per model (%d)" % (ru.size, len(hs)))
+            lifts = list(lifts) if lifts is not None else [None] * len(hs)
+            nb = np.zeros(len(hs), dtype=np.int32)
+            kinds, params = [], []
+            for i, lf in enumerate(lifts):
+                if ru[i] == 2:
+                    if lf is None:
+                        raise ValueError("model %d has rule 2 (lift) and no lift" % i)
+                    nb[i] = len(lf[0])
+                    kinds.extend(int(k) for k in lf[0])
+                    params.extend(float(q) for q in lf[1])
+            lk = np.ascontiguousarray(kinds + [0], dtype=np.int32)
+            lp = as_f64(params + [0.0])
+        check(self.lib.ampc_ilqr_plan_set_linear_models(self._p, len(hs), arr, iptr(ru), iptr(nb), iptr(lk), dptr(lp)))
+        self._linear_models = hs            # (kept alive on this side as well)
+        self.linear_nx = np.array([h.nx for h in hs], dtype=np.int64)
+
+    def _linear_split(self, model_index, n):
+        """Per-problem state dimensions of a plan that holds a table of linear models."""
+        mi = np.zeros(n, dtype=np.int32) if model_index is None else self._model_index(model_index, n)
+        if mi.min() < 0 or mi.max() >= len(self.linear_nx):
+            raise ValueError("model_index out of range")
+        return mi, self.linear_nx[mi]
+
+    def _linear_ragged(self, rows, sizes, name):
+        """A list of per-problem vectors (or their concatenation) -> the ragged f64 array the library reads."""
+        if isinstance(rows, (list, tuple)):
+            rows = np.concatenate([as_f64(r).ravel() for r in rows])
+        flat = as_f64(rows).ravel()
+        if flat.size != int(sizes.sum()):
+            raise ValueError("%s has %d values, expected %d (the problems' own state dimensions)"
+                             % (name, flat.size, int(sizes.sum())))
+        return flat
+
+    def closed_loop_linear(self, surrogate, init_states, init_sim, n_steps, cost_index=None, max_iter=50, horizon=None,
+                           model_index=None):
+        """simulate() with IterativeLQR controllers on a table of linear models with rules (ampc_ilqr_closed_loop_linear),
+        device resident, any surrogate: init_states: per episode its model's traj_to_state of the one-row trajectory (a
+        list, or the concatenation); init_sim [C, surrogate nx].  Returns dict(obs [C, n_steps+1, surrogate nx], ctrls
+        [C, n_steps+1, nu], failed [C], steps [C], iterations [C])."""
+        if not getattr(self, "_linear_models", None):
+            raise ValueError("the plan holds no table of linear models (set_linear_models)")
+        sur = surrogate if surrogate is not None else self.handle
+        nu, snx = self.handle.nu, sur.nx
+        init_sim = as_f64(init_sim).reshape(-1, snx)
+        C = init_sim.shape[0]
+        mi, sizes = self._linear_split(model_index, C)
+        x0 = self._linear_ragged(init_states, sizes, "init_states")
+        ci = None if cost_index is None else np.ascontiguousarray(np.broadcast_to(
+            np.asarray(cost_index, dtype=np.int32), (C,)))
+        hz = self._horizons(horizon, C)
+        out = {"obs": np.empty((C, n_steps + 1, snx)), "ctrls": np.empty((C, n_steps + 1, nu)),
+               "failed": np.zeros(C, dtype=np.int32), "steps": np.zeros(C, dtype=np.int32),
+               "iterations": np.zeros(C, dtype=np.int64)}
+        check(self.lib.ampc_ilqr_closed_loop_linear(
+            self._p, surrogate._h if surrogate is not None else None, C, dptr(x0), dptr(init_sim), iptr(ci), iptr(hz),
+            iptr(mi), int(n_steps), int(max_iter), dptr(out["obs"]), dptr(out["ctrls"]), iptr(out["failed"]),
+            iptr(out["steps"]), out["iterations"].ctypes.data_as(POINTER(ctypes.c_longlong))))
+        return out
+
+    def _solve_queue_linear(self, x0, uguess, cost_index, max_iter, gains, trajectories, horizon, model_index):
+        """solve_queue on a table of linear models: ragged x0, per-problem arrays back."""
+        nu, H = self.handle.nu, self.H
+        P = len(x0) if isinstance(x0, (list, tuple)) else len(np.atleast_1d(model_index))
+        mi, sizes = self._linear_split(model_index, P)
+        x0 = self._linear_ragged(x0, sizes, "x0")
+        nxw = int(self.linear_nx.max())
+        ug = None if uguess is None else as_f64(uguess).reshape(P, H, nu)
+        ci = None if cost_index is None else np.ascontiguousarray(np.broadcast_to(
+            np.asarray(cost_index, dtype=np.int32), (P,)))
+        hz = self._horizons(horizon, P)
+        out = {"converged": np.zeros(P, dtype=np.int32), "iters": np.zeros(P, dtype=np.int32),
+               "status": np.zeros(P, dtype=np.int32), "objective": np.empty(P)}
+        st = ct = Kb = kb = None
+        if trajectories:
+            st, ct = np.empty((P, (H + 1) * nxw)), np.empty((P, H, nu))
+        if gains:
+            Kb, kb = np.empty((P, H * nu * nxw)), np.empty((P, H, nu))
+        check(self.lib.ampc_ilqr_solve_queue_var(self._p, P, dptr(x0), dptr(ug), iptr(ci), iptr(hz), iptr(mi), int(max_iter),
+                                                 dptr(st), dptr(ct), dptr(Kb), dptr(kb), iptr(out["converged"]),
+                                                 iptr(out["iters"]), iptr(out["status"]), dptr(out["objective"])))
+        # a problem's region keeps the widest entry's stride; its rows are packed at its own nx, the rest is zero
+        if trajectories:
+            out["states"] = [st[j, :(H + 1) * n].reshape(H + 1, n) for j, n in enumerate(sizes)]
+            out["ctrls"] = ct
+            out["states_tail"] = [st[j, (H + 1) * n:] for j, n in enumerate(sizes)]
+        if gains:
+            out["Ks"] = [Kb[j, :H * nu * n].reshape(H, nu, n) for j, n in enumerate(sizes)]
+            out["ks"] = kb
+            out["Ks_tail"] = [Kb[j, H * nu * n:] for j, n in enumerate(sizes)]
+        return out
+
     def _model_index(self, model_index, n):
         if model_index is None:
             return None
@@ -948,7 +1064,12 @@ class IlqrPlan:
         uguess [P, H, nu] or None (zeros); cost_index [P] or None (block 0).  Per-problem results are
         bit-identical to one-problem solves.  gains / trajectories = False skip those downloads.
         horizon [P] (optional): each problem's own horizon, at most the plan's (ampc_ilqr_solve_queue_var):
-        arrays keep the plan's H as their stride, rows past a problem's horizon come back zero."""
+        arrays keep the plan's H as their stride, rows past a problem's horizon come back zero.
+        On a table of linear models (set_linear_models): x0 is a list of the problems' own states (or their
+        concatenation, with model_index of length P); "states" and "Ks" come back as lists of per-problem arrays
+        [H+1, nx_j] and [H, nu, nx_j] ("states_tail" / "Ks_tail": what lies behind them in the problem's region: zeros)."""
+        if getattr(self, "_linear_models", None):
+            return self._solve_queue_linear(x0, uguess, cost_index, max_iter, gains, trajectories, horizon, model_index)
         nx, nu, H = self.handle.nx, self.handle.nu, self.H
         x0 = as_f64(x0).reshape(-1, nx)
         P = x0.shape[0]
@@ -968,6 +1089,19 @@ class IlqrPlan:
                                                  dptr(out.get("ks")), iptr(out["converged"]), iptr(out["iters"]),
                                                  iptr(out["status"]), dptr(out["objective"])))
         return out
+
+
+def ilqr_linear_table_layout(nx, nu, obs_dim, B, H, ls_n=10):
+    """(entry_off [n, 3], strides dict) of ampc_ilqr_plan_set_linear_models for models of nx[n] states
+    (ampc_ilqr_linear_table_layout: no device needed)."""
+    nx = np.ascontiguousarray(nx, dtype=np.int32)
+    off = np.zeros((len(nx), 3), dtype=np.int64)
+    st = np.zeros(10, dtype=np.int64)
+    ll = POINTER(ctypes.c_longlong)
+    check(load().ampc_ilqr_linear_table_layout(len(nx), iptr(nx), int(nu), int(obs_dim), int(B), int(H), int(ls_n),
+                                               off.ctypes.data_as(ll), st.ctypes.data_as(ll)))
+    names = ("states", "ctrls", "Ks", "ks", "ls_states", "ls_ctrls", "vj", "table_values", "sweep_lds_bytes", "ls_lds_bytes")
+    return off, {k: int(v) for k, v in zip(names, st)}
 
 
 class LqrPlan:

@@ -6,6 +6,7 @@
 #include "jit_host.hpp"                // shape plugins compiled at run time
 #include "ilqr_table_host.hpp"         // ampc_ilqr_plan_set_model_table: checks and the LDS map without a device call
 #include "ilqr_sindy_table_host.hpp"   // ampc_ilqr_plan_set_sindy_models: checks, the selection rule and the LDS maps
+#include "ilqr_linear_table_host.hpp"  // ampc_ilqr_plan_set_linear_models: the second kernel argument, LDS maps, launchers
 
 extern template int pred_impl<double>(ampc_handle*, const double*, const double*, double*, double*, double*, int);
 extern template int pred_impl<float>(ampc_handle*, const double*, const double*, double*, double*, double*, int);
@@ -149,7 +150,8 @@ extern "C" int ampc_ilqr_plan_set_constants(ampc_ilqr_plan* p, double u_threshol
   p->ls_cost_threshold = ls_cost_threshold;
   p->ls_n = ls_max_iter;
   const size_t e = h->esz();
-  HIP_OK(p->ls_states.reserve((size_t)p->B * p->ls_n * (p->H + 1) * h->nx * e));
+  const int nxs = std::max(h->nx, p->lqt_nxw);        // (a table of linear models: the widest entry's stride)
+  HIP_OK(p->ls_states.reserve((size_t)p->B * p->ls_n * (p->H + 1) * nxs * e));
   HIP_OK(p->ls_ctrls.reserve((size_t)p->B * p->ls_n * p->H * h->nu * e));
   return 0;
 }
@@ -210,6 +212,9 @@ extern "C" int ampc_ilqr_plan_destroy(ampc_ilqr_plan* p) {
   p->mlp_tab.release(); p->slot_model.release(); p->slot_of.release();
   p->table_models.release(); p->table_stage.release(); p->table_dz.release();
   p->sindy_tab.release();
+  p->lqt_buf.release(); p->lqt_tab.release(); p->lqt_rules.release(); p->lqt_prog.release(); p->lqt_xoff.release();
+  p->lqt_sim.release(); p->lqt_desc.release();
+  for (ampc_handle* mh : p->lqt_models) handle_release(mh);
   for (ampc_handle* mh : p->sindy_models) handle_release(mh);
   for (ampc_handle* mh : p->models) handle_release(mh);
   for (hipEvent_t e : p->ev) (void)hipEventDestroy(e);
@@ -315,6 +320,8 @@ extern "C" int ampc_ilqr_solve(ampc_ilqr_plan* p, const double* x0, const double
                                int* converged, int* iters, int* status, double* objective) {
   REQUIRE(p && x0 && uguess, "ampc_ilqr_solve: NULL argument");
   REQUIRE(max_iter >= 0, "ampc_ilqr_solve: max_iter < 0");
+  REQUIRE(p->lqt_n == 0, "ampc_ilqr_solve: the plan holds a table of linear models (ampc_ilqr_plan_set_linear_models), whose "
+                         "problems name their model: use ampc_ilqr_solve_queue_var");
   HIP_OK(hipSetDevice(p->h->device));
   return p->h->precision == AMPC_F64
              ? ilqr_solve_impl<double>(p, x0, uguess, max_iter, states, ctrls, Ks, ks, converged, iters, status, objective)
@@ -327,7 +334,7 @@ extern "C" int ampc_ilqr_solve(ampc_ilqr_plan* p, const double* x0, const double
 // MLP models only (the feature-library and wide-linear kernels keep workgroup b = slot b).
 static bool ilqr_wants_compaction(const ampc_ilqr_plan* p) {
   const int force = env_int("AMPC_ILQR_COMPACT", -1);
-  if (force == 0 || !p->h->has_mlp || p->h->has_sindy || p->h->has_lin) return false;
+  if (force == 0 || !p->h->has_mlp || p->h->has_sindy || p->h->has_lin || p->lqt_n > 0) return false;
   return force == 1 || p->B > p->h->n_cus;
 }
 template <typename T> static int ilqr_compact(ampc_ilqr_plan* p) {
@@ -346,12 +353,23 @@ static int ilqr_solve_queue_impl(ampc_ilqr_plan* p, int P, const double* x0, con
                                  double* states, double* ctrls, double* Ks, double* ks, int* converged, int* iters,
                                  int* status, double* objective) {
   ampc_handle* h = p->h;
-  const int nx = h->nx, nu = h->nu, B = p->B, H = p->H;
+  // a table of linear models (ampc_ilqr_plan_set_linear_models): nx is the widest entry's -- the stride of every region --
+  // and x0 is ragged, problem j's own nx values at x_off[j]
+  const bool lt = p->lqt_n > 0;
+  const int nx = lt ? p->lqt_nxw : h->nx, nu = h->nu, B = p->B, H = p->H;
   const size_t e = sizeof(T);
+  std::vector<int> x_off;
+  size_t x0_elems = (size_t)P * nx;
+  if (lt) {
+    x_off.resize(P);
+    x0_elems = 0;
+    for (int j = 0; j < P; ++j) { x_off[j] = (int)x0_elems; x0_elems += p->lqt_nx[model_index ? model_index[j] : 0]; }
+    REQUIRE(x0_elems < ((size_t)1 << 31), "ampc_ilqr_solve_queue_var: too many states in x0");
+  }
   HIP_OK(p->q_ctl.reserve((size_t)(2 + 2 * B) * sizeof(int)));
-  HIP_OK(p->q_x0.reserve((size_t)P * nx * e));
+  HIP_OK(p->q_x0.reserve(x0_elems * e));
   HIP_OK(p->q_u.reserve((size_t)P * H * nu * e));
-  HIP_OK(p->q_cost.reserve((size_t)3 * P * sizeof(int)));               // cost block [P], horizon [P], model [P]
+  HIP_OK(p->q_cost.reserve((size_t)4 * P * sizeof(int)));               // cost block [P], horizon [P], model [P], x_off [P]
   HIP_OK(p->q_states.reserve((size_t)P * (H + 1) * nx * e));
   HIP_OK(p->q_ctrls.reserve((size_t)P * H * nu * e));
   HIP_OK(p->q_Ks.reserve((size_t)P * H * nu * nx * e));
@@ -370,12 +388,16 @@ static int ilqr_solve_queue_impl(ampc_ilqr_plan* p, int P, const double* x0, con
     HIP_OK(hipMemcpyAsync(p->slot_h.p, slot_h0.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, h->stream));
     HIP_OK(hipMemcpyAsync((int*)p->q_cost.p + P, horizon, (size_t)P * sizeof(int), hipMemcpyHostToDevice, h->stream));
   }
-  if (model_index) {
+  if (model_index || lt) {
     HIP_OK(p->slot_model.reserve((size_t)B * sizeof(int)));
     HIP_OK(hipMemsetAsync(p->slot_model.p, 0, (size_t)B * sizeof(int), h->stream));
-    HIP_OK(hipMemcpyAsync((int*)p->q_cost.p + 2 * P, model_index, (size_t)P * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    if (model_index)
+      HIP_OK(hipMemcpyAsync((int*)p->q_cost.p + 2 * P, model_index, (size_t)P * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    else
+      HIP_OK(hipMemsetAsync((int*)p->q_cost.p + 2 * P, 0, (size_t)P * sizeof(int), h->stream));
   }
-  HIP_OK(upload_converted<T>(p->q_x0.p, x0, (size_t)P * nx, h->stream));
+  if (lt) HIP_OK(hipMemcpyAsync((int*)p->q_cost.p + 3 * P, x_off.data(), (size_t)P * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIP_OK(upload_converted<T>(p->q_x0.p, x0, x0_elems, h->stream));
   if (uguess) HIP_OK(upload_converted<T>(p->q_u.p, uguess, (size_t)P * H * nu, h->stream));
   else HIP_OK(hipMemsetAsync(p->q_u.p, 0, (size_t)P * H * nu * e, h->stream));
   HIP_OK(hipMemsetAsync(p->flags.p, 0, (size_t)9 * B * sizeof(int), h->stream));     // every slot idle
@@ -410,7 +432,7 @@ static int ilqr_solve_queue_impl(ampc_ilqr_plan* p, int P, const double* x0, con
   IlqrQueue<T> q;
   q.P = P; q.B = B; q.H = H; q.nx = nx; q.nu = nu;
   q.horizon = horizon ? (const int*)p->q_cost.p + P : nullptr; q.slot_h = (int*)p->slot_h.p;
-  q.model = model_index ? (const int*)p->q_cost.p + 2 * P : nullptr; q.slot_model = (int*)p->slot_model.p;
+  q.model = (model_index || lt) ? (const int*)p->q_cost.p + 2 * P : nullptr; q.slot_model = (int*)p->slot_model.p;
   q.ctl = (int*)p->q_ctl.p; q.slot_prob = q.ctl + 2;
   q.x0 = (const T*)p->q_x0.p; q.uguess = (const T*)p->q_u.p; q.cost = (const int*)p->q_cost.p;
   q.cost_idx = (int*)p->d_cost_idx.p;
@@ -431,8 +453,12 @@ static int ilqr_solve_queue_impl(ampc_ilqr_plan* p, int P, const double* x0, con
   while (!done && it < bound) {             //  count of slots with work, compact_on: the count is then 4 iterations old)
     for (int k = 0; k < poll_now; ++k) {
       IlqrArgs<T> a = make_ilqr_args<T>(p, 1);
-      hipLaunchKernelGGL(ilqr_queue_refill_kernel<T>, dim3(B), dim3(256), 0, h->stream, a, q);
-      HIP_OK(hipGetLastError());
+      if (lt) {
+        if (int rc = ilqr_linear_table_refill(p, &a, &q, (const int*)p->q_cost.p + 3 * P)) return rc;
+      } else {
+        hipLaunchKernelGGL(ilqr_queue_refill_kernel<T>, dim3(B), dim3(256), 0, h->stream, a, q);
+        HIP_OK(hipGetLastError());
+      }
       if (int rc = ilqr_compact<T>(p)) return rc;
       if (p->timing && (it + k) % p->timing_stride == 0) {
         if (p->ev_used + 5 > p->ev.size())
@@ -504,9 +530,9 @@ static int check_horizons(const ampc_ilqr_plan* p, int n, const int* horizon, co
 
 static int check_models(const ampc_ilqr_plan* p, int n, const int* model_index, const char* who) {
   if (model_index) {
-    REQUIRE(!p->models.empty() || p->table_n > 0 || p->sindy_n > 0,
+    REQUIRE(!p->models.empty() || p->table_n > 0 || p->sindy_n > 0 || p->lqt_n > 0,
             std::string(who) + ": model_index given but the plan has no model table (ampc_ilqr_plan_set_models)");
-    const int n_models = p->table_n > 0 ? p->table_n : p->sindy_n > 0 ? p->sindy_n : (int)p->models.size();
+    const int n_models = p->table_n > 0 ? p->table_n : p->sindy_n > 0 ? p->sindy_n : p->lqt_n > 0 ? p->lqt_n : (int)p->models.size();
     for (int j = 0; j < n; ++j)
       REQUIRE(model_index[j] >= 0 && model_index[j] < n_models, std::string(who) + ": bad model_index");
   }
@@ -527,6 +553,8 @@ extern "C" int ampc_ilqr_plan_set_models(ampc_ilqr_plan* p, int n_models, ampc_h
                            "(ampc_ilqr_plan_set_model_table); remove it first");
   REQUIRE(p->sindy_n == 0, "ampc_ilqr_plan_set_models: the plan holds a table of SINDy models "
                            "(ampc_ilqr_plan_set_sindy_models); remove it first");
+  REQUIRE(p->lqt_n == 0, "ampc_ilqr_plan_set_models: the plan holds a table of linear models "
+                         "(ampc_ilqr_plan_set_linear_models); remove it first");
   for (int i = 0; i < n_models; ++i)
     if (int rc = check_same_shape(p->h, models[i], "ampc_ilqr_plan_set_models")) return rc;
   if (p->static_shape < 0) {
@@ -565,6 +593,8 @@ extern "C" int ampc_ilqr_plan_set_model_table(ampc_ilqr_plan* p, int n_models, c
   }
   if (p->sindy_n > 0)
     return ilqr_table_fail("the plan holds a table of SINDy models (ampc_ilqr_plan_set_sindy_models); remove it first");
+  if (p->lqt_n > 0)
+    return ilqr_table_fail("the plan holds a table of linear models (ampc_ilqr_plan_set_linear_models); remove it first");
   IlqrTablePlanView v;
   v.f64 = h->precision == AMPC_F64;
   v.has_mlp = h->has_mlp && !h->has_sindy && !h->has_lin && h->lin_n == 0;    // (a small linear model is staged as a network)
@@ -663,6 +693,8 @@ extern "C" int ampc_ilqr_plan_set_sindy_models(ampc_ilqr_plan* p, int n_models, 
     return 0;
   }
   if (n_models < 1 || !models) return ilqr_sindy_table_fail("NULL argument");
+  if (p->lqt_n > 0)
+    return ilqr_sindy_table_fail("the plan holds a table of linear models (ampc_ilqr_plan_set_linear_models); remove it first");
   const IlqrSindyView pv = ilqr_sindy_view(h);
   std::vector<IlqrSindyView> views((size_t)n_models);
   std::vector<const IlqrSindyView*> vp((size_t)n_models, nullptr);
@@ -885,6 +917,8 @@ extern "C" int ampc_ilqr_closed_loop_var(ampc_ilqr_plan* p, ampc_handle* surroga
                                          int n_steps, int max_iter, double* traj_obs, double* traj_ctrls, int* failed,
                                          int* steps_done, long long* iterations) {
   REQUIRE(p && init_obs, "ampc_ilqr_closed_loop: NULL argument");
+  REQUIRE(p->lqt_n == 0, "ampc_ilqr_closed_loop: the plan holds a table of linear models (ampc_ilqr_plan_set_linear_models), "
+                         "whose controller states are not the observation: use ampc_ilqr_closed_loop_linear");
   if (int rc = check_horizons(p, n_chains, horizon, "ampc_ilqr_closed_loop_var")) return rc;
   if (int rc = check_models(p, n_chains, model_index, "ampc_ilqr_closed_loop_var")) return rc;
   REQUIRE(n_chains >= 1 && n_steps >= 1 && max_iter >= 1, "ampc_ilqr_closed_loop: n_chains, n_steps, max_iter must be >= 1");
@@ -902,4 +936,365 @@ extern "C" int ampc_ilqr_closed_loop_var(ampc_ilqr_plan* p, ampc_handle* surroga
                                              traj_obs, traj_ctrls, failed, steps_done, iterations)
              : ilqr_closed_loop_impl<float>(p, sur, n_chains, init_obs, cost_index, horizon, model_index, n_steps, max_iter,
                                             traj_obs, traj_ctrls, failed, steps_done, iterations);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Linear models of mixed state dimension in one plan (ilqr_linear_table_kernels.hpp)
+// ---------------------------------------------------------------------------------------------
+static int ilqr_linear_table_fail(const std::string& msg, int rc = -1) {
+  g_err = "ampc_ilqr_plan_set_linear_models: " + msg;
+  return rc;
+}
+
+// Where ampc_ilqr_plan_set_linear_models puts things (no device call; the call itself packs by these numbers).
+extern "C" int ampc_ilqr_linear_table_layout(int n_models, const int* nx, int nu, int obs_dim, int B, int H, int ls_n,
+                                             long long* entry_off, long long* strides) {
+  REQUIRE(n_models >= 1 && nx && entry_off && strides, "ampc_ilqr_linear_table_layout: NULL argument");
+  REQUIRE(nu >= 1 && obs_dim >= 1 && B >= 1 && H >= 1 && ls_n >= 1, "ampc_ilqr_linear_table_layout: bad dimensions");
+  long long o = 0;
+  int w = 0;
+  for (int i = 0; i < n_models; ++i) {
+    REQUIRE(nx[i] >= 1, "ampc_ilqr_linear_table_layout: bad state dimension");
+    const long long n = nx[i], k = n + nu, nxp = round_up(nx[i], 16), ksn = round_up((int)k, 4) / 4, ldj = round_up((int)k, 16);
+    entry_off[3 * i] = o;                                       // fragments [ntile][ksn][64]
+    entry_off[3 * i + 1] = o + (nxp / 16) * ksn * 64;           // plain rows [nx][nx + nu], padded to four values
+    entry_off[3 * i + 2] = entry_off[3 * i + 1] + round_up((int)(n * k), 4);   // jp [nxp][ldj]
+    o = entry_off[3 * i + 2] + nxp * ldj;
+    w = std::max(w, nx[i]);
+  }
+  const long long W = w;
+  strides[0] = (long long)(H + 1) * W;                          // states, per slot / per problem
+  strides[1] = (long long)H * nu;                               // ctrls
+  strides[2] = (long long)H * nu * W;                           // Ks
+  strides[3] = (long long)H * nu;                               // ks
+  strides[4] = (long long)ls_n * (H + 1) * W;                   // ls_states
+  strides[5] = (long long)ls_n * H * nu;                        // ls_ctrls
+  strides[6] = (long long)round_up(w, 16) * round_up(w + nu, 16);   // vj
+  strides[7] = o;                                               // values in the table buffer
+  strides[8] = (long long)ilqr_linear_table_sweep_bytes(w, nu, obs_dim);                                  // LDS of the sweep
+  strides[9] = (long long)ilqr_linear_table_ls_map(w, nu, cost_block_stride(obs_dim, nu), nullptr, nullptr);   // ... line search
+  return 0;
+}
+
+extern "C" int ampc_ilqr_plan_set_linear_models(ampc_ilqr_plan* p, int n_models, ampc_handle* const* models,
+                                                const int* rules, const int* n_basis, const int* lift_kinds,
+                                                const double* lift_params) {
+  if (!p) return ilqr_linear_table_fail("NULL plan");
+  ampc_handle* h = p->h;
+  if (n_models == 0) {                               // back to the handle's own model and its kernels
+    if (p->lqt_n == 0) return 0;
+    HIP_OK(hipSetDevice(h->device));
+    HIP_OK(hipStreamSynchronize(h->stream));
+    for (ampc_handle* mh : p->lqt_models) handle_release(mh);
+    p->lqt_models.clear(); p->lqt_nx.clear();
+    p->lqt_n = 0; p->lqt_nxw = 0; p->lqt_loop = false; p->lqt_sweep_bytes = 0; p->lqt_ls_bytes = 0;
+    return ilqr_plan_build<double>(p);               // (the kernel choices and buffers of the handle's own model)
+  }
+  if (n_models < 1 || !models) return ilqr_linear_table_fail("NULL argument");
+  if (h->precision != AMPC_F64) return ilqr_linear_table_fail("the table kernels are f64 only; this plan's handle is f32");
+  if (!(h->lin_n > 0 && h->lin_n == h->nx))
+    return ilqr_linear_table_fail("the plan handle's model is not a linear model (ampc_set_linear)");
+  if (!p->models.empty())
+    return ilqr_linear_table_fail("the plan holds per-problem models of one shape (ampc_ilqr_plan_set_models); remove them first");
+  if (p->table_n > 0)
+    return ilqr_linear_table_fail("the plan holds a table of MLP models (ampc_ilqr_plan_set_model_table); remove it first");
+  if (p->sindy_n > 0)
+    return ilqr_linear_table_fail("the plan holds a table of SINDy models (ampc_ilqr_plan_set_sindy_models); remove it first");
+  const int nu = h->nu, no = h->obs_dim;
+  if (!(nu == 1 || nu == 2 || nu == 3 || nu == 4 || nu == 6 || nu == 8))
+    return ilqr_linear_table_fail("the sweep on linear models is built for 1, 2, 3, 4, 6 or 8 controls");
+  int n_lift = 0, nxw = 0;
+  std::vector<int> lift_off(n_models, 0);
+  for (int i = 0; i < n_models; ++i) {
+    const ampc_handle* m = models[i];
+    if (!m) return ilqr_linear_table_fail("NULL model handle");
+    if (!(m->lin_n > 0 && m->lin_n == m->nx && (int)m->lin_ab_host.size() == m->nx * (m->nx + m->nu)))
+      return ilqr_linear_table_fail("a model handle holds no linear model (ampc_set_linear)");
+    if (m->precision != AMPC_F64) return ilqr_linear_table_fail("the table kernels are f64 only; a model's handle is f32");
+    if (m->device != h->device) return ilqr_linear_table_fail("models must share the plan's device");
+    if (m->nu != nu) return ilqr_linear_table_fail("models must have the plan handle's control dimension");
+    if (m->nx < no) return ilqr_linear_table_fail("a model has fewer states than the cost's observation (nx < obs_dim)");
+    if (m->nx > kLinMaxIlqrNx)
+      return ilqr_linear_table_fail("iLQR on linear models takes up to 128 model states (the value function's Hessian lives "
+                                    "in LDS); a model has more");
+    nxw = std::max(nxw, m->nx);
+    if (!rules) continue;
+    if (rules[i] < 0 || rules[i] > 2) return ilqr_linear_table_fail("rule must be 0 observation, 1 ARX shift, 2 lift");
+    if (rules[i] == 0 && m->nx != no) return ilqr_linear_table_fail("rule 0 (state = observation) needs nx == obs_dim");
+    if (rules[i] == 2) {
+      if (!(n_basis && lift_kinds && lift_params)) return ilqr_linear_table_fail("rule 2 needs n_basis, lift_kinds and lift_params");
+      if (!(n_basis[i] >= 1 && no >= 1 && n_basis[i] * no == m->nx))
+        return ilqr_linear_table_fail("n_basis * obs_dim must be the model's state dimension");
+      lift_off[i] = 2 * n_lift;
+      for (int k = n_lift; k < n_lift + n_basis[i]; ++k) {
+        if (lift_kinds[k] < 0 || lift_kinds[k] > 3) return ilqr_linear_table_fail("lift kind must be 0 identity, 1 power, 2 sin, 3 cos");
+        if (lift_kinds[k] == 1 && !(lift_params[k] >= 0 && lift_params[k] <= 64 && lift_params[k] == std::floor(lift_params[k])))
+          return ilqr_linear_table_fail("powers must be integers in 0..64");
+      }
+      n_lift += n_basis[i];
+    }
+  }
+  int lds_xn = 0, lds_work = 0;
+  std::vector<int> nxs_in(n_models);
+  for (int i = 0; i < n_models; ++i) nxs_in[i] = models[i]->nx;
+  std::vector<long long> lay_off(3 * (size_t)n_models), lay(10);
+  if (int rc = ampc_ilqr_linear_table_layout(n_models, nxs_in.data(), nu, no, p->B, p->H, p->ls_n, lay_off.data(), lay.data()))
+    return rc;
+  const size_t sweep_bytes = (size_t)lay[8];
+  const size_t ls_bytes = ilqr_linear_table_ls_map(nxw, nu, h->cost_stride, &lds_xn, &lds_work);
+  if (ls_bytes != (size_t)lay[9]) return ilqr_linear_table_fail("internal: the cost block's stride");
+  if (sweep_bytes > kLdsLimit || ls_bytes > kLdsLimit)
+    return ilqr_linear_table_fail("the widest model's sweep workspace or line-search rows and cost block need more than 160 KB "
+                                  "of LDS", -3);
+  if ((size_t)p->B * (p->H + 1) * nxw >= ((size_t)1 << 31)) return ilqr_linear_table_fail("the plan's state regions exceed 2^31 values");
+  HIP_OK(hipSetDevice(h->device));
+  // Pack every entry from its handle's exact f64 [A | B]: the fragments in set_linear_wide's order, the plain rows, the
+  // sweep's zero-padded jp [nxp][ldj] -- into buffers of this call, installed only once everything is on the device.
+  std::vector<size_t> off(n_models + 1, 0);
+  for (int i = 0; i < n_models; ++i) off[i] = (size_t)lay_off[3 * i];
+  off[n_models] = (size_t)lay[7];
+  std::vector<double> buf(off[n_models], 0.0);
+  DevBuf nbuf, ntab, nrules, nprog;
+  struct Drop { DevBuf* b[4]; bool armed = true; ~Drop() { if (armed) for (DevBuf* x : b) x->release(); } } drop{{&nbuf, &ntab, &nrules, &nprog}};
+  HIP_OK(nbuf.reserve(buf.size() * 8));
+  std::vector<LinDev<double>> tab(n_models);
+  for (int i = 0; i < n_models; ++i) {
+    const std::vector<double>& ab = models[i]->lin_ab_host;
+    const int nx = models[i]->nx, k = nx + nu, nxp = round_up(nx, 16), kp = round_up(k, 4), ntile = nxp / 16, ksn = kp / 4;
+    const int ldj = round_up(k, 16), plain_sz = round_up(nx * k, 4);
+    double* wf = buf.data() + off[i];
+    auto Mat = [&](int row, int col) -> double { return (row >= nx || col >= k) ? 0.0 : ab[(size_t)row * k + col]; };
+    for (int nt = 0; nt < ntile; ++nt)
+      for (int ks = 0; ks < ksn; ++ks)
+        for (int l = 0; l < 64; ++l) wf[((size_t)nt * ksn + ks) * 64 + l] = Mat(16 * nt + (l & 15), 4 * ks + (l >> 4));
+    double* plain = buf.data() + lay_off[3 * i + 1];
+    for (size_t e = 0; e < (size_t)nx * k; ++e) plain[e] = ab[e];
+    double* jp = buf.data() + lay_off[3 * i + 2];
+    for (int r = 0; r < nx; ++r)
+      for (int c = 0; c < k; ++c) jp[(size_t)r * ldj + c] = ab[(size_t)r * k + c];
+    LinDev<double>& m = tab[i];
+    m.nx = nx; m.nu = nu; m.nxp = nxp; m.kp = kp; m.ntile = ntile; m.ksn = ksn;
+    m.wf = (const double*)nbuf.p + off[i];
+    m.plain = (const double*)nbuf.p + lay_off[3 * i + 1];
+    m.jp = (const double*)nbuf.p + lay_off[3 * i + 2]; m.ldj = ldj;
+  }
+  std::vector<int> rl(3 * (size_t)n_models, 0);
+  std::vector<double> prog;
+  for (int i = 0, k = 0; i < n_models; ++i) {
+    rl[i] = rules ? rules[i] : 0;
+    const int nb = rules && rules[i] == 2 ? n_basis[i] : 0;
+    rl[n_models + i] = nb;
+    rl[2 * n_models + i] = lift_off[i];
+    for (int j = 0; j < nb; ++j, ++k) { prog.push_back(lift_kinds[k]); prog.push_back(lift_params[k]); }
+  }
+  HIP_OK(ntab.reserve(tab.size() * sizeof(LinDev<double>)));
+  HIP_OK(nrules.reserve(rl.size() * sizeof(int)));
+  HIP_OK(nprog.reserve((prog.size() + 2) * 8));
+  // (a running solve may read the table being replaced; everything below goes through the plan's OWN stream: the
+  //  handle's stream is non-blocking, so the null stream is not ordered against the plan's kernels)
+  HIP_OK(hipStreamSynchronize(h->stream));
+  HIP_OK(hipMemcpyAsync(nbuf.p, buf.data(), buf.size() * 8, hipMemcpyHostToDevice, h->stream));
+  HIP_OK(hipMemcpyAsync(ntab.p, tab.data(), tab.size() * sizeof(LinDev<double>), hipMemcpyHostToDevice, h->stream));
+  HIP_OK(hipMemcpyAsync(nrules.p, rl.data(), rl.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  if (!prog.empty()) HIP_OK(hipMemcpyAsync(nprog.p, prog.data(), prog.size() * 8, hipMemcpyHostToDevice, h->stream));
+  // the per-slot buffers at the widest entry's stride (grown only; what a solve reads of them it has written before)
+  const int B = p->B, H = p->H, nxs = std::max(nxw, h->nx);
+  HIP_OK(p->states.reserve((size_t)B * std::max<size_t>(lay[0], (size_t)(H + 1) * nxs) * 8));
+  HIP_OK(p->ctrls.reserve((size_t)B * lay[1] * 8));
+  HIP_OK(p->Ks.reserve((size_t)B * std::max<size_t>(lay[2], (size_t)H * nu * nxs) * 8));
+  HIP_OK(p->ks.reserve((size_t)B * lay[3] * 8));
+  HIP_OK(p->ls_states.reserve((size_t)B * std::max<size_t>(lay[4], (size_t)p->ls_n * (H + 1) * nxs) * 8));
+  HIP_OK(p->ls_ctrls.reserve((size_t)B * lay[5] * 8));
+  HIP_OK(p->vj.reserve((size_t)B * lay[6] * 8));
+  HIP_OK(hipMemsetAsync(p->Ks.p, 0, (size_t)B * H * nu * nxs * 8, h->stream));
+  HIP_OK(hipMemsetAsync(p->ks.p, 0, (size_t)B * H * nu * 8, h->stream));
+  HIP_OK(hipStreamSynchronize(h->stream));           // (buf, tab, rl, prog live until here)
+  // complete: the new table in, the old handles back
+  std::swap(p->lqt_buf, nbuf); std::swap(p->lqt_tab, ntab); std::swap(p->lqt_rules, nrules); std::swap(p->lqt_prog, nprog);
+  std::vector<ampc_handle*> old;
+  old.swap(p->lqt_models);
+  p->lqt_models.assign(models, models + n_models);
+  for (ampc_handle* mh : p->lqt_models) mh->refs++;
+  for (ampc_handle* mh : old) handle_release(mh);
+  p->lqt_nx.clear();
+  for (int i = 0; i < n_models; ++i) p->lqt_nx.push_back(models[i]->nx);
+  p->lqt_n = n_models; p->lqt_nxw = nxw; p->lqt_loop = rules != nullptr;
+  p->lqt_lds_xn = lds_xn; p->lqt_lds_work = lds_work; p->lqt_sweep_bytes = sweep_bytes; p->lqt_ls_bytes = ls_bytes;
+  p->static_shape = -1;                              // (no shape-specialised kernel or plugin runs on a table plan)
+  p->jit = nullptr;
+  return 0;                                          // (Drop releases the OLD table's buffers, swapped into the locals)
+}
+
+// simulate() with IterativeLQR controllers on a table of linear models, device resident: ilqr_closed_loop_impl with a
+// surrogate state per slot beside the controller state and the controller-state rules between surrogate step and post.
+static int ilqr_closed_loop_linear_impl(ampc_ilqr_plan* p, ampc_handle* sur, int C, const double* init_states,
+                                        const double* init_sim, const int* cost_index, const int* horizon,
+                                        const int* model_index, int n_steps, int max_iter, double* traj_obs,
+                                        double* traj_ctrls, int* failed, int* steps_done, long long* iterations) {
+  using T = double;
+  ampc_handle* h = p->h;
+  const int nxw = p->lqt_nxw, nu = h->nu, B = p->B, H = p->H, T1 = n_steps + 1, snx = sur->nx, NM = p->lqt_n;
+  const size_t e = sizeof(T), db = ilqr_linear_table_desc_bytes();
+  std::vector<int> x_off(C);
+  size_t sum_nx = 0;
+  for (int c = 0; c < C; ++c) { x_off[c] = (int)sum_nx; sum_nx += p->lqt_nx[model_index ? model_index[c] : 0]; }
+  REQUIRE(sum_nx < ((size_t)1 << 31), "ampc_ilqr_closed_loop_linear: too many states in init_states");
+  HIP_OK(p->q_ctl.reserve((size_t)(2 + 2 * B) * sizeof(int)));
+  // ints: need[B] slot_chain[B] chain_t[C] chain_fail[C] cost[C] horizon[C] model[C] x_off[C]
+  HIP_OK(p->c_ints.reserve((size_t)(2 * B + 6 * C) * sizeof(int)));
+  HIP_OK(p->c_iters.reserve((size_t)C * sizeof(long long)));
+  HIP_OK(p->c_stage.reserve((size_t)B * (nu + snx) * e));                // stage_u [B][nu] | stage_next [B][snx]
+  // sim [B][snx] | sim0 [C][snx] | zero controls [C][nu] (u_prev of the first run())
+  HIP_OK(p->lqt_sim.reserve(((size_t)B * snx + (size_t)C * snx + (size_t)C * nu) * e));
+  HIP_OK(p->lqt_desc.reserve((size_t)(B + C) * db));                     // per slot | per chain (the first run())
+  HIP_OK(p->c_obs.reserve((size_t)C * T1 * snx * e));
+  HIP_OK(p->c_ctl.reserve((size_t)C * T1 * nu * e));
+  HIP_OK(p->q_x0.reserve(sum_nx * e));
+  HIP_OK(p->slot_h.reserve((size_t)B * sizeof(int)));
+  HIP_OK(p->slot_model.reserve((size_t)B * sizeof(int)));
+  std::vector<int> ctl(2 + 2 * B, 0), ci(2 * B + 6 * C, 0), slot_h0(B, H);
+  for (int b = 0; b < B; ++b) { ctl[2 + b] = -1; ctl[2 + B + b] = 1; ci[B + b] = -1; }
+  if (cost_index) std::memcpy(ci.data() + 2 * B + 2 * C, cost_index, (size_t)C * sizeof(int));
+  if (horizon) std::memcpy(ci.data() + 2 * B + 3 * C, horizon, (size_t)C * sizeof(int));
+  if (model_index) std::memcpy(ci.data() + 2 * B + 4 * C, model_index, (size_t)C * sizeof(int));
+  std::memcpy(ci.data() + 2 * B + 5 * C, x_off.data(), (size_t)C * sizeof(int));
+  // the chains' first run(): state <- rule(traj_to_state, u_prev = 0, first observation), all chains in one launch
+  const std::vector<int> rl_host = [&] {
+    std::vector<int> v(3 * (size_t)NM);
+    (void)hipMemcpy(v.data(), p->lqt_rules.p, v.size() * sizeof(int), hipMemcpyDeviceToHost);
+    return v;
+  }();
+  std::vector<char> desc((size_t)(B + C) * db, 0);
+  for (int b = 0; b < B; ++b) ilqr_linear_table_desc_fill(desc.data(), b, 0, 0, 0, 0, 0, 0);
+  for (int c = 0; c < C; ++c) {
+    const int mi = model_index ? model_index[c] : 0;
+    ilqr_linear_table_desc_fill(desc.data(), B + c, p->lqt_nx[mi], rl_host[mi], rl_host[NM + mi], mi, x_off[c], rl_host[2 * NM + mi]);
+  }
+  T* sim = (T*)p->lqt_sim.p; T* sim0 = sim + (size_t)B * snx; T* u_zero = sim0 + (size_t)C * snx;
+  HIP_OK(hipMemcpyAsync(p->slot_h.p, slot_h0.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIP_OK(hipMemsetAsync(p->slot_model.p, 0, (size_t)B * sizeof(int), h->stream));
+  HIP_OK(hipMemcpyAsync(p->q_ctl.p, ctl.data(), ctl.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIP_OK(hipMemcpyAsync(p->c_ints.p, ci.data(), ci.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIP_OK(hipMemcpyAsync(p->lqt_desc.p, desc.data(), desc.size(), hipMemcpyHostToDevice, h->stream));
+  HIP_OK(hipMemsetAsync(p->c_iters.p, 0, (size_t)C * sizeof(long long), h->stream));
+  HIP_OK(hipMemsetAsync(p->c_obs.p, 0, (size_t)C * T1 * snx * e, h->stream));
+  HIP_OK(hipMemsetAsync(p->c_ctl.p, 0, (size_t)C * T1 * nu * e, h->stream));
+  HIP_OK(hipMemsetAsync(p->c_stage.p, 0, (size_t)B * (nu + snx) * e, h->stream));
+  HIP_OK(hipMemsetAsync(p->lqt_sim.p, 0, ((size_t)B * snx + (size_t)C * snx + (size_t)C * nu) * e, h->stream));
+  HIP_OK(upload_converted<T>(p->q_x0.p, init_states, sum_nx, h->stream));
+  HIP_OK(upload_converted<T>(sim0, init_sim, (size_t)C * snx, h->stream));
+  HIP_OK(hipMemsetAsync(p->flags.p, 0, (size_t)9 * B * sizeof(int), h->stream));
+  HIP_OK(hipMemsetAsync(p->states.p, 0, (size_t)B * (H + 1) * nxw * e, h->stream));
+  if (int rc = ilqr_linear_table_ctrl_state(p, C, (const char*)p->lqt_desc.p + (size_t)B * db, (T*)p->q_x0.p, sim0, snx, u_zero))
+    return rc;
+  HIP_OK(hipStreamSynchronize(h->stream));
+  if (p->poll_host) { (void)hipHostFree(p->poll_host); p->poll_host = nullptr; }
+  const int npoll = 2 * B + 3;
+  HIP_OK(hipHostMalloc((void**)&p->poll_host, (size_t)2 * npoll * sizeof(int), hipHostMallocDefault));
+  if (!p->poll_ev[0])
+    for (int i = 0; i < 2; ++i) HIP_OK(hipEventCreateWithFlags(&p->poll_ev[i], hipEventDisableTiming));
+  struct Guard {
+    ampc_ilqr_plan* p;
+    ~Guard() {
+      (void)hipStreamSynchronize(p->h->stream);
+      (void)hipMemcpyAsync(p->d_cost_idx.p, p->cost_idx.data(), (size_t)p->B * sizeof(int), hipMemcpyHostToDevice,
+                           p->h->stream);
+      (void)hipStreamSynchronize(p->h->stream);
+      p->queue_on = false; p->var_h = false; p->var_model = false; p->compact_on = false; p->ev_cur = nullptr;
+      (void)hipHostFree(p->poll_host); p->poll_host = nullptr;
+    }
+  } guard{p};
+  p->queue_on = true;
+  p->var_h = true;                    // (slot_h is always filled here: H without `horizon`)
+  p->var_model = true;
+  p->queue_max_iter = max_iter;
+  p->active_hint = B;
+  p->ls_rb_now = 1;
+  p->compact_on = false;
+  IlqrLinChains q;
+  q.C = C; q.B = B; q.H = H; q.nxw = nxw; q.nu = nu; q.snx = snx; q.n_steps = n_steps; q.max_iter = max_iter;
+  q.ctl = (int*)p->q_ctl.p;
+  int* ints = (int*)p->c_ints.p;
+  q.need = ints; q.slot_chain = ints + B; q.chain_t = ints + 2 * B; q.chain_fail = ints + 2 * B + C;
+  q.cost = ints + 2 * B + 2 * C;
+  q.horizon = horizon ? ints + 2 * B + 3 * C : nullptr; q.slot_h = (int*)p->slot_h.p;
+  q.model = ints + 2 * B + 4 * C; q.slot_model = (int*)p->slot_model.p;
+  q.x_off = ints + 2 * B + 5 * C;
+  const int* rl = (const int*)p->lqt_rules.p;
+  q.rule = rl; q.n_basis = rl + NM; q.lift_off = rl + 2 * NM;
+  q.chain_iters = (long long*)p->c_iters.p;
+  q.x0 = (const T*)p->q_x0.p; q.sim0 = sim0; q.cost_idx = (int*)p->d_cost_idx.p;
+  q.sim = sim; q.stage_u = (T*)p->c_stage.p; q.stage_next = q.stage_u + (size_t)B * nu;
+  q.desc = (LinCtrlDesc*)p->lqt_desc.p;
+  q.traj_obs = (T*)p->c_obs.p; q.traj_ctrls = (T*)p->c_ctl.p;
+  constexpr int kPoll = 4;
+  const long long bound = ((long long)(C + B - 1) / B) * n_steps * (max_iter + 2LL) + (long long)C + 4 * kPoll;
+  long long it = 0;
+  int batch = 0, pending = -1;
+  bool done = false;
+  while (!done && it < bound) {
+    for (int k = 0; k < kPoll; ++k) {
+      IlqrArgs<T> a = make_ilqr_args<T>(p, 1);
+      if (int rc = ilqr_linear_table_chain_pre(p, &a, &q)) return rc;
+      if (int rc = surrogate_step<T>(h, sur, q.sim, q.stage_u, q.stage_next, B)) return rc;
+      if (int rc = ilqr_linear_table_ctrl_state(p, B, p->lqt_desc.p, (T*)p->states.p, q.stage_next, snx, q.stage_u)) return rc;
+      if (int rc = ilqr_linear_table_chain_post(p, &a, &q)) return rc;
+      int rc = ilqr_launch_iter<T>(p, 1);
+      if (rc == 0) rc = ilqr_refresh_jacobians<T>(p);
+      if (rc) { (void)hipStreamSynchronize(h->stream); return rc; }
+    }
+    it += kPoll;
+    const int slot = batch & 1;
+    int* ph = p->poll_host + (size_t)slot * npoll;
+    HIP_OK(hipMemcpyAsync(ph, (const int*)p->flags.p + B, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIP_OK(hipMemcpyAsync(ph + B, (const int*)p->flags.p + 8 * B, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIP_OK(hipMemcpyAsync(ph + 2 * B, p->q_ctl.p, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIP_OK(hipEventRecord(p->poll_ev[slot], h->stream));
+    if (pending >= 0) {
+      const int* pp = p->poll_host + (size_t)(pending & 1) * npoll;
+      HIP_OK(hipEventSynchronize(p->poll_ev[pending & 1]));
+      if (pp[2 * B + 1] >= C) done = true;
+    }
+    pending = batch++;
+  }
+  HIP_OK(hipStreamSynchronize(h->stream));
+  p->last_queue_launches = it;
+  p->last_iterations = (int)std::min<long long>(it, 1 << 30);
+  int fin[2] = {0, 0};
+  HIP_OK(hipMemcpy(fin, p->q_ctl.p, sizeof(fin), hipMemcpyDeviceToHost));
+  if (fin[1] < C) return fail("ampc_ilqr_closed_loop_linear: internal: the chains did not finish");
+  std::vector<int> back((size_t)2 * B + 2 * C);
+  HIP_OK(hipMemcpy(back.data(), p->c_ints.p, back.size() * sizeof(int), hipMemcpyDeviceToHost));
+  if (steps_done) std::memcpy(steps_done, back.data() + 2 * B, (size_t)C * sizeof(int));
+  if (failed) std::memcpy(failed, back.data() + 2 * B + C, (size_t)C * sizeof(int));
+  if (iterations) HIP_OK(hipMemcpy(iterations, p->c_iters.p, (size_t)C * sizeof(long long), hipMemcpyDeviceToHost));
+  if (traj_obs) HIP_OK(download_converted<T>(traj_obs, p->c_obs.p, (size_t)C * T1 * snx, h->stream));
+  if (traj_ctrls) HIP_OK(download_converted<T>(traj_ctrls, p->c_ctl.p, (size_t)C * T1 * nu, h->stream));
+  return 0;
+}
+
+extern "C" int ampc_ilqr_closed_loop_linear(ampc_ilqr_plan* p, ampc_handle* surrogate, int n_chains,
+                                            const double* init_states, const double* init_sim, const int* cost_index,
+                                            const int* horizon, const int* model_index, int n_steps, int max_iter,
+                                            double* traj_obs, double* traj_ctrls, int* failed, int* steps_done,
+                                            long long* iterations) {
+  static const std::string w = "ampc_ilqr_closed_loop_linear";
+  REQUIRE(p && init_states && init_sim, w + ": NULL argument");
+  REQUIRE(p->lqt_n > 0, w + ": the plan holds no table of linear models (ampc_ilqr_plan_set_linear_models)");
+  REQUIRE(p->lqt_loop, w + ": the table was set without rules (solves only)");
+  REQUIRE(n_chains >= 1 && n_steps >= 1 && max_iter >= 1, w + ": n_chains, n_steps, max_iter must be >= 1");
+  if (int rc = check_horizons(p, n_chains, horizon, "ampc_ilqr_closed_loop_linear")) return rc;
+  if (int rc = check_models(p, n_chains, model_index, "ampc_ilqr_closed_loop_linear")) return rc;
+  const ampc_handle* h = p->h;
+  ampc_handle* sur = surrogate ? surrogate : p->h;
+  REQUIRE(sur->has_model() && sur->nu == h->nu && sur->nx >= h->obs_dim,
+          w + ": the surrogate must have the plan's controls and a state that starts with the observation");
+  REQUIRE(sur->precision == h->precision && sur->device == h->device,
+          w + ": surrogate must share the plan's device and precision");
+  if (cost_index)
+    for (int j = 0; j < n_chains; ++j)
+      REQUIRE(cost_index[j] >= 0 && cost_index[j] < h->n_costs, w + ": bad cost_index");
+  HIP_OK(hipSetDevice(h->device));
+  return ilqr_closed_loop_linear_impl(p, sur, n_chains, init_states, init_sim, cost_index, horizon, model_index, n_steps,
+                                      max_iter, traj_obs, traj_ctrls, failed, steps_done, iterations);
 }

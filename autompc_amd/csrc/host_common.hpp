@@ -640,8 +640,22 @@ struct ampc_ilqr_plan {
   size_t sindy_lds = 0;
   std::vector<ampc_handle*> sindy_models;
   DevBuf sindy_tab;
+  // Linear models of mixed state dimension (ampc_ilqr_plan_set_linear_models, f64): lqt_buf holds every entry's
+  // fragment-order [A | B], plain rows and zero-padded Jacobian, lqt_tab the device table of their LinDev<double>.
+  // lqt_n > 0: the sweep, the line search and the queue's refill are ilqr_linear_table_kernels.hpp's; every per-slot
+  // region keeps the stride of the widest entry (lqt_nxw), a queue problem / episode names its entry, x0 is ragged.
+  // With rules (lqt_loop) ampc_ilqr_closed_loop_linear is allowed: per-entry rule / basis / lift records on the
+  // device (lqt_rules: rule[n] n_basis[n] lift_off[n]), lqt_prog the lift programs.  The plan keeps the handles alive.
+  int lqt_n = 0, lqt_nxw = 0, lqt_lds_xn = 0, lqt_lds_work = 0;
+  size_t lqt_sweep_bytes = 0, lqt_ls_bytes = 0;
+  bool lqt_loop = false;
+  std::vector<ampc_handle*> lqt_models;
+  std::vector<int> lqt_nx;
+  DevBuf lqt_buf, lqt_tab, lqt_rules, lqt_prog, lqt_xoff, lqt_sim, lqt_desc;
 };
 
+// launch_ilqr_linear_table.cpp (f64 only, not part of a shape plugin)
+int ilqr_linear_table_launch_iter(ampc_ilqr_plan* p, const void* args, int mode, hipEvent_t* e);
 // launch_ilqr_table.cpp (f64 only, not part of a shape plugin)
 int ilqr_table_lds_base();
 int ilqr_table_launch_iter(ampc_ilqr_plan* p, const void* args);
@@ -657,6 +671,7 @@ template <typename T> static IlqrArgs<T> make_ilqr_args(ampc_ilqr_plan* p, int m
   a.mlp = model_of<T>(h);
   if (h->has_sindy) a.sindy = sindy_of<T>(h);
   if (h->has_lin) { a.lin = lin_of<T>(h); a.vj = (T*)p->vj.p; }
+  if (p->lqt_n > 0) a.vj = (T*)p->vj.p;        // (a table of linear models: the sweep's scratch, whatever the handle's form)
   a.lds_xn = p->lds_xn;
   a.lds = p->L;
   a.lds_work = p->lds_work;

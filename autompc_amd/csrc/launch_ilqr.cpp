@@ -9,9 +9,20 @@
 
 template <typename T> int ilqr_launch_iter(ampc_ilqr_plan* p, int mode) {
 #ifndef AMPC_JIT_PLUGIN
-  if (p->var_model && p->table_n == 0 && p->sindy_n == 0 && p->static_shape < 0 && !p->jit)
+  if (p->var_model && p->table_n == 0 && p->sindy_n == 0 && p->lqt_n == 0 && p->static_shape < 0 && !p->jit)
     return fail("iLQR plan: per-slot controller models need the shape-specialised kernels (the run-time-shape kernels "
                 "take one model per plan); call ampc_ilqr_plan_set_models on a plan of a registered / compiled shape");
+  // a table of linear models of mixed state dimension (ampc_ilqr_plan_set_linear_models): sweep and line search of
+  // ilqr_linear_table_kernels.hpp, whatever the staging form of the plan handle's own model
+  if (p->lqt_n > 0) {
+    if constexpr (sizeof(T) == 8) {
+      IlqrArgs<T> ta = make_ilqr_args<T>(p, mode);
+      hipEvent_t* te = mode == 1 ? p->ev_cur : nullptr;
+      if (te) HIP_OK(hipEventRecord(te[0], p->h->stream));
+      return ilqr_linear_table_launch_iter(p, &ta, mode, te);
+    }
+    return fail("internal: a table of linear models on an f32 iLQR plan");
+  }
   if (p->jit) return jit_result(p->jit, p->jit->ilqr_iter(p, mode));
 #endif
   ampc_handle* h = p->h;
@@ -20,7 +31,7 @@ template <typename T> int ilqr_launch_iter(ampc_ilqr_plan* p, int mode) {
   hipEvent_t* e = mode == 1 ? p->ev_cur : nullptr;
   if (e) HIP_OK(hipEventRecord(e[0], h->stream));
 #ifndef AMPC_JIT_PLUGIN
-  if (h->has_lin) {     // wide linear models: ilqr_wide.hpp + the sixteen-row line search on the K-tiled linear step
+  if (h->has_lin) {    // wide linear models: ilqr_wide.hpp + the sixteen-row line search on the K-tiled linear step
     if (mode == 1) {
       const size_t wb = (size_t)make_wide_lds(h->nx, h->nu, h->obs_dim).total * sizeof(T);
 #define AMPC_WIDE_NU(NUV)                                                                          \

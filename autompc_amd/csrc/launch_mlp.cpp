@@ -77,6 +77,10 @@ template <typename T> int ilqr_refresh_jacobians(ampc_ilqr_plan* p) {
 #ifndef AMPC_JIT_PLUGIN
   if (p->table_n > 0) return ilqr_table_refresh(p);       // (a table of MLP models of mixed shapes: launch_ilqr_table.cpp)
   if (p->sindy_n > 0) return ilqr_sindy_table_refresh(p); // (a table of SINDy models: launch_ilqr_sindy_table.cpp)
+  if (p->lqt_n > 0) {             // (a table of linear models: every entry's Jacobian is its constant [A | B])
+    if (p->ev_cur) { HIP_OK(hipEventRecord(p->ev_cur[3], p->h->stream)); HIP_OK(hipEventRecord(p->ev_cur[4], p->h->stream)); }
+    return 0;
+  }
   if (p->jit) return jit_result(p->jit, p->jit->ilqr_refresh(p));
 #endif
   ampc_handle* h = p->h;

@@ -251,6 +251,38 @@ def linear_table_decision(candidates, default, precision="f64", device=0, obs_di
     return True, ""
 
 
+ILQR_LINEAR_MAX_STATES = 128               # iLQR on linear models: the value function's Hessian lives in LDS
+ILQR_LINEAR_CTRLS = (1, 2, 3, 4, 6, 8)     # the control dimensions the sweep on linear models is built for
+
+
+def ilqr_linear_table_decision(candidates, default, precision="f64", device=0, obs_dim=None, ctrl_dim=None):
+    """(True, "") when ONE iLQR plan with a table of linear models (IlqrPlan.set_linear_models) takes the whole batch,
+    else (False, why): ``linear_table_decision`` in f64 -- every candidate's controller model (`default`, the evaluator's
+    own, for a candidate without a "model") is a trained ``sysid.ARX`` or ``sysid.Koopman`` of the evaluator's system and
+    device whose controller-state rule the device has -- with at most 128 states per model and a control dimension the
+    sweep is built for (1, 2, 3, 4, 6 or 8).  The plan handle is a model of obs_dim states, staged as an identity network
+    (obs_dim + ctrl_dim <= 63) or wide (obs_dim > 64); an observation dimension between the two is refused.  Needs no
+    GPU."""
+    if precision != "f64":
+        return False, "the table kernels are f64 only"
+    ok, why = linear_table_decision(candidates, default, precision, device, obs_dim)
+    if not ok:
+        return ok, why
+    system = getattr(default, "system", None)
+    no = int(obs_dim) if obs_dim is not None else int(system.obs_dim)
+    nu = int(ctrl_dim) if ctrl_dim is not None else int(system.ctrl_dim)
+    if nu not in ILQR_LINEAR_CTRLS:
+        return False, "the sweep on linear models is built for 1, 2, 3, 4, 6 or 8 controls, not %d" % nu
+    for c in candidates:
+        m = c.get("model") if isinstance(c, dict) else None
+        m = default if m is None else m
+        if int(m.state_dim) > ILQR_LINEAR_MAX_STATES:
+            return False, "a candidate's model has %d states, more than %d" % (int(m.state_dim), ILQR_LINEAR_MAX_STATES)
+    if no > ILQR_LINEAR_MAX_STATES or 63 - nu < no <= 64:
+        return False, "no plan handle of %d observations and %d controls can be staged" % (no, nu)
+    return True, ""
+
+
 def _needs_specialised_kernels(err):
     """The library's refusal of a model TABLE on a plan that runs the run-time-shape kernels (several models of one
     unregistered shape whose plugin is not built -- and, for one-evaluation models, never will be)."""
@@ -1022,7 +1054,8 @@ class IlqrCandidateEvaluator:
     accepts_global_ids = True
 
     def __init__(self, system, task, model, surrogate=None, precision="f64", device=0, device_resident=True,
-                 max_slots=1024, max_threads=32, one_plan=True, mlp_models="shape", sindy_models="single"):
+                 max_slots=1024, max_threads=32, one_plan=True, mlp_models="shape", sindy_models="single",
+                 linear_models="shape"):
         """device_resident: episodes of known length run entirely on the device (ampc_ilqr_closed_loop_var;
         a user termination condition is asked on the host, one queue of solves per control step);
         max_slots: problems solved side by side (one workgroup each);
@@ -1039,7 +1072,15 @@ class IlqrCandidateEvaluator:
         own handles (IlqrPlan.set_sindy_models: the line search and the Jacobians of
         csrc/ilqr_sindy_table_kernels.hpp) whenever ``ilqr_sindy_table_decision`` allows it, the default way
         otherwise; a plan whose table does not fit the kernel's LDS runs one plan per model (one_plan=False:
-        refused).  ``last_models`` then reads {"path": "sindy_table", "models": n, "plans": 1} or {"path": "model", ...}."""
+        refused).  ``last_models`` then reads {"path": "sindy_table", "models": n, "plans": 1} or {"path": "model", ...}.
+        linear_models: "shape" -- an ARX model scores candidates only as its own surrogate, Koopman models not at all
+        (the TypeError below), and models of different state dimensions run in a plan each (the default); "table" --
+        ARX / Koopman controller models of any mix of state dimensions run in ONE plan on a device table
+        (IlqrPlan.set_linear_models: the sweep and line search of csrc/ilqr_linear_table_kernels.hpp) against ANY
+        surrogate, every controller state following its own model's update_state rule, whenever
+        ``ilqr_linear_table_decision`` allows it; otherwise, and when the widest entry does not fit the kernels' LDS, the
+        default way takes the batch, its refusals included (one_plan=False: refused).  ``last_models`` then reads
+        {"path": "linear_table", "models": n, "plans": 1}."""
         self.device_resident, self.max_slots, self.max_threads = bool(device_resident), int(max_slots), max(1, int(max_threads))
         self.one_plan = bool(one_plan)
         if mlp_models not in ("shape", "table"):
@@ -1052,6 +1093,11 @@ class IlqrCandidateEvaluator:
         if sindy_models == "table" and not self.one_plan:
             raise ValueError('sindy_models="table" puts every candidate into one plan: it needs one_plan=True')
         self.sindy_models = sindy_models
+        if linear_models not in ("shape", "table"):
+            raise ValueError('linear_models must be "shape" or "table", not %r' % (linear_models,))
+        if linear_models == "table" and not self.one_plan:
+            raise ValueError('linear_models="table" puts every candidate into one plan: it needs one_plan=True')
+        self.linear_models = linear_models
         self.last_models = None
         self._table = False
         self._sindy_table = False
@@ -1066,12 +1112,17 @@ class IlqrCandidateEvaluator:
         # whose update_state reproduces its own prediction (ARX: the stacked history, arx.py:94-99,113-127;
         # up to 128 states, csrc/ilqr_wide.hpp).  Koopman re-lifts every observation (koopman.py:166-168):
         # score such candidates with simulate() and the drop-in controller.
+        # (with linear_models="table" the table's closed loop runs every model's own rule: evaluate() raises this
+        #  refusal for a batch that does not take the table)
+        self._no_device_loop = None
         if model.state_dim != system.obs_dim and not (getattr(model, "device_closed_loop", False)
                                                      and self.surrogate is model):
-            raise TypeError("IlqrCandidateEvaluator carries the model state from one solve to the next: the "
-                            "observation itself (MLP, SINDy) or the state of a model that is its own surrogate "
-                            "(ARX); score %s candidates with simulate() and the drop-in controller"
-                            % type(model).__name__)
+            self._no_device_loop = ("IlqrCandidateEvaluator carries the model state from one solve to the next: the "
+                                    "observation itself (MLP, SINDy) or the state of a model that is its own surrogate "
+                                    "(ARX); score %s candidates with simulate() and the drop-in controller"
+                                    % type(model).__name__)
+            if linear_models != "table":
+                raise TypeError(self._no_device_loop)
         self.precision, self.device = precision, device
         self.bounded = bool(task.are_ctrl_bounded())
         b = task.get_ctrl_bounds()
@@ -1133,6 +1184,23 @@ class IlqrCandidateEvaluator:
                 return CandidateEvaluator._evaluate_shape_groups(
                     self, by_model, candidates, global_ids(index_offset, B),
                     dict(n_steps=n_steps, init_obs=init_obs, return_trajectories=return_trajectories, max_iter=max_iter))
+        if self.linear_models == "table" and not self._table and not self._sindy_table:
+            ok, _why = ilqr_linear_table_decision(candidates, self.model, self.precision, self.device,
+                                                  self.system.obs_dim, self.system.ctrl_dim)
+            if ok:
+                opened = []
+                try:
+                    out = self._evaluate_linear_table(candidates, n_steps, init_obs, return_trajectories, int(max_iter),
+                                                      opened)
+                    self.last_models = {"path": "linear_table", "models": n_models, "plans": 1}
+                    return out
+                except _lib.AmpcError as e:
+                    if e.code != _lib.ILQR_TABLE_NO_FIT:      # (the widest entry's LDS need: the default way takes the batch)
+                        raise
+                finally:
+                    _close_or_defer(self, opened)
+        if self._no_device_loop is not None:
+            raise TypeError(self._no_device_loop)
         shape_groups = _by_model_shape(candidates, self.model)
         self.last_models = {"path": "shape", "models": n_models,
                             "plans": 1 if shape_groups is None else len(shape_groups)}
@@ -1286,6 +1354,117 @@ class IlqrCandidateEvaluator:
                     sel = idx[go]
                     ctl[sel, t] = u[go]
                     obs[sel, t + 1] = nxt
+            if term_cond is not None:
+                for i in np.nonzero(alive)[0]:
+                    rows_c = ctl[i, :t + 2].copy()
+                    rows_c[t + 1] = 0.0
+                    if term_cond(Trajectory(self.system, t + 2, obs[i, :t + 2, :no].copy(), rows_c)):
+                        lengths[i] = t + 2
+                        alive[i] = False
+        try:
+            terms = cost_terms(self.task.get_cost(), no, nu)
+        except TypeError:
+            terms = None
+        scores = np.full(B, np.inf)
+        ok = ~failed
+        for L in np.unique(lengths[ok]):
+            idx = np.nonzero(ok & (lengths == L))[0]
+            o, c = obs[idx, :L].copy(), ctl[idx, :L].copy()
+            c[:, L - 1] = 0.0                       # simulate()'s trailing zero control row
+            if terms is not None:
+                scores[idx] = sur.score_trajectories(terms, o, c, obs_dim=no)
+            else:
+                scores[idx] = score_trajectories(self.task.get_cost(), o[:, :, :no], c)
+            obs[idx, L:], ctl[idx, L - 1] = np.nan, 0.0
+            ctl[idx, L:] = np.nan
+        self.last_lengths = lengths
+        if return_trajectories:
+            Lmax = int(lengths.max())
+            return scores, obs[:, :Lmax], ctl[:, :Lmax]
+        return scores
+
+    def _evaluate_linear_table(self, candidates, n_steps, init_obs, return_trajectories, max_iter, opened):
+        """The whole batch in ONE plan on a table of the candidates' ARX / Koopman models (IlqrPlan.set_linear_models).
+        The plan handle holds a model of obs_dim states that no problem runs on -- it gives the plan its controls,
+        observation, cost blocks, bounds and stream; the table comes from the models' own handles.  Every controller
+        state starts from its model's traj_to_state, the surrogate's from the surrogate's.  Known-length episodes run on
+        the device (IlqrPlan.closed_loop_linear: the models' update_state rules on the device); with a user term_cond a
+        control step is each model's own update_state on the host, one solve_queue on the table and the surrogate's
+        pred_batch.  Scores come from the recorded surrogate observations."""
+        from ..trajectory import Trajectory
+        from .lqr_eval import device_rule
+        nu, no = self.system.ctrl_dim, self.system.obs_dim
+        snx = int(self.surrogate.state_dim)
+        B = len(candidates)
+        if n_steps is not None:
+            n_ctl, term_cond = int(n_steps), None
+        else:
+            max_steps, term_cond = episode_of(self.task)
+            n_ctl = default_episode_controls(self.task) if term_cond is None else max_steps
+        init_obs = np.asarray(self.task.get_init_obs() if init_obs is None else init_obs, dtype=np.float64)
+        models, index = candidate_models(candidates, self.model)
+        h = _lib.Handle(self.device, self.precision, jit=False)
+        opened.append(h)
+        h.set_linear(np.zeros((no, no)), np.zeros((no, nu)))
+        handles = [model_handle(m, self.device, self.precision, opened) for m in models]
+        blocks, term_goal = candidate_cost_blocks(candidates, self.goal, no, nu)
+        h.set_cost_blocks(**blocks)
+        if self.bounded:
+            h.set_ctrl_bounds(self.umin, self.umax)
+        sur = _lib.Handle(self.device, self.precision)
+        opened.append(sur)
+        self.surrogate.stage_into(sur)
+        hz_all = np.array([int(c["horizon"]) for c in candidates], dtype=np.int32)
+        slots = min(B, self.max_slots)
+        plan = _lib.IlqrPlan(h, slots, int(hz_all.max()), self.system.dt, cost_index=np.arange(slots),
+                             clip_to_bounds=self.bounded, terminal_goal=term_goal)
+        opened.append(plan)
+        rules = [device_rule(m, no) for m in models]
+        plan.set_linear_models(handles, [r[0] for r in rules], [r[1] for r in rules])
+        # the states of the one-row trajectory simulate() starts from (simulation.py:44-47)
+        one_row = Trajectory(self.system, 1, init_obs[None, :no].copy(), np.zeros((1, nu)))
+        if init_obs.shape == (snx,) and snx != no:
+            sim0 = init_obs
+        else:
+            sim0 = np.asarray(self.surrogate.traj_to_state(one_row), dtype=np.float64)
+        per_model = [np.asarray(m.traj_to_state(one_row), dtype=np.float64) for m in models]
+        obs = np.full((B, n_ctl + 1, snx), np.nan)
+        ctl = np.full((B, n_ctl + 1, nu), np.nan)
+        obs[:, 0] = sim0
+        lengths = np.full(B, n_ctl + 1)
+        failed = np.zeros(B, dtype=bool)          # singular Quu: the reference's LinAlgError -> inf
+        cost_index = np.arange(B)
+        if term_cond is None and n_ctl >= 1 and self.device_resident:
+            out = plan.closed_loop_linear(sur, [per_model[int(k)] for k in index], np.tile(sim0, (B, 1)), n_ctl,
+                                          cost_index=cost_index, max_iter=max_iter, horizon=hz_all, model_index=index)
+            failed = out["failed"] != 0
+            obs, ctl = out["obs"], out["ctrls"]
+            self.last_iterations = np.asarray(out["iterations"], dtype=np.int64)
+            n_ctl_host = 0
+        else:
+            n_ctl_host = n_ctl
+        states = [per_model[int(k)].copy() for k in index]
+        u_prev = np.zeros((B, nu))
+        alive = np.ones(B, dtype=bool)
+        for t in range(n_ctl_host):
+            if not alive.any():
+                break
+            # IterativeLQR.run: state <- model.update_state(state, u_prev, new observation), then the solve (finished
+            # candidates keep their slot: the solve is per problem, their result is unused)
+            for i in np.nonzero(alive)[0]:
+                states[i] = np.asarray(models[int(index[i])].update_state(states[i], u_prev[i], obs[i, t, :no]),
+                                       dtype=np.float64)
+            out = plan.solve_queue(states, None, cost_index, max_iter=max_iter, gains=False, horizon=hz_all,
+                                   model_index=index)
+            u = out["ctrls"][:, 0]                    # u = ubar_0 + K_0 (x - xbar_0) with x = xbar_0
+            bad = alive & (out["status"] == 1)
+            failed[bad] = True
+            alive[bad] = False
+            go = np.nonzero(alive)[0]
+            if go.size:
+                obs[go, t + 1] = sur.pred_batch(obs[go, t], u[go])
+                ctl[go, t] = u[go]
+                u_prev[go] = u[go]
             if term_cond is not None:
                 for i in np.nonzero(alive)[0]:
                     rows_c = ctl[i, :t + 2].copy()

@@ -178,7 +178,7 @@ class BatchPipelineTuner:
             draw_cfg = getattr(self.model_factory, "sample_configuration", None)
             default = sample_mlp_config
             if draw_cfg is None and getattr(self.evaluator, "linear_models", None) == "table":
-                # an MPPI evaluator that runs ARX / Koopman models of mixed sizes in one plan: their own sub-spaces
+                # an MPPI or iLQR evaluator that runs ARX / Koopman models of mixed sizes in one plan: their own sub-spaces
                 from ..sysid.linear import ARXFactory, KoopmanFactory
                 if isinstance(self.model_factory, ARXFactory):
                     default = sample_arx_config

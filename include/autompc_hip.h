@@ -46,7 +46,8 @@ int ampc_version(void);   /* 100 * major + minor; 104: + ampc_mppi_run_legacy; 1
                            * 111: + ampc_kstep_errors_linear; 112: + ampc_kstep_errors_sindy;
                            * 113: + ampc_sindy_fit; 114: + ampc_lasso_fit; + ampc_stable_fit, + ampc_mlpfit_*, + ampc_kstep_errors_mlp,
                            *      + ampc_mppi_plan_set_model_table, + ampc_ilqr_plan_set_model_table, + ampc_mppi_plan_set_sindy_models,
-                           *      + ampc_ilqr_plan_set_sindy_models, + ampc_mppi_plan_set_linear_models, + ampc_mppi_closed_loop_linear
+                           *      + ampc_ilqr_plan_set_sindy_models, + ampc_mppi_plan_set_linear_models, + ampc_mppi_closed_loop_linear,
+                           *      + ampc_ilqr_plan_set_linear_models, + ampc_ilqr_closed_loop_linear, + ampc_ilqr_linear_table_layout
                            *      (no bump: callers detect them by their symbols) */
 int ampc_device_count(void);
 
@@ -570,6 +571,53 @@ int ampc_ilqr_plan_set_model_table(ampc_ilqr_plan* p, int n_models, const int* n
  * only once it is complete.  Deterministic: a problem's results are the same bits alone, in any plan, in any slot, at
  * any position of the table.  (Added without a version bump: callers detect it by its symbol.) */
 int ampc_ilqr_plan_set_sindy_models(ampc_ilqr_plan* p, int n_models, ampc_handle* const* models);
+
+/* Linear models x' = A x + B u of MIXED state dimension (ARX histories, Koopman lifts) in one f64 iLQR plan: the slot of
+ * a problem / episode runs on models[model_index[n]] of ampc_ilqr_solve_queue_var / ampc_ilqr_closed_loop_linear (range-
+ * checked; NULL runs models[0]).  models[n_models]: handles staged with ampc_set_linear, either staging form; every
+ * entry is packed from the handle's exact f64 [A | B].  The plan handle -- a linear model as well -- supplies nu,
+ * obs_dim, the cost blocks, the bounds and the stream.  rules / n_basis / lift_kinds / lift_params: exactly
+ * ampc_mppi_plan_set_linear_models' (rule 0 the observation, 1 the ARX shift, 2 a lift); rules == NULL: a table for
+ * solves only, ampc_ilqr_closed_loop_linear is then refused.  n_models == 0 removes the table and restores the plan as it
+ * was built.  The sweep and the line search are csrc/ilqr_linear_table_kernels.hpp's.
+ * Layout with a table: every per-problem region of x0-independent outputs keeps the stride of the plan's horizon and of
+ * the WIDEST entry (nxw = max nx); inside its region a problem's rows are packed at its OWN nx, the rest is zero:
+ *   x0 of ampc_ilqr_solve_queue_var is ragged, problem j's own nx values, concatenated;
+ *   states [P][(H+1) * nxw], Ks [P][H * nu * nxw] hold (H_j+1) x nx_j and H_j x nu x nx_j packed values each.
+ * Refused with a message: NULL arguments; an f32 plan or model; a plan handle or a model handle without a linear model;
+ * models of another control dimension or device; nx < obs_dim; more than 128 states; nu not one of 1, 2, 3, 4, 6, 8; a
+ * plan that holds ampc_ilqr_plan_set_models handles, an MLP table or a SINDy table (and those calls on a plan that holds
+ * this table); ampc_ilqr_solve and ampc_ilqr_closed_loop[_var] on a plan that holds this table; and -- return code -3
+ * instead of -1 -- an LDS need above 160 KB for the widest entry.  A replacing call installs the new table only once
+ * it is complete; a refused one leaves the old table working.  Deterministic: a problem's results are the same bits
+ * alone, in any batch, in any slot, at any table position, and the bits of a single-model plan on the wide linear path.
+ * (Added without a version bump: callers detect it by its symbol.) */
+int ampc_ilqr_plan_set_linear_models(ampc_ilqr_plan* p, int n_models, ampc_handle* const* models, const int* rules,
+                                     const int* n_basis, const int* lift_kinds, const double* lift_params);
+
+/* The layout ampc_ilqr_plan_set_linear_models packs and reserves by, without a device call: for models of nx[n_models]
+ * states and nu controls in a plan of B slots, horizon H and ls_n line-search step sizes,
+ *   entry_off [n_models][3]: offsets (in values) of every entry's fragments, plain rows and padded Jacobian in the
+ *     table buffer;
+ *   strides [10]: values per slot of states, ctrls, Ks, ks, ls_states, ls_ctrls and vj -- those of the plan's horizon
+ *     and of the widest entry --, the values in the table buffer, and the LDS bytes of the sweep and of the line search
+ *     for the widest entry with a cost block of obs_dim observations (above 160 KB the table is refused with -3). */
+int ampc_ilqr_linear_table_layout(int n_models, const int* nx, int nu, int obs_dim, int B, int H, int ls_n,
+                                  long long* entry_off, long long* strides);
+
+/* simulate() with IterativeLQR controllers on a plan that holds a table of linear models WITH rules, any surrogate,
+ * device resident: as ampc_ilqr_closed_loop_var, with a slot carrying its episode's surrogate state (surrogate nx wide)
+ * beside the controller state.  Per control step: solve from a zero guess, u = ubar_0, sim <- surrogate.pred(sim, u),
+ * controller state <- rule(state, u, sim[:obs_dim]); the first solve of an episode runs on rule(init state, 0,
+ * init_sim[:obs_dim]), as IterativeLQR.run does.  init_states: ragged, episode c's own nx values (its model's
+ * traj_to_state of the one-row trajectory), concatenated; init_sim [C][surrogate nx]; surrogate: any model with the
+ * plan's controls, precision and device whose state starts with the observation (NULL: the plan handle's own model).
+ * traj_obs [C][n_steps+1][surrogate nx] (row 0: init_sim), traj_ctrls [C][n_steps+1][nu] (last row zero); failed,
+ * steps_done, iterations as ampc_ilqr_closed_loop.  Any output may be NULL.  (Added without a version bump.) */
+int ampc_ilqr_closed_loop_linear(ampc_ilqr_plan* p, ampc_handle* surrogate, int n_chains, const double* init_states,
+                                 const double* init_sim, const int* cost_index, const int* horizon,
+                                 const int* model_index, int n_steps, int max_iter, double* traj_obs,
+                                 double* traj_ctrls, int* failed, int* steps_done, long long* iterations);
 
 /* simulate() with IterativeLQR controllers, device resident (utils/simulation.py:44-63 as eval_cfg drives it,
  * pipeline_tuner.py:222-231; IterativeLQR.run, ilqr.py:267-295: every control step is a full solve from a zero
