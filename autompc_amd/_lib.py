@@ -84,6 +84,9 @@ SIGNATURES = {
     "ampc_mppi_run_legacy": (c_int, [c_void_p, _dp, _dp, POINTER(c_uint32), c_int, c_int, c_double,
                                      POINTER(c_uint32), _ip, _ip, _dp, _dp]),
     "ampc_mppi_plan_info": (c_int, [c_void_p, _ip, _ip, _dp, _dp]),
+    "ampc_mppi_plan_sindy_launch": (c_int, [c_void_p, _ip, _ip, _ip, _ip]),
+    "ampc_mppi_sindy_launch_choice": (c_int, [c_int] * 11 + [ctypes.c_longlong, c_int, c_int, _ip, _ip, _ip, _ip]),
+    "ampc_sindy_pred_lds": (c_int, [c_int] * 9 + [_ip, _ip]),
     "ampc_mppi_plan_set_outputs": (c_int, [c_void_p, c_int]),
     "ampc_mppi_plan_set_timing": (c_int, [c_void_p, c_int]),
     "ampc_mppi_plan_timing": (c_int, [c_void_p, _dp, _dp, _ip]),
@@ -187,6 +190,28 @@ def check(rc):
         err = AmpcError(msg.decode() if msg else "libautompc_hip error %d" % rc)
         err.code = int(rc)
         raise err
+
+
+def sindy_launch_choice(sizes, nu, cost_stride, max_h, num_path, precision="f64", fp_allowed=True, g_forced=0):
+    """ampc_mppi_sindy_launch_choice: MppiPlan.sindy_launch() from sizes alone, without a device.  sizes: (nx, n_feat,
+    n_trig, n_pow, n_mon, n_pool, n_tab) of the model's feature program; num_path: the problems' sample counts."""
+    nx, n_feat, n_trig, n_pow, n_mon, n_pool, n_tab = (int(v) for v in sizes)
+    samples = sum((int(n) + 63) // 64 * 64 for n in np.atleast_1d(num_path))
+    v = [c_int() for _ in range(4)]
+    check(load().ampc_mppi_sindy_launch_choice(int(precision == "f64"), nx, int(nu), n_feat, n_trig, n_pow, n_mon, n_pool,
+                                               n_tab, int(cost_stride), int(max_h), samples, int(bool(fp_allowed)),
+                                               int(g_forced), *[ctypes.byref(x) for x in v]))
+    return {"spread": bool(v[0].value), "lanes": v[1].value, "staged": bool(v[2].value), "lds_bytes": v[3].value}
+
+
+def sindy_pred_lds(sizes, nu, precision="f64"):
+    """ampc_sindy_pred_lds: (staged, LDS bytes) of the prediction kernel for a feature program of these sizes; raises
+    AmpcError where pred_batch refuses the model."""
+    nx, n_feat, n_trig, n_pow, n_mon, n_pool, n_tab = (int(v) for v in sizes)
+    st, lb = c_int(), c_int()
+    check(load().ampc_sindy_pred_lds(int(precision == "f64"), nx, int(nu), n_feat, n_trig, n_pow, n_mon, n_pool, n_tab,
+                                     ctypes.byref(st), ctypes.byref(lb)))
+    return bool(st.value), lb.value
 
 
 def as_f64(a):
@@ -798,6 +823,14 @@ class MppiPlan:
                                            ctypes.byref(fl), ctypes.byref(by)))
         return {"workgroups": wg.value, "samples_per_wg": spw.value, "flops": fl.value,
                 "bytes": by.value}
+
+    def sindy_launch(self):
+        """The rollout kernel solve() launches for this plan on its handle's SINDy model
+        (ampc_mppi_plan_sindy_launch): spread (features over `lanes` lanes per sample) or one thread per sample,
+        whether the feature program is staged in LDS, and the launch's LDS bytes."""
+        v = [c_int() for _ in range(4)]
+        check(self.lib.ampc_mppi_plan_sindy_launch(self._p, *[ctypes.byref(x) for x in v]))
+        return {"spread": bool(v[0].value), "lanes": v[1].value, "staged": bool(v[2].value), "lds_bytes": v[3].value}
 
 
 class IlqrPlan:

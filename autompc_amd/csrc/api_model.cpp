@@ -709,17 +709,40 @@ extern "C" int ampc_mlp_pred_diff_batch(ampc_handle* h, const double* states, co
 // ---------------------------------------------------------------------------------------------
 // SINDy feature-library model
 // ---------------------------------------------------------------------------------------------
+static const char* const kSindyPredNoFit =
+    "ampc_sindy_pred_batch: the SINDy model's per-row columns (states, controls, value table, 64 rows) and its staged "
+    "feature program need more than 160 KB of LDS in sindy_forward_kernel";
+
+// LDS bytes sindy_forward_kernel asks for on a model of these program sizes (no handle, no device); -1 (message set)
+// where ampc_sindy_pred_batch refuses the model.
+extern "C" int ampc_sindy_pred_lds(int f64, int nx, int nu, int n_feat, int n_trig, int n_pow, int n_mon, int n_pool,
+                                   int n_tab, int* staged, int* lds_bytes) {
+  REQUIRE(nx >= 1 && nx <= 64 && nu >= 1 && nu <= kMaxNu && n_feat >= 1 && n_feat <= 4096 && n_tab >= 0 &&
+              n_tab <= kSindyMaxTab && n_trig >= 0 && n_pow >= 0 && n_mon >= 0 && n_pool >= 0,
+          "ampc_sindy_pred_lds: sizes outside what ampc_set_sindy takes");
+  const int esz = f64 ? 8 : 4;
+  const size_t stage = sindy_stage_bytes_of(sindy_prog_elems(nx, n_feat, n_trig, n_pow, n_mon, n_pool, (size_t)esz), n_tab,
+                                            esz, (size_t)kSindyStageBytes);
+  const size_t lb = sindy_forward_lds_bytes(esz, nx, nu, n_tab, stage);
+  if (staged) *staged = stage > 0 ? 1 : 0;
+  if (lds_bytes) *lds_bytes = (int)lb;
+  REQUIRE(lb <= kLdsLimit, kSindyPredNoFit);
+  return 0;
+}
+
 template <typename T>
 static int sindy_pred_impl(ampc_handle* h, const double* states, const double* ctrls, double* out,
                            double* jx, double* ju, int n) {
   const int nx = h->nx, nu = h->nu;
   const SindyDev<T> m = sindy_of<T>(h);
+  // (before any launch or upload: a request beyond what a workgroup can have is refused by name, not by the runtime)
+  const size_t lb = sindy_forward_lds_bytes((int)sizeof(T), nx, nu, h->s_ntab, sindy_stage_bytes<T>(h));
+  REQUIRE(lb <= kLdsLimit, kSindyPredNoFit);
   HIP_OK(h->s_states.reserve((size_t)n * nx * sizeof(T)));
   HIP_OK(h->s_ctrls.reserve((size_t)n * nu * sizeof(T)));
   HIP_OK(h->s_out.reserve((size_t)n * nx * sizeof(T)));
   HIP_OK(upload_converted<T>(h->s_states.p, states, (size_t)n * nx, h->stream));
   HIP_OK(upload_converted<T>(h->s_ctrls.p, ctrls, (size_t)n * nu, h->stream));
-  const size_t lb = (size_t)(2 * nx + nu + h->s_ntab) * 64 * sizeof(T) + sindy_stage_bytes<T>(h);
   HIP_OK(allow_lds(sindy_forward_kernel<T>, lb));
   hipLaunchKernelGGL(sindy_forward_kernel<T>, dim3((n + 63) / 64), dim3(64), lb, h->stream, m,
                      (const T*)h->s_states.p, (const T*)h->s_ctrls.p, (T*)h->s_out.p, n);

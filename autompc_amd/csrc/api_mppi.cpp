@@ -164,6 +164,16 @@ template <typename T> static int plan_build(ampc_mppi_plan* p) {
   p->lds_aseq = round_up(p->lds_cost + h->cost_stride + 3 * nu, 4);
   p->lds_bytes = ((size_t)p->lds_aseq + (size_t)p->max_h * nu) * sizeof(T);
   REQUIRE(p->lds_bytes <= kLdsLimit, "mppi plan: model + horizon do not fit the 160 KB LDS");
+  if (h->has_sindy && !table && !lint) {
+    // what the launch will request (launch_mppi.cpp asks mppi_sindy_choice_host.hpp the same question): the map above
+    // has no staged feature program in it.  A program that does not fit on top of the one-thread kernel's columns is
+    // not staged; only columns that do not fit by themselves are refused.
+    long long tiles = 0;
+    for (int b = 0; b < p->B; ++b) tiles += (p->N[b] + 63) / 64;
+    REQUIRE(mppi_sindy_choice_of<T>(p, tiles * 64).lds_bytes <= kLdsLimit,
+            "mppi plan: the SINDy model's per-sample columns (states, controls, value table, 64 samples) and the cost "
+            "block do not fit the 160 KB LDS, even without the staged feature program");
+  }
   if (p->quad) {
     p->lds_bytes = (size_t)make_q4_lds(nu, m.k1p, m.nxp, m.hpad, m.n_hidden, h->cost_stride, p->max_h).total * sizeof(T);
     p->lds_eps = env_int("AMPC_FUSED_UPDATE", 1) != 0 ? 0 : -1;       // (a flag here: the map has the region)
@@ -1425,6 +1435,46 @@ extern "C" int ampc_mppi_plan_info(const ampc_mppi_plan* p, int* n_workgroups, i
   by += (double)h->esz() * (macs + 0);
   if (flops) *flops = f;
   if (bytes) *bytes = by;
+  return 0;
+}
+
+extern "C" int ampc_mppi_plan_sindy_launch(const ampc_mppi_plan* p, int* spread, int* lanes, int* staged, int* lds_bytes) {
+  REQUIRE(p, "ampc_mppi_plan_sindy_launch: NULL plan");
+  REQUIRE(p->h->has_sindy, "ampc_mppi_plan_sindy_launch: the plan handle's model is not a SINDy model");
+  REQUIRE(p->sindy_n == 0 && p->lint_n == 0 && p->table_n == 0,
+          "ampc_mppi_plan_sindy_launch: the plan holds a table of models; the query describes the single-model launch");
+  const long long samples = (long long)p->n_tiles * 64;
+  const MppiSindyChoice ch = p->h->precision == AMPC_F64 ? mppi_sindy_choice_of<double>(p, samples)
+                                                         : mppi_sindy_choice_of<float>(p, samples);
+  if (spread) *spread = ch.spread;
+  if (lanes) *lanes = ch.lanes;
+  if (staged) *staged = ch.staged;
+  if (lds_bytes) *lds_bytes = (int)ch.lds_bytes;
+  return 0;
+}
+
+// The same decision from sizes alone (no handle, no device): what a plan of `samples` samples and horizon cap max_h
+// on a SINDy model of these program sizes would launch.  -1 (message set) where the plan would be refused.
+extern "C" int ampc_mppi_sindy_launch_choice(int f64, int nx, int nu, int n_feat, int n_trig, int n_pow, int n_mon,
+                                             int n_pool, int n_tab, int cost_stride, int max_h, long long samples,
+                                             int fp_allowed, int g_forced, int* spread, int* lanes, int* staged,
+                                             int* lds_bytes) {
+  REQUIRE(nx >= 1 && nx <= 64 && nu >= 1 && nu <= kMaxNu && n_feat >= 1 && n_feat <= 4096 && n_tab >= 0 &&
+              n_tab <= kSindyMaxTab && n_trig >= 0 && n_pow >= 0 && n_mon >= 0 && n_pool >= 0 && cost_stride >= 0 &&
+              max_h >= 2 && samples >= 1,
+          "ampc_mppi_sindy_launch_choice: sizes outside what ampc_set_sindy / ampc_mppi_plan_create take");
+  const int esz = f64 ? 8 : 4;
+  const size_t stage = sindy_stage_bytes_of(sindy_prog_elems(nx, n_feat, n_trig, n_pow, n_mon, n_pool, (size_t)esz), n_tab,
+                                            esz, (size_t)kSindyStageBytes);
+  const MppiSindyShape s{esz, nx, nu, n_tab, stage, cost_stride, max_h, (samples + 63) / 64 * 64};
+  const MppiSindyChoice ch = mppi_sindy_choice(s, fp_allowed, g_forced, kLdsLimit);
+  if (spread) *spread = ch.spread;
+  if (lanes) *lanes = ch.lanes;
+  if (staged) *staged = ch.staged;
+  if (lds_bytes) *lds_bytes = (int)ch.lds_bytes;
+  REQUIRE(ch.lds_bytes <= kLdsLimit,
+          "ampc_mppi_sindy_launch_choice: the SINDy model's per-sample columns and the cost block do not fit the 160 KB "
+          "LDS, even without the staged feature program");
   return 0;
 }
 

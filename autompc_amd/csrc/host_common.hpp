@@ -30,6 +30,7 @@
 #include "mppi_rollout4.hpp"
 #include "rng_kernels.hpp"
 #include "sindy_kernels.hpp"
+#include "mppi_sindy_choice_host.hpp"
 #include "score_kernels.hpp"
 #include "shapes.hpp"
 
@@ -227,9 +228,8 @@ static const char* const kNeedStatic =
 
 // LDS bytes the kernels need on top of their own regions for the staged feature program
 template <typename T> static size_t sindy_stage_bytes(const ampc_handle* h) {
-  if (h->s_ntab == 0) return 0;
-  const size_t b = sindy_prog_elems(h->nx, h->s_nfeat, h->s_ntrig, h->s_npow, h->s_nmon, h->s_npool, sizeof(T)) * sizeof(T);
-  return b <= (size_t)kSindyStageBytes ? b + 2 * sizeof(T) : 0;
+  return sindy_stage_bytes_of(sindy_prog_elems(h->nx, h->s_nfeat, h->s_ntrig, h->s_npow, h->s_nmon, h->s_npool, sizeof(T)),
+                              h->s_ntab, (int)sizeof(T), (size_t)kSindyStageBytes);
 }
 
 template <typename T> static LinDev<T> lin_of(const ampc_handle* h) {
@@ -503,6 +503,15 @@ struct ampc_mppi_plan {
   std::vector<double> lint_prog_host;                                  // (kind, parameter) pairs of every lifted entry
   DevBuf lint_buf, lint_tab, lint_xoff, lint_desc, lint_prog, lint_uprev;
 };
+
+// The single-model SINDy rollout a plan of `samples` samples (64 x its tiles) launches now (mppi_sindy_choice_host.hpp):
+// from the handle, the plan's horizon cap and AMPC_SINDY_FP / AMPC_SINDY_G as they stand.  The launcher, the check of
+// ampc_mppi_plan_set_geometry and ampc_mppi_plan_sindy_launch all decide here.
+template <typename T> static MppiSindyChoice mppi_sindy_choice_of(const ampc_mppi_plan* p, long long samples) {
+  const ampc_handle* h = p->h;
+  const MppiSindyShape s{(int)sizeof(T), h->nx, h->nu, h->s_ntab, sindy_stage_bytes<T>(h), h->cost_stride, p->max_h, samples};
+  return mppi_sindy_choice(s, env_int("AMPC_SINDY_FP", 1) != 0, env_int("AMPC_SINDY_G", 0), kLdsLimit);
+}
 
 // api_mppi.cpp: (re)compute sindy_lds for the plan's current horizon cap; -3 when an entry's need exceeds the limit
 int mppi_sindy_table_lds(ampc_mppi_plan* p, const char* who);

@@ -187,7 +187,9 @@ int surrogate_step(ampc_handle* h, ampc_handle* sur, const void* x, const void* 
   }
   if (sur->has_sindy) {
     const SindyDev<T> sd = sindy_of<T>(sur);
-    const size_t lb = (size_t)(2 * sur->nx + sur->nu + sur->s_ntab) * 64 * sizeof(T) + sindy_stage_bytes<T>(sur);
+    const size_t lb = sindy_forward_lds_bytes((int)sizeof(T), sur->nx, sur->nu, sur->s_ntab, sindy_stage_bytes<T>(sur));
+    REQUIRE(lb <= kLdsLimit, "surrogate step: the SINDy model's per-row columns and its staged feature program need more "
+                             "than 160 KB of LDS in sindy_forward_kernel");
     HIP_OK(allow_lds(sindy_forward_kernel<T>, lb));
     hipLaunchKernelGGL(sindy_forward_kernel<T>, dim3((B + 63) / 64), dim3(64), lb, h->stream, sd,
                        (const T*)x, (const T*)u, (T*)x_next, B);

@@ -128,18 +128,19 @@ template <typename T> int mppi_solve_impl(ampc_mppi_plan* p) {
     hipLaunchKernelGGL(linear_rollout_kernel<T>, dim3(p->n_tiles), dim3(64 * kLinW), p->lds_bytes, h->stream, a,
                        lin_of<T>(h));
   } else if (h->has_sindy) {
-    const SindyDev<T> sm = sindy_of<T>(h);
-    // features spread over sixteen lanes per sample (sindy_kernels.hpp) when the library is staged in LDS
-    // and has a product table and at most eight states; AMPC_SINDY_FP = 0: one thread per sample
-    const bool fp_allowed = env_int("AMPC_SINDY_FP", 1) != 0;
-    // lanes per sample: all 64 while that still leaves the chip waves to spare, else 32 / 16
-    const long long samples = (long long)p->n_tiles * 64;
-    int G = samples <= 2048 ? 64 : (samples <= 8192 ? 32 : 16);
-    { const int g = env_int("AMPC_SINDY_G", 0); if (g == 16 || g == 32 || g == 64) G = g; }
-    const int hcap = (p->max_h * h->nu + 3) / 4 * 4;
-    const size_t lbf = ((size_t)(64 / G) * (h->nx + h->nu + h->s_ntab + 2 * hcap) + h->cost_stride + 3 * h->nu + 2) * sizeof(T) +
-                       sindy_stage_bytes<T>(h);
-    if (fp_allowed && sm.stage && sm.n_tab > 0 && h->nx <= 8 && lbf <= kLdsLimit) {
+    SindyDev<T> sm = sindy_of<T>(h);
+    // lane-spread (features over 16 / 32 / 64 lanes per sample, sindy_kernels.hpp) or one thread per sample, and the
+    // launch's LDS: decided in mppi_sindy_choice_host.hpp, where ampc_mppi_plan_set_geometry and
+    // ampc_mppi_plan_sindy_launch read the same answer
+    const MppiSindyChoice ch = mppi_sindy_choice_of<T>(p, (long long)p->n_tiles * 64);
+    if (ch.lds_bytes > kLdsLimit)
+      return fail("ampc_mppi_solve: the per-sample columns of this SINDy model (states, controls, value table, 64 samples) "
+                  "and the cost block need more than 160 KB of LDS (the handle's model or cost changed after "
+                  "ampc_mppi_plan_set_geometry?)");
+    const int G = ch.lanes;
+    const size_t lbf = ch.lds_bytes;
+    if (ch.spread) {
+      const int hcap = mppi_sindy_hcap(p->max_h, h->nu);
       const dim3 grid((unsigned)(p->n_tiles * G));
       auto launch = [&](auto kernel) -> int {
         HIP_OK(allow_lds(kernel, lbf));
@@ -153,8 +154,9 @@ template <typename T> int mppi_solve_impl(ampc_mppi_plan* p) {
       else rc = ind ? launch(mppi_rollout_sindy_fp_kernel<T, 16, true>) : launch(mppi_rollout_sindy_fp_kernel<T, 16>);
       if (rc) return rc;
     } else {
-      const size_t lb = ((size_t)(2 * h->nx + h->nu + h->s_ntab) * 64 + h->cost_stride + 3 * h->nu + 2) * sizeof(T) +
-                        sindy_stage_bytes<T>(h);
+      // (columns that fit without the staged program but not with it: the kernel reads the program from global memory)
+      sm.stage = ch.staged;
+      const size_t lb = ch.lds_bytes;
       HIP_OK(allow_lds(mppi_rollout_sindy_kernel<T>, lb));
       hipLaunchKernelGGL(mppi_rollout_sindy_kernel<T>, dim3(p->n_tiles), dim3(64), lb, h->stream, a, sm);
     }

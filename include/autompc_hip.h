@@ -155,6 +155,12 @@ int ampc_sindy_pred_batch(ampc_handle* h, const double* states, const double* ct
                           int n);
 int ampc_sindy_pred_diff_batch(ampc_handle* h, const double* states, const double* ctrls,
                                double* out, double* jx, double* ju, int n);
+/* Dynamic LDS (bytes) that the prediction kernel requests for a SINDy model of these feature-program sizes
+ * (n_tab == 0: direct evaluation), and whether it copies the program to LDS; no handle and no device needed.
+ * Returns -1, with ampc_last_error() naming the staged program, where ampc_sindy_pred_batch refuses the model:
+ * a request beyond the 160 KB a workgroup can have is refused before any launch. */
+int ampc_sindy_pred_lds(int f64, int nx, int nu, int n_feat, int n_trig, int n_pow, int n_mon, int n_pool,
+                        int n_tab, int* staged, int* lds_bytes);
 
 /* ---- cost / bounds ------------------------------------------------------------------------
  * Replaces QuadCost (quad_cost.py:7-51) as read through Cost.eval_* (cost.py:66-213).
@@ -293,6 +299,19 @@ int ampc_mppi_set_x0_dev(ampc_mppi_plan* p, const void* x0_dev);
  * the rollout launch, algorithmic FLOPs and bytes of one solve. */
 int ampc_mppi_plan_info(const ampc_mppi_plan* p, int* n_workgroups, int* samples_per_wg,
                         double* flops, double* bytes);
+/* Which rollout kernel ampc_mppi_solve launches for a plan whose handle holds a SINDy model (read-only; the
+ * launcher takes the same decision from the same function, with AMPC_SINDY_FP / AMPC_SINDY_G as they stand):
+ * spread 1 = features spread over `lanes` (16 / 32 / 64) lanes per sample, 0 = one thread per sample (lanes 1);
+ * staged = the kernel copies the feature program to LDS; lds_bytes = dynamic LDS of the launch, the staged program
+ * included.  A one-thread launch whose columns fit the 160 KB of a workgroup only without the staged program runs
+ * unstaged (staged 0).  Refused for a plan that holds a table of models. */
+int ampc_mppi_plan_sindy_launch(const ampc_mppi_plan* p, int* spread, int* lanes, int* staged, int* lds_bytes);
+/* The same decision from sizes alone (no handle, no device): a plan of `samples` samples (every problem's count
+ * rounded up to 64) and horizon cap max_h on a model of these feature-program sizes; fp_allowed / g_forced stand
+ * for AMPC_SINDY_FP / AMPC_SINDY_G.  Returns -1 where ampc_mppi_plan_create would refuse the plan. */
+int ampc_mppi_sindy_launch_choice(int f64, int nx, int nu, int n_feat, int n_trig, int n_pow, int n_mon, int n_pool,
+                                  int n_tab, int cost_stride, int max_h, long long samples, int fp_allowed,
+                                  int g_forced, int* spread, int* lanes, int* staged, int* lds_bytes);
 
 /* keep_eps_out = 0: do not materialise the clipped noise in HBM (it is only needed by
  * ampc_mppi_download(eps_out); the solve itself keeps it in LDS).  Default 1. */

@@ -27,6 +27,7 @@ def test_every_declared_symbol_is_exported_and_bound(lib_path):
     from autompc_amd import _lib
     names = _declared()
     assert len(names) >= 20
+    assert {"ampc_mppi_plan_sindy_launch", "ampc_mppi_sindy_launch_choice", "ampc_sindy_pred_lds"} <= set(names)
     lib = ctypes.CDLL(lib_path)
     for n in names:
         assert hasattr(lib, n), "libautompc_hip.so does not export %s" % n
