@@ -140,7 +140,9 @@ SIGNATURES = {
     "ampc_lqr_plan_destroy": (c_int, [c_void_p]),
     "ampc_lqr_plan_set_models": (c_int, [c_void_p, POINTER(c_void_p)]),
     "ampc_lqr_gains": (c_int, [c_void_p, _ip, _dp, _dp, _dp, _dp, _ip]),
+    "ampc_lqr_gains_ex": (c_int, [c_void_p, _ip, _dp, _ip, _dp, _dp, _dp, _dp, _ip, _ip]),
     "ampc_lqr_plan_set_loop": (c_int, [c_void_p, _ip, _ip, _ip, _dp, _dp, _dp, _dp]),
+    "ampc_lqr_plan_set_loop_ex": (c_int, [c_void_p, _ip, _ip, _ip, _dp, _dp, _dp, _dp, _ip]),
     "ampc_lqr_closed_loop": (c_int, [c_void_p, c_void_p, _dp, _dp, c_int, _dp, _dp]),
     "ampc_lqr_closed_loop_scored": (c_int, [c_void_p, c_void_p, _dp, _dp, c_int, c_int, _ip, _dp, _dp, _dp, _dp]),
     "ampc_linfit_fit": (c_int, [c_int, c_int, _ip, c_int, c_int, _dp, _dp, c_int, _ip, c_int, _ip, _ip, _dp, _dp, _ip,
@@ -1138,8 +1140,8 @@ def ilqr_linear_table_layout(nx, nu, obs_dim, B, H, ls_n=10):
 
 
 class LqrPlan:
-    """Finite-horizon LQR controllers of B problems (ampc_lqr_*): linear controller models of any state dimension
-    up to 256 in one plan, gains kept on the device for the closed loop.  f64 only."""
+    """LQR controllers of B problems, finite and infinite horizon (ampc_lqr_*): linear controller models of any state
+    dimension up to 256 in one plan, gains kept on the device for the closed loop.  f64 only."""
 
     def __init__(self, models, obs_dim, ctrl_dim, device=0):
         """models: B f64 Handles staged with set_linear (one per problem; the same handle may repeat)."""
@@ -1182,9 +1184,30 @@ class LqrPlan:
         check(self.lib.ampc_lqr_gains(self._p, iptr(hz), dptr(Q), dptr(R), dptr(F), dptr(K), iptr(status)))
         return [K[self.k_off[i]:self.k_off[i + 1]].reshape(nu, self.n[i]) for i in range(B)], status
 
-    def set_loop(self, rules, goal, ctrl_lo, ctrl_hi, lifts=None):
+    def gains_ex(self, horizons, Q, R, F, thresholds=1e-3, max_iters=10000):
+        """gains() with infinite-horizon problems in the same launch (ampc_lqr_gains_ex): horizons[i] == 0 iterates
+        the Riccati step from P = Q until max|dP| <= thresholds[i] (F is not read), at most max_iters[i] steps (up to
+        100000; a step of a 256-state model takes about a millisecond, so lower it where models may not converge).
+        Returns (K list, status [B], iters [B]): status 0 ok, 1 singular / non-finite, 2 not converged (K NaN for 1
+        and 2); iters the Riccati steps performed (horizon + 1 for a finite problem)."""
+        B, no, nu = self.B, self.no, self.nu
+        hz = np.broadcast_to(np.asarray(horizons, dtype=np.int32), (B,)).copy()
+        th = as_f64(np.broadcast_to(np.asarray(thresholds, dtype=np.float64), (B,)))
+        mi = np.broadcast_to(np.asarray(max_iters, dtype=np.int32), (B,)).copy()
+        Q = as_f64(np.broadcast_to(Q, (B, no, no)))
+        R = as_f64(np.broadcast_to(R, (B, nu, nu)))
+        F = as_f64(np.broadcast_to(F, (B, no, no)))
+        K = np.empty(int(self.k_off[-1]))
+        status = np.zeros(B, dtype=np.int32)
+        iters = np.zeros(B, dtype=np.int32)
+        check(self.lib.ampc_lqr_gains_ex(self._p, iptr(hz), dptr(th), iptr(mi), dptr(Q), dptr(R), dptr(F), dptr(K),
+                                         iptr(status), iptr(iters)))
+        return [K[self.k_off[i]:self.k_off[i + 1]].reshape(nu, self.n[i]) for i in range(B)], status, iters
+
+    def set_loop(self, rules, goal, ctrl_lo, ctrl_hi, lifts=None, clip=None):
         """rules [B]: 0 observation, 1 ARX shift, 2 lift; lifts: per problem None or (kinds, params); goal [B][no]
-        (or [no]); ctrl_lo / ctrl_hi [nu]."""
+        (or [no]); ctrl_lo / ctrl_hi [nu]; clip [B] (None: every problem clips): 0 leaves that problem's control
+        unclipped (InfiniteHorizonLQR.run, which also subtracts no goal: give it a zero goal)."""
         B = self.B
         rules = np.asarray(rules, dtype=np.int32).reshape(B).copy()
         nb = np.zeros(B, dtype=np.int32)
@@ -1198,8 +1221,13 @@ class LqrPlan:
         kinds = np.array(kinds + [0], dtype=np.int32)
         params = np.array(params + [0.0])
         goal = as_f64(np.broadcast_to(goal, (B, self.no)))
-        check(self.lib.ampc_lqr_plan_set_loop(self._p, iptr(rules), iptr(nb), iptr(kinds), dptr(params), dptr(goal),
-                                              dptr(as_f64(ctrl_lo)), dptr(as_f64(ctrl_hi))))
+        if clip is None:
+            check(self.lib.ampc_lqr_plan_set_loop(self._p, iptr(rules), iptr(nb), iptr(kinds), dptr(params),
+                                                  dptr(goal), dptr(as_f64(ctrl_lo)), dptr(as_f64(ctrl_hi))))
+            return
+        clip = np.asarray(clip, dtype=np.int32).reshape(B).copy()
+        check(self.lib.ampc_lqr_plan_set_loop_ex(self._p, iptr(rules), iptr(nb), iptr(kinds), dptr(params), dptr(goal),
+                                                 dptr(as_f64(ctrl_lo)), dptr(as_f64(ctrl_hi)), iptr(clip)))
 
     def closed_loop(self, surrogate, init_states, init_sim, n_steps, terms=None, trajectories=True):
         """Episodes of n_steps control steps against `surrogate` (a Handle).  init_states: list of each problem's

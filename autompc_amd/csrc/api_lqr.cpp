@@ -1,5 +1,5 @@
-// api_lqr.cpp -- finite-horizon LQR plans (reference: autompc/control/lqr.py:35-47 _finite_horz_dt_lqr,
-// :139-192 FiniteHorizonLQR): batched Riccati gains of controller models of any state dimension up to 256 in
+// api_lqr.cpp -- LQR plans (reference: autompc/control/lqr.py:35-47 _finite_horz_dt_lqr, :139-192 FiniteHorizonLQR;
+// :22-33 _inf_horz_dt_lqr, :96-136 InfiniteHorizonLQR): batched Riccati gains of controller models of any state dimension up to 256 in
 // one launch, and the device-resident closed loop simulate() runs with those gains (utils/simulation.py:44-63).
 // f64 only; kernels in lqr_kernels.hpp, launchers in launch_lqr.cpp.
 #include "host_common.hpp"
@@ -18,13 +18,16 @@ int lqr_launch_record(hipStream_t st, int B, const void* next, const void* u, vo
 size_t lqr_desc_bytes();
 size_t lqr_loop_desc_bytes();
 void lqr_pack_desc(void* dst, int n, int nu, int no, int horizon, int id, const double* ab, long long ws,
-                   long long cost, long long k);
-void lqr_pack_loop_desc(void* dst, int n, int rule, int n_basis, const double* ab, long long s, long long k,
-                        long long goal, long long lift);
+                   long long cost, long long k, double threshold, int max_iter);
+void lqr_pack_loop_desc(void* dst, int n, int rule, int n_basis, int noclip, const double* ab, long long s,
+                        long long k, long long goal, long long lift);
 
 // horizons as LQRFactory's space (lqr.py:214-224): a Riccati step of a 256-state model is ~70 MFLOP in one
 // workgroup, so 1000 steps hold a compute unit for well under a second
 static constexpr int kLqrPlanMaxN = 256, kLqrPlanMaxNu = 16, kLqrMaxHorizon = 1000;
+// the cap of an infinite-horizon problem's max_iter: at about a millisecond per update of a 256-state model, a
+// workgroup that never converges gives up after a couple of minutes at the latest
+static constexpr int kLqrMaxIterCap = 100000;
 
 struct ampc_lqr_plan {
   int device = 0, B = 0, no = 0, nu = 0;
@@ -35,7 +38,7 @@ struct ampc_lqr_plan {
   std::vector<long long> k_off;         // K [nu][n_i] offsets (doubles), packed in problem order
   long long k_total = 0;
   bool have_gains = false;
-  DevBuf descs, order, ws, cost, kbuf, status;
+  DevBuf descs, order, ws, cost, kbuf, status;   // status: [B] status then [B] update counts
   // closed loop
   bool have_loop = false;
   std::vector<int> rule;
@@ -130,14 +133,27 @@ extern "C" int ampc_lqr_plan_set_models(ampc_lqr_plan* p, ampc_handle* const* mo
   return 0;
 }
 
-extern "C" int ampc_lqr_gains(ampc_lqr_plan* p, const int* horizons, const double* Q, const double* R,
-                              const double* F, double* K, int* status) {
-  REQUIRE(p && horizons && Q && R && F, "ampc_lqr_gains: NULL argument");
-  if (int rc = lqr_check_models(p, "ampc_lqr_gains")) return rc;
+// horizons[i] == 0: infinite horizon (thresholds[i], max_iters[i]); who: the entry point, for the messages
+static int lqr_gains_impl(ampc_lqr_plan* p, const char* who, const int* horizons, const double* thresholds,
+                          const int* max_iters, const double* Q, const double* R, const double* F, double* K,
+                          int* status, int* iters) {
+  if (int rc = lqr_check_models(p, who)) return rc;
   const int B = p->B, no = p->no, nu = p->nu;
-  for (int i = 0; i < B; ++i)
-    REQUIRE(horizons[i] >= 1 && horizons[i] <= kLqrMaxHorizon,
-            "ampc_lqr_gains: horizon must be in 1..1000 (LQRFactory's range, lqr.py:214-224)");
+  const bool ex = thresholds != nullptr;
+  for (int i = 0; i < B; ++i) {
+    if (!ex) {
+      REQUIRE(horizons[i] >= 1 && horizons[i] <= kLqrMaxHorizon,
+              std::string(who) + ": horizon must be in 1..1000 (LQRFactory's range, lqr.py:214-224)");
+      continue;
+    }
+    REQUIRE(horizons[i] >= 0 && horizons[i] <= kLqrMaxHorizon,
+            std::string(who) + ": horizon must be 0 (infinite) or in 1..1000 (LQRFactory's range, lqr.py:214-224)");
+    if (horizons[i] != 0) continue;
+    REQUIRE(std::isfinite(thresholds[i]) && thresholds[i] > 0.0,
+            std::string(who) + ": the threshold of an infinite-horizon problem must be finite and > 0");
+    REQUIRE(max_iters[i] >= 1 && max_iters[i] <= kLqrMaxIterCap,
+            std::string(who) + ": max_iter of an infinite-horizon problem must be in 1..100000");
+  }
   HIP_OK(hipSetDevice(p->device));
   const size_t dsz = lqr_desc_bytes();
   const long long csz = 2LL * no * no + (long long)nu * nu;
@@ -145,16 +161,20 @@ extern "C" int ampc_lqr_gains(ampc_lqr_plan* p, const int* horizons, const doubl
   long long ws = 0;
   for (int i = 0; i < B; ++i) {
     const int n = p->n[i], m = n + nu;
+    const bool inf = horizons[i] == 0;
     lqr_pack_desc(descs.data() + (size_t)i * dsz, n, nu, no, horizons[i], i, (const double*)p->models[i]->lin_ab.p,
-                  ws, (long long)i * csz, p->k_off[i]);
+                  ws, (long long)i * csz, p->k_off[i], inf ? thresholds[i] : 0.0, inf ? max_iters[i] : 0);
     ws += (long long)n * n + (long long)n * m + (long long)m * m;
   }
-  // heaviest problem first: (horizon + 2) * n^3 decides how long a workgroup runs
+  // heaviest problem first: (horizon + 2) * n^3 decides how long a workgroup runs; an infinite-horizon problem's
+  // length is not known before it runs, so it is placed as if it were the longest horizon
   std::vector<int> order(B);
   std::iota(order.begin(), order.end(), 0);
   std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
-    const double wa = (horizons[a] + 2.0) * p->n[a] * p->n[a] * (p->n[a] + nu);
-    const double wb = (horizons[b] + 2.0) * p->n[b] * p->n[b] * (p->n[b] + nu);
+    const double ha = horizons[a] == 0 ? kLqrMaxHorizon : horizons[a];
+    const double hb = horizons[b] == 0 ? kLqrMaxHorizon : horizons[b];
+    const double wa = (ha + 2.0) * p->n[a] * p->n[a] * (p->n[a] + nu);
+    const double wb = (hb + 2.0) * p->n[b] * p->n[b] * (p->n[b] + nu);
     return wa > wb;
   });
   std::vector<double> cost((size_t)B * csz);
@@ -168,25 +188,39 @@ extern "C" int ampc_lqr_gains(ampc_lqr_plan* p, const int* horizons, const doubl
   HIP_OK(p->order.reserve((size_t)B * 4));
   HIP_OK(p->ws.reserve((size_t)ws * 8));
   HIP_OK(p->cost.reserve(cost.size() * 8));
-  HIP_OK(p->status.reserve((size_t)B * 4));
+  HIP_OK(p->status.reserve((size_t)B * 8));
   HIP_OK(hipMemcpyAsync(p->descs.p, descs.data(), descs.size(), hipMemcpyHostToDevice, p->stream));
   HIP_OK(hipMemcpyAsync(p->order.p, order.data(), (size_t)B * 4, hipMemcpyHostToDevice, p->stream));
   HIP_OK(hipMemcpyAsync(p->cost.p, cost.data(), cost.size() * 8, hipMemcpyHostToDevice, p->stream));
   if (int rc = lqr_launch_gains(p->stream, B, p->descs.p, p->order.p, p->ws.p, p->cost.p, p->kbuf.p, p->status.p))
     return rc;
   if (K) HIP_OK(hipMemcpyAsync(K, p->kbuf.p, (size_t)p->k_total * 8, hipMemcpyDeviceToHost, p->stream));
-  std::vector<int> st(B);
-  HIP_OK(hipMemcpyAsync(st.data(), p->status.p, (size_t)B * 4, hipMemcpyDeviceToHost, p->stream));
+  std::vector<int> st(2 * (size_t)B);
+  HIP_OK(hipMemcpyAsync(st.data(), p->status.p, (size_t)B * 8, hipMemcpyDeviceToHost, p->stream));
   HIP_OK(hipStreamSynchronize(p->stream));
-  if (status) std::copy(st.begin(), st.end(), status);
+  if (status) std::copy(st.begin(), st.begin() + B, status);
+  if (iters) std::copy(st.begin() + B, st.end(), iters);
   p->have_gains = true;
   return 0;
 }
 
-extern "C" int ampc_lqr_plan_set_loop(ampc_lqr_plan* p, const int* rules, const int* n_basis, const int* lift_kinds,
-                                      const double* lift_params, const double* goal, const double* ctrl_lo,
-                                      const double* ctrl_hi) {
-  REQUIRE(p && rules && goal && ctrl_lo && ctrl_hi, "ampc_lqr_plan_set_loop: NULL argument");
+extern "C" int ampc_lqr_gains(ampc_lqr_plan* p, const int* horizons, const double* Q, const double* R,
+                              const double* F, double* K, int* status) {
+  REQUIRE(p && horizons && Q && R && F, "ampc_lqr_gains: NULL argument");
+  return lqr_gains_impl(p, "ampc_lqr_gains", horizons, nullptr, nullptr, Q, R, F, K, status, nullptr);
+}
+
+extern "C" int ampc_lqr_gains_ex(ampc_lqr_plan* p, const int* horizons, const double* thresholds,
+                                 const int* max_iters, const double* Q, const double* R, const double* F, double* K,
+                                 int* status, int* iters) {
+  REQUIRE(p && horizons && thresholds && max_iters && Q && R && F, "ampc_lqr_gains_ex: NULL argument");
+  return lqr_gains_impl(p, "ampc_lqr_gains_ex", horizons, thresholds, max_iters, Q, R, F, K, status, iters);
+}
+
+// clip[i] == 0: problem i's control is not clipped (NULL: every problem clips)
+static int lqr_set_loop_impl(ampc_lqr_plan* p, const int* rules, const int* n_basis, const int* lift_kinds,
+                             const double* lift_params, const double* goal, const double* ctrl_lo,
+                             const double* ctrl_hi, const int* clip) {
   if (int rc = lqr_check_models(p, "ampc_lqr_plan_set_loop")) return rc;
   const int B = p->B, no = p->no, nu = p->nu;
   std::vector<double> prog;
@@ -218,7 +252,7 @@ extern "C" int ampc_lqr_plan_set_loop(ampc_lqr_plan* p, const int* rules, const 
   long long s = 0;
   for (int i = 0; i < B; ++i) {
     lqr_pack_loop_desc(descs.data() + (size_t)i * dsz, p->n[i], rules[i], rules[i] == 2 ? n_basis[i] : 0,
-                       (const double*)p->models[i]->lin_ab.p, s, p->k_off[i], (long long)i * no, lift_off[i]);
+                       clip && clip[i] == 0 ? 1 : 0, (const double*)p->models[i]->lin_ab.p, s, p->k_off[i], (long long)i * no, lift_off[i]);
     s += 2LL * p->n[i];
   }
   HIP_OK(hipSetDevice(p->device));
@@ -238,6 +272,20 @@ extern "C" int ampc_lqr_plan_set_loop(ampc_lqr_plan* p, const int* rules, const 
   p->rule.assign(rules, rules + B);
   p->have_loop = true;
   return 0;
+}
+
+extern "C" int ampc_lqr_plan_set_loop(ampc_lqr_plan* p, const int* rules, const int* n_basis, const int* lift_kinds,
+                                      const double* lift_params, const double* goal, const double* ctrl_lo,
+                                      const double* ctrl_hi) {
+  REQUIRE(p && rules && goal && ctrl_lo && ctrl_hi, "ampc_lqr_plan_set_loop: NULL argument");
+  return lqr_set_loop_impl(p, rules, n_basis, lift_kinds, lift_params, goal, ctrl_lo, ctrl_hi, nullptr);
+}
+
+extern "C" int ampc_lqr_plan_set_loop_ex(ampc_lqr_plan* p, const int* rules, const int* n_basis,
+                                         const int* lift_kinds, const double* lift_params, const double* goal,
+                                         const double* ctrl_lo, const double* ctrl_hi, const int* clip) {
+  REQUIRE(p && rules && goal && ctrl_lo && ctrl_hi, "ampc_lqr_plan_set_loop_ex: NULL argument");
+  return lqr_set_loop_impl(p, rules, n_basis, lift_kinds, lift_params, goal, ctrl_lo, ctrl_hi, clip);
 }
 
 static int lqr_closed_loop_impl(ampc_lqr_plan* p, ampc_handle* sur, const double* init_state,

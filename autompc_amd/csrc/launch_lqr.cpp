@@ -2,7 +2,8 @@
 #include "host_common.hpp"
 #include "lqr_kernels.hpp"
 
-// Riccati gains of n problems, descriptors and launch order already on the device.
+// Riccati gains of n problems, descriptors and launch order already on the device.  status [2 n]: status, then the
+// Riccati updates performed.
 int lqr_launch_gains(hipStream_t st, int n, const void* descs, const void* order, void* ws, const void* cost,
                      void* kout, void* status) {
   hipLaunchKernelGGL(lqr_gains_kernel, dim3(n), dim3(kLqrThreads), 0, st, (const LqrDesc*)descs,
@@ -36,17 +37,18 @@ size_t lqr_loop_desc_bytes() { return sizeof(LqrLoopDesc); }
 
 // host-side descriptor packing (the layouts live with the kernels)
 void lqr_pack_desc(void* dst, int n, int nu, int no, int horizon, int id, const double* ab, long long ws,
-                   long long cost, long long k) {
+                   long long cost, long long k, double threshold, int max_iter) {
   LqrDesc d{};
   d.n = n; d.nu = nu; d.no = no; d.horizon = horizon; d.id = id;
   d.ab = ab; d.ws = ws; d.cost = cost; d.k = k;
+  d.threshold = threshold; d.max_iter = max_iter;
   std::memcpy(dst, &d, sizeof d);
 }
 
-void lqr_pack_loop_desc(void* dst, int n, int rule, int n_basis, const double* ab, long long s, long long k,
-                        long long goal, long long lift) {
+void lqr_pack_loop_desc(void* dst, int n, int rule, int n_basis, int noclip, const double* ab, long long s,
+                        long long k, long long goal, long long lift) {
   LqrLoopDesc d{};
-  d.n = n; d.rule = rule; d.n_basis = n_basis;
+  d.n = n; d.rule = rule; d.n_basis = n_basis; d.noclip = noclip;
   d.ab = ab; d.s = s; d.k = k; d.goal = goal; d.lift = lift;
   std::memcpy(dst, &d, sizeof d);
 }

@@ -1,4 +1,5 @@
-// lqr_kernels.hpp -- finite-horizon discrete LQR in f64 (reference: autompc/control/lqr.py:15-47, 139-192).
+// lqr_kernels.hpp -- discrete LQR in f64, finite and infinite horizon (reference: autompc/control/lqr.py:15-47,
+// 96-192).
 //
 // lqr_gains_kernel: one workgroup per Riccati problem, problems of different state dimension in one launch.
 // Each problem runs the reference's recursion from P = F (padded to the model state):
@@ -7,7 +8,11 @@
 //                                             G_BA = B^T P A (lower left), G_BB = B^T P B
 //     X = (R + G_BB)^-1 G_BA                  (Gauss-Jordan with partial pivoting, nu <= 16, in LDS)
 //     P <- (G_AA - G_AB X) + Q
-// horizon + 1 times, and returns K = -X of the last P.  Nothing is assumed symmetric: Q, F and R are taken as
+// horizon + 1 times, and returns K = -X of the last P.  An infinite-horizon problem (horizon 0) runs the same update
+// from P = Q until max|P_new - P_old| <= threshold (_inf_horz_dt_lqr, lqr.py:22-33) or max_iter updates have run; the
+// maximum is taken where the update stores P (each lane reads the entry it is about to overwrite) and reduced over
+// the wave and then the four waves, and a maximum does not depend on the order it is taken in.
+// Nothing is assumed symmetric: Q, F and R are taken as
 // given, as the reference takes them, and P is then not symmetric either.  The workspace holds P TRANSPOSED
 // (Pt[k][i] = P[i][k]), so lqr_gemm_tn's X^T Y with X = Pt is P [A | B] with every load of the product
 // coalesced; the update transposes 8 x 8 blocks between the lanes of a wave, so it loads and stores runs of 8.
@@ -30,13 +35,17 @@ static_assert(kLqrThreads % 64 == 0, "the update of P hands values between the l
 // One Riccati problem.  Read field by field through a global pointer (uniform, scalar loads): a copy of the
 // struct in registers indexed at run time is what spilled the plans' model table to scratch.
 struct LqrDesc {
-  int n, nu, no, horizon;
-  int id, pad0, pad1, pad2;
+  int n, nu, no, horizon;     // horizon 0: iterate to the fixed point (threshold, max_iter)
+  int id, max_iter, pad1, pad2;
   const double* ab;           // [n][n + nu] row-major: [A | B] of the controller model
   long long ws;               // workspace offset (doubles): P [n][n], M [n][n+nu], G [n+nu][n+nu]
   long long cost;             // cost offset (doubles): Q [no][no], R [nu][nu], F [no][no]
   long long k;                // gain offset (doubles): K [nu][n]
+  double threshold;           // infinite horizon: stop once max|P_new - P_old| <= threshold
 };
+
+// max of two magnitudes in which a NaN sticks, whichever side it is on (so the order does not matter)
+__device__ inline double lqr_nanmax(double a, double b) { return (b > a || b != b) ? b : a; }
 
 // C[i][j] = sum_k X[k][i] Y[k][j]  (i < m, j < nn, k < K); X, Y, C row-major with leading dimensions
 // ldx, ldy, ldc.  64 x 64 output tiles, 16-deep k slices staged in LDS, a 4 x 4 register block per thread.
@@ -86,18 +95,13 @@ __device__ inline void lqr_gemm_tn(const double* __restrict__ X, int ldx, const 
     }
 }
 
-// Problems are launched in `order` (heaviest first, so a horizon-1000 problem starts at once);
-// status[id] = 0 ok, 1 singular R + B^T P B or a non-finite value (the reference's LinAlgError / NaN).
-__global__ __launch_bounds__(kLqrThreads) void lqr_gains_kernel(const LqrDesc* __restrict__ descs,
-                                                                 const int* __restrict__ order,
-                                                                 double* __restrict__ ws,
-                                                                 const double* __restrict__ cost,
-                                                                 double* __restrict__ kout, int* __restrict__ status) {
-  __shared__ double tiles[2 * kLqrKt * kLqrTile];
-  __shared__ double aug[kLqrMaxNu * (kLqrMaxNu + kLqrMaxN)];
-  __shared__ double fac[kLqrMaxNu];
-  __shared__ int s_piv, s_bad;
-  const LqrDesc* d = descs + order[blockIdx.x];
+// The body of lqr_gains_kernel, instantiated once per kind of problem: with inf == false every infinite-horizon
+// statement folds away and what is left is the finite recursion as it was before those existed.
+template <bool inf>
+__device__ __forceinline__ void lqr_gains_body(const LqrDesc* __restrict__ d, double* __restrict__ ws,
+                                               const double* __restrict__ cost, double* __restrict__ kout,
+                                               int* __restrict__ status, double* tiles, double* aug, double* fac,
+                                               double* s_red, int& s_piv, int& s_bad, int& s_conv) {
   const int n = d->n, nu = d->nu, no = d->no, H = d->horizon, id = d->id;
   const double* __restrict__ ab = d->ab;
   const int m = n + nu, w = nu + n;          // w: width of the augmented system [S | G_BA]
@@ -109,13 +113,17 @@ __global__ __launch_bounds__(kLqrThreads) void lqr_gains_kernel(const LqrDesc* _
   const double* F = R + (size_t)nu * nu;
   double* K = kout + d->k;
   const int t = threadIdx.x;
+  const double* P0 = inf ? Q : F;            // _inf_horz_dt_lqr starts from P = Q (lqr.py:23)
   for (int e = t; e < n * n; e += kLqrThreads) {
     const int i = e / n, j = e - i * n;
-    Pt[e] = (i < no && j < no) ? F[j * no + i] : 0.0;
+    Pt[e] = (i < no && j < no) ? P0[j * no + i] : 0.0;
   }
-  if (t == 0) s_bad = 0;
+  if (t == 0) s_bad = s_conv = 0;
   __syncthreads();
-  for (int it = 0; it <= H + 1; ++it) {      // H + 1 Riccati updates (lqr.py:36-40), then the gain (:42)
+  int it = 0;                                // Riccati updates performed so far
+  // finite: H + 1 Riccati updates (lqr.py:36-40), then the gain (:42); infinite: updates until P stands still
+  // (:24-29), then the gain (:31)
+  for (;; ++it) {
     lqr_gemm_tn(Pt, n, ab, m, M, m, n, m, n, tiles);
     __syncthreads();
     lqr_gemm_tn(ab, m, M, m, G, m, m, m, n, tiles);
@@ -158,7 +166,7 @@ __global__ __launch_bounds__(kLqrThreads) void lqr_gains_kernel(const LqrDesc* _
       __syncthreads();
     }
     if (s_bad) break;
-    if (it == H + 1) {                       // K = -(R + B^T P B)^-1 B^T P A
+    if (inf ? s_conv : it == H + 1) {        // K = -(R + B^T P B)^-1 B^T P A
       for (int e = t; e < nu * n; e += kLqrThreads) {
         const int r = e / n, j = e - r * n;
         const double v = -aug[r * w + nu + j];
@@ -172,6 +180,7 @@ __global__ __launch_bounds__(kLqrThreads) void lqr_gains_kernel(const LqrDesc* _
     // stores it to Pt[j0 + a][i0 + b]: loads and stores both run over 8 consecutive doubles, with no barrier
     {
       const int lane = t & 63, a = lane >> 3, b = lane & 7, nb = (n + 7) >> 3;
+      double dm = 0.0;                         // this lane's max|P_new - P_old| (a masked-off lane adds nothing)
       for (int blk = t >> 6; blk < nb * nb; blk += kLqrThreads / 64) {   // (uniform in the wave)
         const int bi = blk / nb, i0 = 8 * bi, j0 = 8 * (blk - bi * nb);
         const int i = i0 + a, j = j0 + b;
@@ -183,20 +192,72 @@ __global__ __launch_bounds__(kLqrThreads) void lqr_gains_kernel(const LqrDesc* _
           v = (G[(size_t)i * m + j] - y) + q;
         }
         v = __shfl(v, 8 * b + a);              // every lane of the wave takes part
-        if (i0 + b < n && j0 + a < n) Pt[(size_t)(j0 + a) * n + i0 + b] = v;
+        if (i0 + b < n && j0 + a < n) {
+          double* dst = Pt + (size_t)(j0 + a) * n + i0 + b;
+          if (inf) dm = lqr_nanmax(dm, fabs(v - *dst));
+          *dst = v;
+        }
+      }
+      if (inf) {
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) dm = lqr_nanmax(dm, __shfl_xor(dm, off));
+        if (lane == 0) s_red[t >> 6] = dm;
       }
     }
     __syncthreads();
+    if (inf) {
+      double dm = s_red[0];
+#pragma unroll
+      for (int wv = 1; wv < kLqrThreads / 64; ++wv) dm = lqr_nanmax(dm, s_red[wv]);
+      if (dm != dm) {                          // NaN: the reference's loop ends on it and returns a NaN gain
+        if (t == 0) s_bad = 1;
+        ++it;
+        break;
+      }
+      if (dm <= d->threshold) {                // (read here, once a step: nothing more to keep in registers)
+        if (t == 0) s_conv = 1;                // read after the next pass's barriers
+      } else if (it + 1 >= d->max_iter) {      // still moving at the cap
+        if (t == 0) s_bad = 2;
+        ++it;
+        break;
+      }
+    }
   }
   __syncthreads();
-  if (t == 0) status[id] = s_bad;
+  if (t == 0) {
+    status[id] = s_bad;
+    status[gridDim.x + id] = inf ? it : H + 1;
+  }
   if (s_bad)
     for (int e = t; e < nu * n; e += kLqrThreads) K[e] = __builtin_nan("");
 }
 
+// Problems are launched in `order` (heaviest first, so a horizon-1000 problem starts at once);
+// status[id] = 0 ok, 1 singular R + B^T P B or a non-finite value (the reference's LinAlgError / NaN), 2 an
+// infinite-horizon problem whose P still moved by more than its threshold after max_iter updates (the reference's
+// loop would not return).  status [2 * gridDim.x]: the second half takes the Riccati updates performed, horizon + 1 of
+// a finite problem (one array, and the convergence flag in LDS: the products leave no scalar register to spare).
+__global__ __launch_bounds__(kLqrThreads) void lqr_gains_kernel(const LqrDesc* __restrict__ descs,
+                                                                 const int* __restrict__ order,
+                                                                 double* __restrict__ ws,
+                                                                 const double* __restrict__ cost,
+                                                                 double* __restrict__ kout, int* __restrict__ status) {
+  __shared__ double tiles[2 * kLqrKt * kLqrTile];
+  __shared__ double aug[kLqrMaxNu * (kLqrMaxNu + kLqrMaxN)];
+  __shared__ double fac[kLqrMaxNu];
+  __shared__ double s_red[kLqrThreads / 64];
+  __shared__ int s_piv, s_bad, s_conv;
+  const LqrDesc* d = descs + order[blockIdx.x];
+  if (d->horizon == 0)
+    lqr_gains_body<true>(d, ws, cost, kout, status, tiles, aug, fac, s_red, s_piv, s_bad, s_conv);
+  else
+    lqr_gains_body<false>(d, ws, cost, kout, status, tiles, aug, fac, s_red, s_piv, s_bad, s_conv);
+}
+
 // One candidate of the closed loop.
 struct LqrLoopDesc {
-  int n, rule, n_basis, pad0;  // rule 0: state = observation, 1: ARX shift A s + B u then the observation
+  int n, rule, n_basis, noclip;  // noclip 1: u = K (s - state0) as it is (InfiniteHorizonLQR.run, lqr.py:126-136)
+                               // rule 0: state = observation, 1: ARX shift A s + B u then the observation
                                // slot overwritten (arx.py:94-99), 2: lift (koopman.py:105-122, 166-168)
   const double* ab;            // [n][n + nu]
   long long s;                 // state offset (doubles): two buffers of n, alternating per step
@@ -206,8 +267,9 @@ struct LqrLoopDesc {
 };
 
 // Controller step of every candidate (one workgroup each): modelstate = update_state(state, u_prev, obs),
-// u = clip(K (modelstate - state0)).  sim [B][snx]: the surrogate state, whose first `no` entries are the
-// observation simulate() hands the controller; u [B][nu] holds u_prev on entry and u on exit.
+// u = clip(K (modelstate - state0)), not clipped where the problem's descriptor says so.  sim [B][snx]: the
+// surrogate state, whose first `no` entries are the observation simulate() hands the controller; u [B][nu] holds
+// u_prev on entry and u on exit.
 __global__ __launch_bounds__(kLqrThreads) void lqr_ctrl_kernel(const LqrLoopDesc* __restrict__ descs,
                                                                 double* __restrict__ states, int cur,
                                                                 const double* __restrict__ sim, int snx, int no,
@@ -272,8 +334,10 @@ __global__ __launch_bounds__(kLqrThreads) void lqr_ctrl_kernel(const LqrLoopDesc
     const double* g = gbuf + d->goal;
     double acc = 0.0;
     for (int j = 0; j < n; ++j) acc = fma(kr[j], s_new[j] - (j < no ? g[j] : 0.0), acc);
-    acc = acc > hi[t] ? hi[t] : acc;      // np.minimum then np.maximum (NaN propagates)
-    acc = acc < lo[t] ? lo[t] : acc;
+    if (!d->noclip) {
+      acc = acc > hi[t] ? hi[t] : acc;    // np.minimum then np.maximum (NaN propagates)
+      acc = acc < lo[t] ? lo[t] : acc;
+    }
     ub[t] = acc;
   }
 }

@@ -303,12 +303,18 @@ class BatchPipelineTuner:
         if cand.get("controller") == "lqr":   # the drop-in LQR (gain on the device, run() on the host)
             from ..control.lqr import LQR
             from .lqr_eval import is_finite_horizon
-            if not is_finite_horizon(cand.get("finite_horizon", True)):
+            finite = is_finite_horizon(cand.get("finite_horizon", True))
+            if not finite and getattr(ev, "infinite_horizon", "refuse") == "refuse":
                 return float("inf")           # InfiniteHorizonLQR: the reference's dare is undefined
             try:
-                ctl = LQR(self.system, task, cand.get("model") or ev.model, "true", int(cand["horizon"]),
-                          device=ev.device)
-            except np.linalg.LinAlgError:
+                if finite:
+                    ctl = LQR(self.system, task, cand.get("model") or ev.model, "true", int(cand["horizon"]),
+                              device=ev.device)
+                else:                         # the evaluator iterates: so does the drop-in, with its settings
+                    ctl = LQR(self.system, task, cand.get("model") or ev.model, "false", device=ev.device,
+                              infinite_horizon=ev.infinite_horizon, threshold=ev.inf_threshold,
+                              max_iter=ev.inf_max_iter)
+            except np.linalg.LinAlgError:     # (RiccatiNotConverged is one)
                 return float("inf")           # eval_cfg's LinAlgError branch (pipeline_tuner.py:236-239)
         elif "num_path" not in cand:          # an iLQR candidate (horizon + cost weights)
             ctl = IterativeLQR(self.system, task, cand.get("model") or ev.model, int(cand["horizon"]),

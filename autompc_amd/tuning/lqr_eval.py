@@ -14,8 +14,13 @@ Nothing runs on the host per control step, and each distinct model is staged onc
 
 Edge cases, on purpose:
 
-* ``finite_horizon`` false scores ``inf``: the reference's ``InfiniteHorizonLQR`` calls ``dare``, which it never
-  defines (lqr.py:104), so such a configuration can never become its incumbent.
+* ``finite_horizon`` false scores ``inf`` by default (``infinite_horizon="refuse"``, status 2): the reference's
+  ``InfiniteHorizonLQR`` calls ``dare``, which it never defines (lqr.py:104), so such a configuration can never become
+  its incumbent.  With ``infinite_horizon="iterate"`` such a candidate gets the gain the reference ships for that class
+  (``_inf_horz_dt_lqr``, lqr.py:22-33; ``control.lqr`` has the details) and rides in the same plan as the finite ones:
+  horizon 0 in the one ``ampc_lqr_gains_ex`` launch, and in the one ``ampc_lqr_plan_set_loop_ex`` a zero goal and no
+  clipping (``InfiniteHorizonLQR.run`` applies neither).  A candidate whose Riccati iteration has not converged after
+  ``inf_max_iter`` steps scores ``inf`` with status 3, as ``eval_cfg`` scores a ``LinAlgError``.
 * Gain status 1 (singular ``R + B'PB`` or a non-finite recursion) scores ``inf``, as ``eval_cfg``'s
   ``LinAlgError`` branch does.
 * A nonlinear model raises ``TypeError`` and a horizon outside 1..1000 ``ValueError``, as the drop-in ``LQR`` does.
@@ -30,7 +35,9 @@ Edge cases, on purpose:
 import numpy as np
 
 from .. import _lib
-from ..control.lqr import FiniteHorizonLQR, check_horizon, check_linear, lqr_gain_host
+from ..control.lqr import (INF_MAX_ITER_DEFAULT, INF_THRESHOLD_DEFAULT, FiniteHorizonLQR, InfiniteHorizonLQR,
+                           RiccatiNotConverged, check_horizon, check_inf_params, check_infinite_horizon,
+                           check_linear, lqr_gain_host, lqr_gain_inf_host)
 from ..costs.terms import cost_terms
 from .batch_eval import (_as_matrix, _task_goal, default_episode_controls, episode_of, model_handle,
                          score_trajectories)
@@ -82,6 +89,13 @@ class _HostFiniteHorizonLQR(FiniteHorizonLQR):
         self.umax = task.get_ctrl_bounds()[:, 1]
 
 
+class _HostInfiniteHorizonLQR(InfiniteHorizonLQR):
+    """InfiniteHorizonLQR ("iterate") whose gain comes from the host iteration (models the device does not take)."""
+
+    def _gain(self, A, B, Q, R):
+        return lqr_gain_inf_host(A, B, Q, R, self.threshold, self.max_iter)
+
+
 class LqrCandidateEvaluator:
     """Closed-loop surrogate scores of LQR + QuadCost candidates on one GPU (see the module docstring).
 
@@ -91,10 +105,18 @@ class LqrCandidateEvaluator:
 
     accepts_global_ids = True
 
-    def __init__(self, system, task, model=None, surrogate=None, device=0, term_check_every=64):
+    def __init__(self, system, task, model=None, surrogate=None, device=0, term_check_every=64,
+                 infinite_horizon="refuse", inf_threshold=INF_THRESHOLD_DEFAULT, inf_max_iter=INF_MAX_ITER_DEFAULT):
         """model: the controller model of candidates that carry none (may be None if every candidate carries one);
         surrogate: the simulation model (default: `model`); term_check_every: with a user termination condition,
-        the length of the first device run (doubled until every candidate has ended)."""
+        the length of the first device run (doubled until every candidate has ended); infinite_horizon: "refuse"
+        scores a ``finite_horizon`` false candidate ``inf`` unrun, "iterate" runs it (module docstring) with
+        ``_inf_horz_dt_lqr``'s threshold `inf_threshold` and at most `inf_max_iter` Riccati steps.  The default cap of
+        10000 is a choice, not a measurement: that many steps of a 235-state model take of the order of ten seconds,
+        and an ARX model with a noticeable bias never converges, so lower it when tuning ARX models."""
+        self.infinite_horizon = check_infinite_horizon(infinite_horizon)
+        check_inf_params(inf_threshold, inf_max_iter)
+        self.inf_threshold, self.inf_max_iter = float(inf_threshold), int(inf_max_iter)
         if surrogate is None:
             surrogate = model
         if surrogate is None:
@@ -113,26 +135,32 @@ class LqrCandidateEvaluator:
         self.goal = np.nan_to_num(_task_goal(task.get_cost(), system.obs_dim), nan=0.0)
         self.last_lengths = None
         self.host_fallbacks = 0          # candidates scored on the host (models the device does not take)
-        self.last_status = None          # per candidate: 0 scored, 1 singular gain, 2 infinite horizon
+        self.last_status = None          # per candidate: 0 scored, 1 singular gain, 2 infinite horizon refused,
+        #                                  3 infinite horizon not converged at inf_max_iter
+        self.last_iterations = None      # per candidate: Riccati steps of its gain (0: none computed)
 
     # -- one candidate's pieces --------------------------------------------------------------------------
     def _prepare(self, c):
-        """(finite, model, horizon, Q, R, F) of a candidate, with the drop-in's refusals."""
+        """(finite, model, horizon, Q, R, F) of a candidate, with the drop-in's refusals; horizon 0 for an infinite
+        horizon that is iterated, and model None for one that is refused."""
         if not isinstance(c, dict):
             raise TypeError("LQR candidates are dicts")
         if c.get("controller", "lqr") != "lqr":
             raise ValueError("LqrCandidateEvaluator scores controller='lqr' candidates, not %r" % c.get("controller"))
         finite = is_finite_horizon(c.get("finite_horizon", True))
-        if not finite:
+        if not finite and self.infinite_horizon == "refuse":
             return False, None, None, None, None, None
         model = c.get("model")
         model = self.model if model is None else model
         if model is None:
             raise ValueError("candidate carries no model and the evaluator has none")
         check_linear(model)
+        no, nu = self.system.obs_dim, self.system.ctrl_dim
+        if not finite:                     # F is not used (lqr.py:101-104)
+            F = _as_matrix(c["F"], no) if c.get("F") is not None else np.zeros((no, no))
+            return False, model, 0, _as_matrix(c["Q"], no), _as_matrix(c["R"], nu), F
         horizon = int(c["horizon"])
         check_horizon(horizon)
-        no, nu = self.system.obs_dim, self.system.ctrl_dim
         return True, model, horizon, _as_matrix(c["Q"], no), _as_matrix(c["R"], nu), _as_matrix(c["F"], no)
 
     def _controller_task(self, Q, R, F):
@@ -175,27 +203,30 @@ class LqrCandidateEvaluator:
         lengths = np.ones(B, dtype=np.int64)
         scores = np.full(B, np.inf)
         status = np.full(B, 2, dtype=np.int32)
+        iterations = np.zeros(B, dtype=np.int64)
         dev, host = [], []
         rules = {}
         for i, (finite, model, *_rest) in enumerate(prep):
-            if not finite:
+            if model is None:              # an infinite horizon, refused
                 continue
             r = rules.setdefault(id(model), device_rule(model, no))
             (dev if r is not None else host).append(i)
         if dev:
             self._evaluate_device(prep, dev, rules, x0, t0, n_ctl, term_cond, terms, obs, ctl, lengths, scores,
-                                  status)
+                                  status, iterations)
         for i in host:
-            self._evaluate_host(prep[i], i, x0, n_ctl, term_cond, obs, ctl, lengths, scores, status)
+            self._evaluate_host(prep[i], i, x0, n_ctl, term_cond, obs, ctl, lengths, scores, status, iterations)
         self.host_fallbacks += len(host)
         self.last_lengths = lengths
         self.last_status = status
+        self.last_iterations = iterations
         if return_trajectories:
             Lmax = int(lengths.max())
             return scores, obs[:, :Lmax], ctl[:, :Lmax]
         return scores
 
-    def _evaluate_device(self, prep, dev, rules, x0, t0, n_ctl, term_cond, terms, obs, ctl, lengths, scores, status):
+    def _evaluate_device(self, prep, dev, rules, x0, t0, n_ctl, term_cond, terms, obs, ctl, lengths, scores, status,
+                         iterations):
         no, nu = self.system.obs_dim, self.system.ctrl_dim
         opened = []
         try:
@@ -213,15 +244,26 @@ class LqrCandidateEvaluator:
             Q = np.array([prep[i][3] for i in dev])
             R = np.array([prep[i][4] for i in dev])
             F = np.array([prep[i][5] for i in dev])
-            _, st = plan.gains([prep[i][2] for i in dev], Q, R, F)
+            hz = np.array([prep[i][2] for i in dev])
+            inf = hz == 0
             rl = [rules[id(m)] for m in models]
-            plan.set_loop([r for r, _ in rl], np.tile(self.goal, (len(dev), 1)), self.umin, self.umax,
-                          lifts=[lift for _, lift in rl])
+            if inf.any():                      # one launch for finite and infinite problems alike
+                _, st, its = plan.gains_ex(hz, Q, R, F, thresholds=self.inf_threshold, max_iters=self.inf_max_iter)
+                # InfiniteHorizonLQR.run subtracts no goal and does not clip (lqr.py:126-136)
+                goal = np.where(inf[:, None], 0.0, np.tile(self.goal, (len(dev), 1)))
+                plan.set_loop([r for r, _ in rl], goal, self.umin, self.umax, lifts=[lift for _, lift in rl],
+                              clip=(~inf).astype(np.int32))
+            else:
+                _, st = plan.gains(hz, Q, R, F)
+                its = hz + 1
+                plan.set_loop([r for r, _ in rl], np.tile(self.goal, (len(dev), 1)), self.umin, self.umax,
+                              lifts=[lift for _, lift in rl])
             init_states = [m.traj_to_state(t0) for m in models]
             init_sim = np.tile(np.asarray(self.surrogate.traj_to_state(t0), dtype=np.float64), (len(dev), 1))
             idx = np.asarray(dev)
             ok = st == 0
-            status[idx] = np.where(ok, 0, 1)
+            status[idx] = np.where(ok, 0, np.where(st == 2, 3, 1))
+            iterations[idx] = its
             if n_ctl == 0:                     # max_steps = 0: the one-row trajectory is scored as is
                 o, c = obs[idx, :1].copy(), ctl[idx, :1].copy()
                 sc = self._score(sur, terms, o, c)
@@ -237,7 +279,7 @@ class LqrCandidateEvaluator:
                 sc = self._device_until(plan, sur, init_states, init_sim, idx, n_ctl, term_cond, terms, obs, ctl,
                                         lengths)
             scores[idx] = np.where(ok, sc, np.inf)
-            bad = idx[~ok]                     # singular gain: no trajectory (eval_cfg keeps none)
+            bad = idx[~ok]                     # singular or unconverged gain: no trajectory (eval_cfg keeps none)
             obs[bad, 1:], ctl[bad, 1:] = np.nan, np.nan
             ctl[bad, 0] = 0.0
             lengths[bad] = 1
@@ -284,12 +326,22 @@ class LqrCandidateEvaluator:
             return sur.score_trajectories(terms, obs, ctrls, obs_dim=no)
         return score_trajectories(self.task.get_cost(), obs[:, :, :no], ctrls)
 
-    def _evaluate_host(self, p, i, x0, n_ctl, term_cond, obs, ctl, lengths, scores, status):
+    def _evaluate_host(self, p, i, x0, n_ctl, term_cond, obs, ctl, lengths, scores, status, iterations):
         """A model the device cannot take: the reference's recursion and simulate() on the host."""
         from ..utils import simulate
-        _, model, horizon, Q, R, F = p
+        finite, model, horizon, Q, R, F = p
         try:
-            ctl_i = _HostFiniteHorizonLQR(self.system, self._controller_task(Q, R, F), model, horizon)
+            if finite:
+                ctl_i = _HostFiniteHorizonLQR(self.system, self._controller_task(Q, R, F), model, horizon)
+                iterations[i] = horizon + 1
+            else:
+                ctl_i = _HostInfiniteHorizonLQR(self.system, self._controller_task(Q, R, F), model, "iterate",
+                                                self.inf_threshold, self.inf_max_iter)
+                iterations[i] = ctl_i.iters
+        except RiccatiNotConverged:
+            iterations[i] = self.inf_max_iter
+            status[i] = 3
+            return
         except np.linalg.LinAlgError:
             ctl_i = None
         if ctl_i is None or not np.all(np.isfinite(ctl_i.K)):  # (the device's status 1)

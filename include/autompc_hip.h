@@ -47,7 +47,8 @@ int ampc_version(void);   /* 100 * major + minor; 104: + ampc_mppi_run_legacy; 1
                            * 113: + ampc_sindy_fit; 114: + ampc_lasso_fit; + ampc_stable_fit, + ampc_mlpfit_*, + ampc_kstep_errors_mlp,
                            *      + ampc_mppi_plan_set_model_table, + ampc_ilqr_plan_set_model_table, + ampc_mppi_plan_set_sindy_models,
                            *      + ampc_ilqr_plan_set_sindy_models, + ampc_mppi_plan_set_linear_models, + ampc_mppi_closed_loop_linear,
-                           *      + ampc_ilqr_plan_set_linear_models, + ampc_ilqr_closed_loop_linear, + ampc_ilqr_linear_table_layout
+                           *      + ampc_ilqr_plan_set_linear_models, + ampc_ilqr_closed_loop_linear, + ampc_ilqr_linear_table_layout,
+                           *      + ampc_lqr_gains_ex, + ampc_lqr_plan_set_loop_ex
                            *      (no bump: callers detect them by their symbols) */
 int ampc_device_count(void);
 
@@ -863,7 +864,7 @@ int ampc_mlpfit_steps(const ampc_mlpfit_plan* p, long long* steps);
 /* Waits for the stream, then frees what the plan owns (mlp.py has no counterpart: the optimiser is garbage collected). */
 int ampc_mlpfit_destroy(ampc_mlpfit_plan* p);
 
-/* ---- finite-horizon LQR (f64 only) ---------------------------------------------------------- */
+/* ---- LQR, finite and infinite horizon (f64 only) --------------------------------------------- */
 /* A plan of n_problems LQR controllers (reference: autompc/control/lqr.py:139-192 FiniteHorizonLQR) that keeps
  * their gains on the device between ampc_lqr_gains and the closed loop.  obs_dim 1..256, ctrl_dim 1..16. */
 int ampc_lqr_plan_create(int device, int n_problems, int obs_dim, int ctrl_dim, ampc_lqr_plan** out);
@@ -883,6 +884,22 @@ int ampc_lqr_plan_set_models(ampc_lqr_plan* p, ampc_handle* const* models);
  * A problem's result does not depend on the other problems of the call (fixed-order sums).  Synchronises. */
 int ampc_lqr_gains(ampc_lqr_plan* p, const int* horizons, const double* Q, const double* R, const double* F,
                    double* K, int* status);
+/* ampc_lqr_gains with infinite-horizon problems in the same launch (_inf_horz_dt_lqr, lqr.py:22-33, with N = 0).
+ *   horizons [n]: 1..1000 a finite problem, exactly as ampc_lqr_gains computes it; 0 an infinite one: from P = Q
+ *   (padded; F is not read) the same Riccati step until max|P_new - P_old| over the n_i x n_i entries is
+ *   <= thresholds[i], then K of that P as above;
+ *   thresholds [n]: finite and > 0 where horizons[i] == 0 (the reference's default is 1e-3), not read elsewhere;
+ *   max_iters [n]: 1..100000 where horizons[i] == 0, not read elsewhere.  The reference's loop has no cap and does
+ *   not return when P keeps moving (an ARX model with a bias column: its constant state adds a constant to P every
+ *   step); here such a problem stops after max_iters[i] steps.  A step of a 256-state model takes about a millisecond,
+ *   so the bound of 100000 keeps a workgroup that never converges to a couple of minutes;
+ *   status [n] (may be NULL): 0 and 1 as ampc_lqr_gains (a NaN in max|P_new - P_old| is 1); 2 = not converged after
+ *   max_iters[i] steps; K is NaN for 1 and 2;
+ *   iters [n] (may be NULL): Riccati steps performed; horizons[i] + 1 for a finite problem.
+ * The maximum is order-independent, so a problem's K and iters do not depend on the rest of the call either.
+ * (Added without a version bump: callers detect it by its symbol.) */
+int ampc_lqr_gains_ex(ampc_lqr_plan* p, const int* horizons, const double* thresholds, const int* max_iters,
+                      const double* Q, const double* R, const double* F, double* K, int* status, int* iters);
 /* How each problem's controller updates its model state in the closed loop (model.update_state, lqr.py:176-177):
  *   rules [n]: 0 = the observation (model state == observation), 1 = ARX shift A s + B u_prev with the
  *   observation slot overwritten (arx.py:94-99), 2 = lift of the observation (koopman.py:105-122, 166-168)
@@ -893,6 +910,12 @@ int ampc_lqr_gains(ampc_lqr_plan* p, const int* horizons, const double* Q, const
 int ampc_lqr_plan_set_loop(ampc_lqr_plan* p, const int* rules, const int* n_basis, const int* lift_kinds,
                            const double* lift_params, const double* goal, const double* ctrl_lo,
                            const double* ctrl_hi);
+/* ampc_lqr_plan_set_loop with clip [n] (NULL: every problem clips, as ampc_lqr_plan_set_loop): clip[i] == 0 leaves
+ * problem i's u = K (s - state0) as it is, whatever the bounds -- InfiniteHorizonLQR.run (lqr.py:126-136), which also
+ * subtracts no goal: pass a zero goal for such a problem.  (Added without a version bump.) */
+int ampc_lqr_plan_set_loop_ex(ampc_lqr_plan* p, const int* rules, const int* n_basis, const int* lift_kinds,
+                              const double* lift_params, const double* goal, const double* ctrl_lo,
+                              const double* ctrl_hi, const int* clip);
 /* simulate(controller, init_obs, sim_model=surrogate, max_steps=n_steps) for every problem at once, on the device
  * (utils/simulation.py:44-63; FiniteHorizonLQR.run, lqr.py:174-192): per control step the controller state update,
  * u = clip(K (s - state0)), simstate = surrogate.pred(simstate, u).  Needs ampc_lqr_gains and ampc_lqr_plan_set_loop.
