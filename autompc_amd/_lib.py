@@ -149,6 +149,8 @@ SIGNATURES = {
                                 _dp]),
     "ampc_sindy_fit": (c_int, [c_int, c_int, _ip, c_int, c_int, _dp, _dp, _dp, c_int, _ip, _ip, _ip, _ip, _ip, _dp, _ip,
                                _ip, c_int, _ip, _ip, _dp, c_double, c_int, _dp, _ip, _dp, _dp, _ip]),
+    "ampc_sindy_fit_wide": (c_int, [c_int, c_int, _ip, c_int, c_int, _dp, _dp, _dp, c_int, _ip, _ip, _ip, _ip, _ip, _dp,
+                                    _ip, _ip, c_int, _ip, _ip, _dp, c_double, c_int, _dp, _ip, _dp, _dp, _ip]),
     "ampc_lasso_fit": (c_int, [c_int, c_int, _ip, c_int, c_int, _dp, _dp, c_int, _ip, _ip, _dp, c_int, _ip, _dp,
                                c_double, c_double, _dp, _ip, _dp, _ip]),
     "ampc_stable_fit": (c_int, [c_int, c_int, _ip, c_int, c_int, _dp, _dp, c_int, _ip, _ip, _dp, c_double, _dp, _ip,
@@ -1335,6 +1337,13 @@ def linfit_fit(traj_len, obs, ctrls, arx_histories=(), koopman_bases=(), device=
     return [coeffs[off[i]:off[i + 1]].reshape(shapes[i]) for i in range(len(shapes))], status, pivot
 
 
+def sindy_fit_wide(traj_len, obs, ctrls, designs, configs, ycont=None, alpha=0.05, max_iter=20, device=0):
+    """ampc_sindy_fit_wide: ``sindy_fit`` for feature libraries of up to 2048 features, on the wide kernels (the
+    same arguments and results; every design of the call runs on them)."""
+    return _sindy_fit_entry("ampc_sindy_fit_wide", traj_len, obs, ctrls, designs, configs, ycont, alpha, max_iter,
+                            device)
+
+
 def sindy_fit(traj_len, obs, ctrls, designs, configs, ycont=None, alpha=0.05, max_iter=20, device=0):
     """ampc_sindy_fit: sequentially-thresholded least-squares fits of SINDy configurations of one data set.
     obs [R][nx], ctrls [R][nu]: the trajectories concatenated, traj_len their lengths; ycont: None or [R][nx], the
@@ -1342,6 +1351,10 @@ def sindy_fit(traj_len, obs, ctrls, designs, configs, ycont=None, alpha=0.05, ma
     tuples of ``sysid.sindy.build_library``; configs: ``(design index, continuous, threshold)`` triples.  Returns
     (coeffs, status, min_pivot, min_margin, iterations): a list of [nx][n_features] matrices and four
     per-configuration arrays (status 0 fitted, 1 pivot rule, 2 threshold tie)."""
+    return _sindy_fit_entry("ampc_sindy_fit", traj_len, obs, ctrls, designs, configs, ycont, alpha, max_iter, device)
+
+
+def _sindy_fit_entry(_entry, traj_len, obs, ctrls, designs, configs, ycont, alpha, max_iter, device):
     lib, lens, obs, ctrls, nx, nu = _fit_data(traj_len, obs, ctrls)
     if ycont is not None:
         ycont = as_f64(ycont)
@@ -1366,10 +1379,10 @@ def sindy_fit(traj_len, obs, ctrls, designs, configs, ycont=None, alpha=0.05, ma
     status = np.zeros(C, dtype=np.int32)
     pivot, margin = np.empty(C), np.empty(C)
     iters = np.zeros(C, dtype=np.int32)
-    check(lib.ampc_sindy_fit(int(device), len(lens), iptr(lens), nx, nu, dptr(obs), dptr(ctrls), dptr(ycont),
-                             len(designs), iptr(feat_off), iptr(pair_off), iptr(kind), iptr(a0), iptr(a1), dptr(par),
-                             iptr(pvar), iptr(pexp), C, iptr(cd), iptr(cc), dptr(ct), float(alpha), int(max_iter),
-                             dptr(coeffs), iptr(status), dptr(pivot), dptr(margin), iptr(iters)))
+    check(getattr(lib, _entry)(int(device), len(lens), iptr(lens), nx, nu, dptr(obs), dptr(ctrls), dptr(ycont),
+                               len(designs), iptr(feat_off), iptr(pair_off), iptr(kind), iptr(a0), iptr(a1), dptr(par),
+                               iptr(pvar), iptr(pexp), C, iptr(cd), iptr(cc), dptr(ct), float(alpha), int(max_iter),
+                               dptr(coeffs), iptr(status), dptr(pivot), dptr(margin), iptr(iters)))
     return [coeffs[off[i]:off[i + 1]].reshape(shapes[i]) for i in range(C)], status, pivot, margin, iters
 
 

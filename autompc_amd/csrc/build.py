@@ -1,8 +1,8 @@
 """Build libautompc_hip.so for gfx950 with hipcc (cross-compiles without a GPU).
 
-Thirty-four translation units compiled in parallel and linked into one shared library: api.cpp +
+Thirty-five translation units compiled in parallel and linked into one shared library: api.cpp +
 api_{model,mppi,ilqr,lqr,linfit,sindyfit,lasso,stable,mlpfit,kstep_mlp}.cpp (the C ABI and host logic by family), launch_{mlp,mppi,ilqr,kstep,kstep_linear,kstep_sindy}.cpp
-once per precision (-DAMPC_T=double|float), launch_lqr.cpp, launch_linfit.cpp, launch_sindyfit.cpp, launch_lasso.cpp, launch_stable.cpp, launch_mlpfit.cpp, launch_kstep_mlp.cpp, launch_mppi_table.cpp, launch_ilqr_table.cpp, launch_ilqr_sindy_table.cpp and launch_ilqr_linear_table.cpp (f64 only).
+once per precision (-DAMPC_T=double|float), launch_lqr.cpp, launch_linfit.cpp, launch_sindyfit.cpp, launch_sindyfit_wide.cpp, launch_lasso.cpp, launch_stable.cpp, launch_mlpfit.cpp, launch_kstep_mlp.cpp, launch_mppi_table.cpp, launch_ilqr_table.cpp, launch_ilqr_sindy_table.cpp and launch_ilqr_linear_table.cpp (f64 only).
 """
 import concurrent.futures
 import os
@@ -30,6 +30,7 @@ UNITS = [("api", "api.cpp", []), ("api_model", "api_model.cpp", []), ("api_mppi"
     ("linfit_double", "launch_linfit.cpp", ["-DAMPC_T=double", "-DAMPC_T_IS_F64=1"]),
     ("api_sindyfit", "api_sindyfit.cpp", []),
     ("sindyfit_double", "launch_sindyfit.cpp", ["-DAMPC_T=double", "-DAMPC_T_IS_F64=1"]),
+    ("sindyfit_wide_double", "launch_sindyfit_wide.cpp", ["-DAMPC_T=double", "-DAMPC_T_IS_F64=1"]),
     ("api_lasso", "api_lasso.cpp", []),
     ("lasso_double", "launch_lasso.cpp", ["-DAMPC_T=double", "-DAMPC_T_IS_F64=1"]),
     ("api_stable", "api_stable.cpp", []),

@@ -24,26 +24,15 @@
 #define AMPC_SINDYFIT_KERNELS_HPP
 #include <hip/hip_runtime.h>
 
-#include "gram_frame.hpp"
-#include "sindy_kernels.hpp"
+#include "sindyfit_frame.hpp"
 
 namespace ampc {
 
-constexpr int kSindyfitMaxState = 64, kSindyfitMaxCtrl = 16;
 // columns of a design: features + both target sets, padded to a tile; two per thread
 constexpr int kSindyfitMaxCols = (kFitMaxFeat + 2 * kSindyfitMaxState + 15) / 16 * 16;
 constexpr int kSindyfitColsPerThread = (kSindyfitMaxCols + kFitThreads - 1) / kFitThreads;
 
-enum { SFC_NEXT_OBS = 7, SFC_YCONT = 8, SFC_ZERO = 9 };   // column kinds behind the library's SF_* kinds
 
-// How one column of [Theta | Y] is formed from a data row.
-struct SindyfitCol {
-  int kind;     // SF_ID .. SF_MONO: a library feature; SFC_NEXT_OBS: obs[t + 1][a0]; SFC_YCONT: ycont[t][a0]; SFC_ZERO
-  int a0, a1;   // variables (index into [obs | ctrls]); SF_MONO: first (variable, exponent) pair and their number
-  int pad;
-  double par;   // frequency / exponent
-  __host__ __device__ static SindyfitCol zero() { return SindyfitCol{SFC_ZERO, 0, 0, 0, 0.0}; }     // a padding column
-};
 
 // One design.  Read field by field through a global pointer (uniform loads), as LinfitSolveDesc.
 struct SindyfitDesign {
@@ -55,32 +44,8 @@ struct SindyfitDesign {
   int nf, w, wp, nfp, n_tiles, lds_stride;
 };
 
-struct SindyfitGramArgs {
-  const double* obs;          // [R][nx]
-  const double* ctrls;        // [R][nu]
-  const double* ycont;        // [R][nx] or nullptr (no design has continuous targets then)
-  const int* row_start;       // [R]: first row of the row's trajectory; -1: the row has no successor (no design row)
-  const SindyfitDesign* designs;
-  int R, nx, nu, splits;
-};
 
-__device__ inline double sindyfit_var(const SindyfitGramArgs& a, int g, int i) {
-  return i < a.nx ? a.obs[(size_t)g * a.nx + i] : a.ctrls[(size_t)g * a.nu + (i - a.nx)];
-}
 
-__device__ inline double sindyfit_value(const SindyfitGramArgs& a, const SindyfitCol c, const int* __restrict__ pool,
-                                        int g) {
-  if (c.kind == SFC_ZERO) return 0.0;
-  if (c.kind == SFC_NEXT_OBS) return a.obs[(size_t)(g + 1) * a.nx + c.a0];
-  if (c.kind == SFC_YCONT) return a.ycont[(size_t)g * a.nx + c.a0];
-  if (c.kind == SF_MONO) {
-    double val = 1.0;
-    for (int j = 0; j < c.a1; ++j)
-      val *= sindy_ipow<double>(sindyfit_var(a, g, pool[2 * (c.a0 + j)]), pool[2 * (c.a0 + j) + 1]);
-    return val;
-  }
-  return sindy_feature<double>(c.kind, sindyfit_var(a, g, c.a0), sindyfit_var(a, g, c.a1), c.par);
-}
 
 // grid (splits, tile groups, designs); dynamic LDS: kFitChunk * (largest lds_stride of the call) doubles.
 __global__ __launch_bounds__(kFitThreads) void sindyfit_gram_kernel(const SindyfitGramArgs a) {
@@ -109,15 +74,6 @@ __global__ void sindyfit_gram_reduce_kernel(const SindyfitDesign* __restrict__ d
   d->G[(size_t)ra * wp + cb] = gram_split_sum(part, splits, nfp, wp, ra, cb, cb < nf);
 }
 
-// One (configuration, target) pair.  Read field by field through a global pointer (uniform loads).
-struct SindyfitSolveDesc {
-  int n, tcol, id, pad;       // features, the target's column of G, output slot (pair index)
-  const double* g;            // the design's Gram [.][ldg]
-  long long ldg;
-  long long ws;               // workspace offset (doubles): [n + 1][n]
-  long long out;              // coefficient offset (doubles): [n]
-  double threshold;
-};
 
 __global__ __launch_bounds__(kFitThreads) void sindyfit_solve_kernel(
     const SindyfitSolveDesc* __restrict__ descs, const int* __restrict__ order, double* ws, double* __restrict__ coef,

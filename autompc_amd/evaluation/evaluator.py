@@ -29,7 +29,7 @@ class ModelEvaluator(ABC):
 
     def __init__(self, system, trajs, metric, rng, horizon=1, linear_fit="host", linear_kstep="host",
                  sindy_kstep="host", sindy_fit="host", lasso_fit="host", stable_fit="host", mlp_fit="torch",
-                 mlp_kstep="shape"):
+                 mlp_kstep="shape", sindy_wide_fit="host"):
         """linear_fit: how ``evaluate_batch`` fits ARX / Koopman models -- "host": each by its own ``train()``;
         "device": all of a batch by one ``sysid.linear_fit.fit_linear_models`` call (one Gram pass on the device,
         equal configurations fitted once).
@@ -40,6 +40,9 @@ class ModelEvaluator(ABC):
         sindy_fit: how ``evaluate_batch`` fits SINDy models -- "host": each by its own ``train()``; "device": all of
         a batch by one ``sysid.sindy_fit.fit_sindy_models`` call (one Gram launch, equal configurations fitted once);
         ``last_sindy_fit`` holds its ``SindyFitReport``.
+        sindy_wide_fit: with ``sindy_fit="device"``, how that call fits SINDy models whose library has 273..2048
+        features -- "host": each by its own ``train()``; "device": by ``ampc_sindy_fit_wide``
+        (``fit_sindy_models(..., wide="device")``).
         lasso_fit: with ``linear_fit="device"``, how that call fits Koopman models of method "lasso" -- "host": each
         by its own ``train()``; "device": by ``ampc_lasso_fit`` (``fit_linear_models(..., lasso="device")``).
         stable_fit: with ``linear_fit="device"``, how that call fits Koopman models of method "stable" -- "host": each
@@ -61,6 +64,8 @@ class ModelEvaluator(ABC):
             raise ValueError("sindy_kstep must be 'host' or 'device'")
         if sindy_fit not in ("host", "device"):
             raise ValueError("sindy_fit must be 'host' or 'device'")
+        if sindy_wide_fit not in ("host", "device"):
+            raise ValueError("sindy_wide_fit must be 'host' or 'device'")
         if lasso_fit not in ("host", "device"):
             raise ValueError("lasso_fit must be 'host' or 'device'")
         if stable_fit not in ("host", "device"):
@@ -76,6 +81,7 @@ class ModelEvaluator(ABC):
         self.lasso_fit = lasso_fit
         self.stable_fit = stable_fit
         self.sindy_fit = sindy_fit
+        self.sindy_wide_fit = sindy_wide_fit
         self.last_sindy_fit = None
         self.linear_kstep = linear_kstep
         self.sindy_kstep = sindy_kstep
@@ -133,7 +139,7 @@ class ModelEvaluator(ABC):
             from ..sysid.sindy_fit import fit_sindy_models
             sindys = [m for m in others if isinstance(m, SINDy)]
             if sindys:
-                self.last_sindy_fit = fit_sindy_models(sindys, train_trajs)
+                self.last_sindy_fit = fit_sindy_models(sindys, train_trajs, wide=self.sindy_wide_fit)
             others = [m for m in others if not isinstance(m, SINDy)]
         for m in others:
             m.train(train_trajs, silent=True)

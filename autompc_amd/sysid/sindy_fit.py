@@ -23,6 +23,12 @@ model ends up exactly as after its own ``train(trajs, xdot=xdot, alpha=alpha, ma
 ``set_coefficients``.
 
 ``stlsq_gram_host`` is the same algorithm in numpy (what the CPU tests run and the GPU tests compare against first).
+
+Libraries of 273..2048 features (``wide="device"``, opt-in).  The same algorithm on a second pair of kernels
+(``ampc_sindy_fit_wide``: the design rows of a run of 512-row splits materialised once, a rank-k MFMA pass that sums
+the splits in order, a Cholesky blocked by 32 columns whose trailing update runs on the matrix pipe; Gram pass and
+solves in waves under a memory budget).  A batch's models of at most 272 features keep the narrow call, the wider ones
+make one wide call; statuses 1 and 2 and libraries over 2048 features end in ``train()`` as before.
 """
 import numpy as np
 
@@ -31,6 +37,7 @@ from .linear_fit import PIVOT_EPS, SPLIT_ROWS, _row_start, concat_trajs
 from .sindy import SINDy, _features
 
 MAX_FEATURES, MAX_STATE, MAX_CTRL = 272, 64, 16
+MAX_FEATURES_WIDE = 2048               # with wide="device": libraries of 273..2048 features take ampc_sindy_fit_wide
 TIE_MARGIN = 2.0 ** -20                # relative distance of a coefficient to the threshold below which a fit is a tie
 
 
@@ -140,8 +147,9 @@ def stlsq_gram_host(traj_len, obs, ctrls, designs, configs, ycont=None, alpha=0.
 
 
 class SindyFitReport(list):
-    """One entry per model, in order: ``{"where": "device" | "host", "reason": None | str, "pivot", "margin",
-    "iters"}`` (the last three None when the Gram route was not tried).  ``host_fits``: the ``train()`` calls that
+    """One entry per model, in order: ``{"where": "device" | "host", "reason": None | str, "route": None | "narrow" |
+    "wide", "pivot", "margin", "iters"}`` (route: the Gram call that took the model, None when none did; the last
+    three None then).  ``host_fits``: the ``train()`` calls that
     were made (equal configurations share one); ``device_fits``: configurations fitted on the Gram route;
     ``designs``: Grams formed."""
     host_fits = 0
@@ -157,11 +165,11 @@ def _config_key(m):
     return (type(m), _library_key(m), m.time_mode, float(m.threshold))
 
 
-def _host_reason(m):
+def _host_reason(m, max_features=MAX_FEATURES):
     """Why a model cannot take the Gram route (None: it can)."""
     if type(m).train is not SINDy.train:
         return "subclass"
-    if (len(m.library[0]) > MAX_FEATURES or m.system.obs_dim > MAX_STATE
+    if (len(m.library[0]) > max_features or m.system.obs_dim > MAX_STATE
             or not 1 <= m.system.ctrl_dim <= MAX_CTRL):
         return "size"
     return None
@@ -175,22 +183,28 @@ def continuous_targets(trajs, dt, xdot=None):
     return np.concatenate([np.gradient(t.obs, dt, axis=0) for t in trajs])
 
 
-def fit_sindy_models(models, trajs, xdot=None, alpha=0.05, max_iter=20, device=0, backend="device"):
+def fit_sindy_models(models, trajs, xdot=None, alpha=0.05, max_iter=20, device=0, backend="device", wide="host"):
     """Fit untrained ``SINDy`` models of one system to `trajs`; every model ends up as after its own
     ``train(trajs, xdot=xdot, alpha=alpha, max_iter=max_iter)``.  Equal configurations are fitted once, models with
     equal libraries share a design.  Models the Gram route declines (module docstring) are fitted by ``train()``.
     backend="numpy" runs ``stlsq_gram_host`` in place of the device call (the check of the algorithm on a host without
-    a GPU; there is no automatic fallback).  Returns a ``SindyFitReport``."""
+    a GPU; there is no automatic fallback).  wide="device": models whose library has 273..2048 features take the
+    Gram route as well, in one ``ampc_sindy_fit_wide`` call next to the narrow one (backend="numpy":
+    ``stlsq_gram_host``, which has no limit); "host": they are fitted by ``train()`` (reason "size").  Returns a
+    ``SindyFitReport``."""
     if backend not in ("device", "numpy"):
         raise ValueError("backend must be 'device' or 'numpy'")
+    if wide not in ("host", "device"):
+        raise ValueError("wide must be 'host' or 'device'")
+    max_features = MAX_FEATURES_WIDE if wide == "device" else MAX_FEATURES
     models = list(models)
     for m in models:
         if not isinstance(m, SINDy):
             raise TypeError("fit_sindy_models fits SINDy models, not %s" % type(m).__name__)
         if m.system != models[0].system:
             raise ValueError("fit_sindy_models: the models must share one system")
-    report = SindyFitReport({"where": None, "reason": None, "pivot": None, "margin": None, "iters": None}
-                            for _ in models)
+    report = SindyFitReport({"where": None, "reason": None, "route": None, "pivot": None, "margin": None,
+                             "iters": None} for _ in models)
     groups = {}                                            # configuration -> indices of its models
     for i, m in enumerate(models):
         groups.setdefault(_config_key(m), []).append(i)
@@ -198,7 +212,7 @@ def fit_sindy_models(models, trajs, xdot=None, alpha=0.05, max_iter=20, device=0
     dev_keys, host = [], {}                                # host: configuration -> reason
     for key, members in groups.items():
         m = models[members[0]]
-        reason = _host_reason(m)
+        reason = _host_reason(m, max_features)
         if reason is None and m.time_mode == "continuous" and short:
             reason = "short trajectory"                    # np.gradient raises in train(): let it
         if reason is None:
@@ -211,28 +225,34 @@ def fit_sindy_models(models, trajs, xdot=None, alpha=0.05, max_iter=20, device=0
         ycont = None
         if any(k[2] == "continuous" for k in dev_keys):
             ycont = continuous_targets(trajs, models[0].system.dt, xdot)
-        design_of, designs = {}, []
-        configs = []
-        for key in dev_keys:
-            if key[1] not in design_of:
-                design_of[key[1]] = len(designs)
-                designs.append(models[groups[key][0]].library)
-            configs.append((design_of[key[1]], key[2] == "continuous", key[3]))
-        report.designs = len(designs)
-        if backend == "device":
-            out = _lib.sindy_fit(lens, obs, ctrls, designs, configs, ycont=ycont, alpha=alpha, max_iter=max_iter,
-                                 device=device)
-        else:
-            out = stlsq_gram_host(lens, obs, ctrls, designs, configs, ycont=ycont, alpha=alpha, max_iter=max_iter)
-        for key, c, s, p, mg, it in zip(dev_keys, *out):
-            stats[key] = {"pivot": float(p), "margin": float(mg), "iters": int(it)}
-            if s != 0:
-                host[key] = "status %d" % s
+        narrow = [k for k in dev_keys if len(models[groups[k][0]].library[0]) <= MAX_FEATURES]
+        routes = (("narrow", narrow, _lib.sindy_fit), ("wide", [k for k in dev_keys if k not in narrow],
+                                                         _lib.sindy_fit_wide))
+        for route, keys, call in routes:                   # one call per kernel family
+            if not keys:
                 continue
-            for i in groups[key]:
-                models[i].set_coefficients(c)
-                report[i].update(where="device", **stats[key])
-            report.device_fits += 1
+            design_of, designs = {}, []
+            configs = []
+            for key in keys:
+                if key[1] not in design_of:
+                    design_of[key[1]] = len(designs)
+                    designs.append(models[groups[key][0]].library)
+                configs.append((design_of[key[1]], key[2] == "continuous", key[3]))
+            report.designs += len(designs)
+            if backend == "device":
+                out = call(lens, obs, ctrls, designs, configs, ycont=ycont, alpha=alpha, max_iter=max_iter,
+                           device=device)
+            else:
+                out = stlsq_gram_host(lens, obs, ctrls, designs, configs, ycont=ycont, alpha=alpha, max_iter=max_iter)
+            for key, c, s, p, mg, it in zip(keys, *out):
+                stats[key] = {"route": route, "pivot": float(p), "margin": float(mg), "iters": int(it)}
+                if s != 0:
+                    host[key] = "status %d" % s
+                    continue
+                for i in groups[key]:
+                    models[i].set_coefficients(c)
+                    report[i].update(where="device", **stats[key])
+                report.device_fits += 1
     for key, reason in host.items():
         first = models[groups[key][0]]
         first.train(trajs, xdot=xdot, silent=True, alpha=alpha, max_iter=max_iter)

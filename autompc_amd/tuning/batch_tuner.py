@@ -46,7 +46,7 @@ class BatchPipelineTuner:
     def __init__(self, system, evaluator, batch_size=64, sampler=None, truedyn_noise="device",
                  eval_kwargs=None, keep_trajs=False, balance=None, models=None, model_factory=None,
                  trajs=None, as_configs=False, linear_fit="host", sindy_fit="host", lasso_fit="host",
-                 stable_fit="host", mlp_fit="torch"):
+                 stable_fit="host", mlp_fit="torch", sindy_wide_fit="host"):
         """truedyn_noise: the noise mode of the controllers scored against the true dynamics
         (MPPI(noise=...): "device" Philox, or "numpy" / "numpy_device" = the reference's global
         legacy stream).  eval_kwargs: extra keyword arguments for every ``evaluator.evaluate`` call
@@ -79,6 +79,10 @@ class BatchPipelineTuner:
 
         sindy_fit: the same for SINDy configurations ("device": one ``sysid.sindy_fit.fit_sindy_models`` call per
         shard); ``sindy_host_fits`` counts the ``train()`` calls it made.
+
+        sindy_wide_fit: with ``sindy_fit="device"``, "device" lets that call fit SINDy configurations whose library has
+        273..2048 features by ``ampc_sindy_fit_wide`` (``fit_sindy_models(..., wide="device")``) instead of handing
+        them to ``train()``.
 
         as_configs: report ``cfgs`` / ``inc_cfg`` as pipeline configurations with the reference's key names
         (`_ctrlr:horizon`, `_cost:<obs>_Q`, `_model:lr`, ...; tuning/configs.py) instead of candidate dicts;
@@ -127,6 +131,9 @@ class BatchPipelineTuner:
         if sindy_fit not in ("host", "device"):
             raise ValueError("sindy_fit must be 'host' or 'device'")
         self.sindy_fit = sindy_fit
+        if sindy_wide_fit not in ("host", "device"):
+            raise ValueError("sindy_wide_fit must be 'host' or 'device'")
+        self.sindy_wide_fit = sindy_wide_fit
         self.sindy_host_fits = 0
         self.batch_size = int(batch_size)
         if self.batch_size < 1:
@@ -232,7 +239,7 @@ class BatchPipelineTuner:
                 from ..sysid.sindy_fit import fit_sindy_models
                 sindys = [m for m in others if isinstance(m, SINDy)]
                 if sindys:
-                    self.sindy_host_fits += fit_sindy_models(sindys, self.trajs).host_fits
+                    self.sindy_host_fits += fit_sindy_models(sindys, self.trajs, wide=self.sindy_wide_fit).host_fits
                 others = [m for m in others if not isinstance(m, SINDy)]
             for m in others:
                 m.train(self.trajs, silent=True)

@@ -33,7 +33,8 @@ class BatchModelTuner:
     evaluator's own options decide where a batch's linear models are fitted and scored (``linear_fit="device"``,
     ``linear_kstep="device"``: ARX / Koopman models wider than 64 states in one k-step launch;
     ``sindy_kstep="device"``: a batch's SINDy models in one k-step launch; ``sindy_fit="device"``: their thresholded
-    fits in one ``ampc_sindy_fit`` call; ``mlp_fit="device"``: a batch's MLPs by the library's training kernels;
+    fits in one ``ampc_sindy_fit`` call, with ``sindy_wide_fit="device"`` those of 273..2048 features in one
+    ``ampc_sindy_fit_wide`` call; ``mlp_fit="device"``: a batch's MLPs by the library's training kernels;
     ``mlp_kstep="batch"``: a batch's MLPs of any mix of shapes scored by one ``ampc_kstep_errors_mlp`` launch, read where
     the fit left them).
     sampler: ``sampler(tuner, n, rng) -> n combined configurations``; the default draws a factory uniformly and
@@ -41,8 +42,15 @@ class BatchModelTuner:
     ``sample_arx_config`` / ``sample_koopman_config``; other factories need a
     ``sample_configuration(rng)`` method, ``sampler=`` or ``run(..., configs=...)``)."""
 
-    def __init__(self, system, evaluator, batch_size=64, sampler=None):
+    def __init__(self, system, evaluator, batch_size=64, sampler=None, sindy_wide_fit=None):
+        """sindy_wide_fit: None leaves the evaluator as it is; "host" / "device" sets the evaluator's option of that
+        name (``ModelEvaluator``: with ``sindy_fit="device"``, SINDy libraries of 273..2048 features fitted by
+        ``ampc_sindy_fit_wide``)."""
         self.system, self.evaluator = system, evaluator
+        if sindy_wide_fit is not None:
+            if sindy_wide_fit not in ("host", "device"):
+                raise ValueError("sindy_wide_fit must be 'host' or 'device'")
+            evaluator.sindy_wide_fit = sindy_wide_fit
         self.batch_size = int(batch_size)
         if self.batch_size < 1:
             raise ValueError("batch_size must be >= 1")

@@ -784,6 +784,21 @@ int ampc_sindy_fit(int device, int n_traj, const int* traj_len, int obs_dim, int
                    const double* cfg_threshold, double alpha, int max_iter, double* coeffs, int* status,
                    double* min_pivot, double* min_margin, int* iterations);
 
+/* ampc_sindy_fit for feature libraries of up to 2048 features: the same arguments, outputs, statistics and status
+ * rules on a second pair of kernels (every design of the call runs on them, also those of at most 272 features; the
+ * results need not be bit-equal to ampc_sindy_fit's, the order of summation differs).  Refused: a design outside
+ * 1..2048 features, obs_dim outside 1..64, ctrl_dim outside 1..16, and what ampc_sindy_fit refuses.  The Grams, the
+ * materialised design rows of one wave of the Gram pass and the workspaces of one wave of solves stay under a memory
+ * budget of AMPC_SINDY_WIDE_BUDGET_MB MiB (environment, default 8192; one row split of one design and one pair at the
+ * least); a configuration's result does not depend on how the waves were cut.  Deterministic as ampc_sindy_fit.
+ * Synchronises.  (Detected by its symbol: ampc_version() stays 114.) */
+int ampc_sindy_fit_wide(int device, int n_traj, const int* traj_len, int obs_dim, int ctrl_dim, const double* obs,
+                        const double* ctrls, const double* ycont, int n_designs, const int* feat_off,
+                        const int* pair_off, const int* kind, const int* a0, const int* a1, const double* par,
+                        const int* pair_var, const int* pair_exp, int n_configs, const int* cfg_design,
+                        const int* cfg_continuous, const double* cfg_threshold, double alpha, int max_iter,
+                        double* coeffs, int* status, double* min_pivot, double* min_margin, int* iterations);
+
 /* Lasso fits of Koopman models (sysid/koopman.py:150-156: sklearn's Lasso(alpha).fit with its defaults -- intercept
  * fitted and dropped, max_iter 1000, tol 1e-4, cyclic coordinate descent) of ONE data set in one call, by the same
  * descent run on the Gram.  Data as ampc_linfit_fit (obs_dim 1..256, ctrl_dim 1..16).  Bases: basis_n[n_bases] and the
