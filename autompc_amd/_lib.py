@@ -59,6 +59,8 @@ SIGNATURES = {
                                c_int, c_int, _ip, _ip]),
     "ampc_sindy_pred_batch": (c_int, [c_void_p, _dp, _dp, _dp, c_int]),
     "ampc_sindy_pred_diff_batch": (c_int, [c_void_p, _dp, _dp, _dp, _dp, _dp, c_int]),
+    "ampc_set_program": (c_int, [c_void_p, c_int, c_int, c_int, c_int, _ip, c_int, _dp, _ip]),
+    "ampc_program_rollout": (c_int, [c_void_p, c_int, c_int, _dp, _dp, _dp]),
     "ampc_set_quad_costs": (c_int, [c_void_p, c_int, c_int, _dp, _dp, _dp, _dp]),
     "ampc_set_indicator_costs": (c_int, [c_void_p, c_int, _ip, _dp]),
     "ampc_set_affine_quad_costs": (c_int, [c_void_p, c_int, c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
@@ -378,6 +380,35 @@ class Handle:
                                       iptr(pair_exp) if pair_exp.size else None))
         self.nx, self.nu = nx, nu
         self._sindy = True
+
+    def set_program(self, nx, nu, n_slots, code, consts, out_slot):
+        """Analytic dynamics as a straight-line program (ampc_set_program; sysid/program.py): code [n_instr][4] rows
+        (op, dst, a, b), consts the constant pool, out_slot [nx].  The library validates everything on the host and
+        refuses a malformed program with an AmpcError before anything is uploaded.  pred_batch, program_rollout and
+        the `surrogate` argument of the closed loops serve such a handle; it has no Jacobians and takes no plans."""
+        code = np.ascontiguousarray(code, dtype=np.int32).reshape(-1, 4)
+        consts = as_f64(consts).reshape(-1)
+        out_slot = np.ascontiguousarray(out_slot, dtype=np.int32).reshape(-1)
+        if out_slot.shape[0] != int(nx):
+            raise ValueError("out_slot needs one entry per state")
+        check(self.lib.ampc_set_program(self._h, int(nx), int(nu), int(n_slots), code.shape[0], iptr(code),
+                                        consts.shape[0], dptr(consts), iptr(out_slot)))
+        self.nx, self.nu = int(nx), int(nu)
+        self._sindy = False
+
+    def program_rollout(self, x0, ctrls):
+        """ampc_program_rollout: obs [n][T+1][nx] from x0 [n][nx] under ctrls [n][T][nu], one launch."""
+        x0, ctrls = as_f64(x0), as_f64(ctrls)
+        n = x0.shape[0]
+        if self.nx is None:                 # nothing staged: the library says so (it checks before it reads)
+            check(self.lib.ampc_program_rollout(self._h, n, 0, dptr(x0), dptr(ctrls), dptr(x0)))
+        if x0.shape != (n, self.nx) or ctrls.ndim != 3 or ctrls.shape[0] != n or ctrls.shape[2] != self.nu:
+            raise ValueError("program_rollout: x0 %r / ctrls %r do not match (n,%d) / (n,T,%d)"
+                             % (x0.shape, ctrls.shape, self.nx, self.nu))
+        T = ctrls.shape[1]
+        obs = np.empty((n, T + 1, self.nx))
+        check(self.lib.ampc_program_rollout(self._h, n, T, dptr(x0), dptr(ctrls), dptr(obs)))
+        return obs
 
     def pred_batch(self, states, ctrls):
         states, ctrls = as_f64(states), as_f64(ctrls)

@@ -108,6 +108,7 @@ extern "C" int ampc_ilqr_plan_create(ampc_handle* h, int B, int horizon, double 
                                      const int* cost_index, int clip_to_bounds,
                                      ampc_ilqr_plan** out) {
   REQUIRE(h && out, "ampc_ilqr_plan_create: NULL argument");
+  REQUIRE(!h->has_prog, std::string("ampc_ilqr_plan_create") + kProgNoPlan);
   if (h->has_lin) {      // wide linear models: ilqr_wide.hpp (V [nx][nx] in LDS, per-thread Quu solves)
     REQUIRE(h->nx <= kLinMaxIlqrNx, "ampc_ilqr_plan_create: iLQR on wide linear models takes up to 128 model states (the "
                                     "value function's Hessian lives in LDS); larger ones run MPPI and the closed loop");

@@ -96,6 +96,7 @@ extern "C" int ampc_lqr_plan_set_models(ampc_lqr_plan* p, ampc_handle* const* mo
   for (int i = 0; i < p->B; ++i) {
     const ampc_handle* m = models[i];
     REQUIRE(m, "ampc_lqr_plan_set_models: NULL model handle");
+    REQUIRE(!m->has_prog, std::string("ampc_lqr_plan_set_models") + kProgNoPlan);
     REQUIRE(m->lin_n > 0 && m->has_model(),
             "ampc_lqr_plan_set_models: LQR needs a linear model (ampc_set_linear; the reference's is_compatible, "
             "lqr.py:161-168)");

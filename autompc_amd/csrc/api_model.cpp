@@ -305,6 +305,7 @@ static void model_staged(ampc_handle* h) {
   h->has_mlp = true;
   h->has_sindy = false;
   h->has_lin = false;
+  h->has_prog = false;
   ampc_internal_jit_kick(h);   // (needs obs_dim: if the cost is set later, ampc_set_quad_costs starts it)
 }
 
@@ -479,7 +480,7 @@ static int set_linear_wide(ampc_handle* h, int nx, int nu, const double* A, cons
   std::memset(&h->md, 0, sizeof(h->md));
   std::memset(&h->mf, 0, sizeof(h->mf));
   h->md.nx = h->mf.nx = nx; h->md.nu = h->mf.nu = nu; h->md.kin = h->mf.kin = nx + nu;
-  h->has_lin = true; h->has_mlp = false; h->has_sindy = false;
+  h->has_lin = true; h->has_mlp = false; h->has_sindy = false; h->has_prog = false;
   return 0;
 }
 
@@ -675,6 +676,7 @@ static int lin_pred_impl(ampc_handle* h, const double* states, const double* ctr
 extern "C" int ampc_mlp_pred_batch(ampc_handle* h, const double* states, const double* ctrls,
                                    double* out, int n) {
   REQUIRE(h && states && ctrls && out, "ampc_mlp_pred_batch: NULL argument");
+  if (h->has_prog) return program_pred_batch(h, states, ctrls, out, n);
   if (h->has_sindy) return ampc_sindy_pred_batch(h, states, ctrls, out, n);
   if (h->has_lin) {
     if (n <= 0) return 0;
@@ -692,6 +694,7 @@ extern "C" int ampc_mlp_pred_batch(ampc_handle* h, const double* states, const d
 extern "C" int ampc_mlp_pred_diff_batch(ampc_handle* h, const double* states, const double* ctrls,
                                         double* out, double* jx, double* ju, int n) {
   REQUIRE(h && states && ctrls && out && jx && ju, "ampc_mlp_pred_diff_batch: NULL argument");
+  REQUIRE(!h->has_prog, kProgNoJacobian);
   if (h->has_sindy) return ampc_sindy_pred_diff_batch(h, states, ctrls, out, jx, ju, n);
   if (h->has_lin) {
     if (n <= 0) return 0;
@@ -862,6 +865,7 @@ extern "C" int ampc_set_sindy(ampc_handle* h, int nx, int nu, int n_feat, const 
   h->has_sindy = true;
   h->has_mlp = false;
   h->has_lin = false;
+  h->has_prog = false;
   return 0;
 }
 
@@ -878,6 +882,7 @@ extern "C" int ampc_sindy_pred_batch(ampc_handle* h, const double* states, const
 extern "C" int ampc_sindy_pred_diff_batch(ampc_handle* h, const double* states, const double* ctrls,
                                           double* out, double* jx, double* ju, int n) {
   REQUIRE(h && states && ctrls && out && jx && ju, "ampc_sindy_pred_diff_batch: NULL argument");
+  REQUIRE(!h->has_prog, kProgNoJacobian);
   REQUIRE(h->has_sindy, "ampc_sindy_pred_diff_batch: no SINDy model set");
   if (n <= 0) return 0;
   HIP_OK(hipSetDevice(h->device));

@@ -273,6 +273,7 @@ extern "C" int ampc_mppi_plan_create(ampc_handle* h, int B, const int* num_path,
                                      const int* horizon, const double* sigma, const double* lmda,
                                      const int* cost_index, int term_mode, ampc_mppi_plan** out) {
   REQUIRE(h && num_path && horizon && sigma && lmda && out, "ampc_mppi_plan_create: NULL argument");
+  REQUIRE(!h->has_prog, std::string("ampc_mppi_plan_create") + kProgNoPlan);
   REQUIRE(h->has_model() && h->n_costs > 0 && h->has_bounds,
           "ampc_mppi_plan_create: model, cost and control bounds must be set first");
   REQUIRE(B >= 1, "ampc_mppi_plan_create: B < 1");

@@ -1,7 +1,7 @@
 """Build libautompc_hip.so for gfx950 with hipcc (cross-compiles without a GPU).
 
-Thirty-five translation units compiled in parallel and linked into one shared library: api.cpp +
-api_{model,mppi,ilqr,lqr,linfit,sindyfit,lasso,stable,mlpfit,kstep_mlp}.cpp (the C ABI and host logic by family), launch_{mlp,mppi,ilqr,kstep,kstep_linear,kstep_sindy}.cpp
+Thirty-six translation units compiled in parallel and linked into one shared library: api.cpp +
+api_{model,program,mppi,ilqr,lqr,linfit,sindyfit,lasso,stable,mlpfit,kstep_mlp}.cpp (the C ABI and host logic by family), launch_{mlp,mppi,ilqr,kstep,kstep_linear,kstep_sindy}.cpp
 once per precision (-DAMPC_T=double|float), launch_lqr.cpp, launch_linfit.cpp, launch_sindyfit.cpp, launch_sindyfit_wide.cpp, launch_lasso.cpp, launch_stable.cpp, launch_mlpfit.cpp, launch_kstep_mlp.cpp, launch_mppi_table.cpp, launch_ilqr_table.cpp, launch_ilqr_sindy_table.cpp and launch_ilqr_linear_table.cpp (f64 only).
 """
 import concurrent.futures
@@ -21,7 +21,8 @@ def _headers():
     """Every header a translation unit may include: all of csrc/*.hpp and the public C header."""
     return sorted(glob.glob(os.path.join(HERE, "*.hpp"))) + [os.path.join(ROOT, "include", "autompc_hip.h")]
 # (object name, source file, extra flags)
-UNITS = [("api", "api.cpp", []), ("api_model", "api_model.cpp", []), ("api_mppi", "api_mppi.cpp", []),
+UNITS = [("api", "api.cpp", []), ("api_model", "api_model.cpp", []), ("api_program", "api_program.cpp", []),
+         ("api_mppi", "api_mppi.cpp", []),
          ("api_ilqr", "api_ilqr.cpp", [])] + [
     ("%s_%s" % (fam, t), "launch_%s.cpp" % fam, ["-DAMPC_T=%s" % t] + (["-DAMPC_T_IS_F64=1"] if t == "double" else []))
     for fam in ("mlp", "mppi", "ilqr", "kstep", "kstep_linear", "kstep_sindy") for t in ("double", "float")] + [

@@ -4,6 +4,7 @@
 //
 //   api.cpp                       the C ABI (include/autompc_hip.h), host logic, the small kernels
 //   api_model.cpp                 MLP staging: weight packing, ampc_set_mlp, ampc_set_mlp_dev
+//   api_program.cpp               analytic dynamics programs: ampc_set_program, ampc_program_rollout
 //   launch_mlp.cpp   -DAMPC_T=..  MLP forward / Jacobian launchers         } one unit per precision:
 //   launch_mppi.cpp  -DAMPC_T=..  MPPI rollout / update launcher           } each holds the explicit
 //   launch_ilqr.cpp  -DAMPC_T=..  iLQR sweep / line-search launcher        } instantiation for AMPC_T
@@ -30,6 +31,7 @@
 #include "mppi_rollout4.hpp"
 #include "rng_kernels.hpp"
 #include "sindy_kernels.hpp"
+#include "program_kernels.hpp"
 #include "mppi_sindy_choice_host.hpp"
 #include "score_kernels.hpp"
 #include "shapes.hpp"
@@ -132,7 +134,10 @@ struct ampc_handle {
   bool has_lin = false;           // wide linear model (65..256 states): linear_kernels.hpp
   int l_nxp = 0, l_kp = 0;
   DevBuf lin_buf;                 // fragments of [A | B], then the plain row-major copy
-  bool has_model() const { return has_mlp || has_sindy || has_lin; }
+  bool has_prog = false;          // analytic dynamics as a straight-line program (ampc_set_program): a SIMULATION model
+  int p_nslots = 0, p_ninstr = 0, p_nconst = 0;
+  DevBuf prog_int, prog_flt;      // code [n_instr][4] then out_slot [nx] (int); the constant pool (T)
+  bool has_model() const { return has_mlp || has_sindy || has_lin || has_prog; }
   int lin_n = 0;                  // > 0: the model came from ampc_set_linear with this many states
   unsigned lin_gen = 0;           // counts ampc_set_linear calls (an LQR plan notices a re-staged model)
   std::vector<double> lin_ab_host;  // its exact [A | B], f64 row-major [lin_n][lin_n + nu] (the LQR plans) ...
@@ -241,6 +246,24 @@ template <typename T> static LinDev<T> lin_of(const ampc_handle* h) {
   m.jp = m.plain + (size_t)round_up(h->nx * (h->nx + h->nu), 4);
   return m;
 }
+
+template <typename T> static ProgDev<T> prog_of(const ampc_handle* h) {
+  ProgDev<T> m;
+  m.nx = h->nx; m.nu = h->nu; m.n_slots = h->p_nslots; m.n_instr = h->p_ninstr;
+  m.code = (const int4*)h->prog_int.p;
+  m.out_slot = (const int*)h->prog_int.p + 4 * (size_t)h->p_ninstr;
+  m.consts = (const T*)h->prog_flt.p;
+  return m;
+}
+
+// A program is a simulation model only: it has no Jacobians and no controller plans (api_program.cpp).
+static const char* const kProgNoJacobian =
+    "the handle holds an analytic dynamics program (ampc_set_program), which has no Jacobians: pred_diff is not "
+    "available on it";
+static const char* const kProgNoPlan =
+    ": the handle holds an analytic dynamics program (ampc_set_program); a program is a simulation model (the "
+    "surrogate of a closed loop, ampc_program_rollout), not a controller model";
+int program_pred_batch(ampc_handle* h, const double* states, const double* ctrls, double* out, int n);
 
 template <typename T> static SindyDev<T> sindy_of(const ampc_handle* h) {
   SindyDev<T> m;

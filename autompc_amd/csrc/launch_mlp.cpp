@@ -176,6 +176,14 @@ template <typename T> int ilqr_refresh_jacobians(ampc_ilqr_plan* p) {
 // x_next[b] = surrogate.pred(x[b], u[b]) for B rows, all device pointers, enqueued on h's stream.
 template <typename T>
 int surrogate_step(ampc_handle* h, ampc_handle* sur, const void* x, const void* u, void* x_next, int B) {
+  if (sur->has_prog) {            // analytic true dynamics (ampc_set_program): program_kernels.hpp
+    const size_t lb = (size_t)sur->p_nslots * kProgLanes * sizeof(T);
+    HIP_OK(allow_lds(program_forward_kernel<T>, lb));
+    hipLaunchKernelGGL(program_forward_kernel<T>, dim3((B + kProgLanes - 1) / kProgLanes), dim3(kProgLanes), lb,
+                       h->stream, prog_of<T>(sur), (const T*)x, (const T*)u, (T*)x_next, B);
+    HIP_OK(hipGetLastError());
+    return 0;
+  }
   if (sur->has_lin) {
     const LinDev<T> lm = lin_of<T>(sur);
     const size_t lb = (size_t)16 * lin_xs(lm.kp, (int)sizeof(T)) * sizeof(T);

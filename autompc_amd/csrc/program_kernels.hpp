@@ -1,0 +1,136 @@
+// program_kernels.hpp -- analytic dynamics as a straight-line program (ampc_set_program): x' = f(x, u) written as
+// a list of three-address instructions over value slots, interpreted one row per lane.
+//
+//   instruction word  (op, dst, a, b)          slots 0 .. nx+nu-1 hold the row's [x | u] on entry
+//     PO_CONST  v[dst] = consts[a]             PO_SIN .. PO_TANH  v[dst] = f(v[a])  (device library, full precision)
+//     PO_ADD / SUB / MUL / DIV / MIN / MAX     v[dst] = v[a] op v[b]
+//     PO_NEG / PO_ABS                          v[dst] = -v[a], |v[a]|
+//     PO_POWI   v[dst] = v[a] ** b             b an integer in -64..64: repeated multiplication, left to right
+//   output i of the row is v[out_slot[i]].
+//
+// Rounding contract: every instruction rounds once, in T, in list order -- contraction is off in the interpreter, so
+// a * b + c stays two roundings as in the host evaluation (sysid/program.py), and add / sub / mul / div / sqrt / abs /
+// min / max / integer power agree with numpy bit for bit.
+//
+// LDS: the slots are [slot][lane] (consecutive lanes on consecutive words: no bank conflicts), n_slots * 64 * sizeof(T)
+// bytes; the rollout adds [nx][lane] for the hand-over of a step's outputs.  With the limits below the largest request
+// is (256 + 64) * 64 * 8 bytes = 160 KB, exactly what a workgroup can have.  The instruction words, the constant pool
+// and out_slot are indexed by wave-uniform values only, so they arrive through scalar loads and the opcode switch is
+// a scalar branch; every result leaves through ordinary vector stores.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace ampc {
+
+enum ProgOp {
+  PO_CONST = 0, PO_ADD, PO_SUB, PO_MUL, PO_DIV, PO_NEG, PO_SIN, PO_COS, PO_EXP, PO_SQRT, PO_ABS, PO_TANH, PO_POWI,
+  PO_MIN, PO_MAX, PO_COUNT
+};
+
+static constexpr int kProgMaxSlots = 256;    // value slots of a program (inputs included)
+static constexpr int kProgMaxInstr = 4096;   // instructions of a program
+static constexpr int kProgMaxNx = 64;        // outputs / states
+static constexpr int kProgMaxPow = 64;       // |exponent| of PO_POWI
+static constexpr int kProgLanes = 64;        // rows per workgroup: one wave
+
+template <typename T> struct ProgDev {
+  int nx, nu, n_slots, n_instr;
+  const int4* code;        // [n_instr] (op, dst, a, b)
+  const T* consts;         // [n_const]
+  const int* out_slot;     // [nx]
+};
+
+__device__ __forceinline__ double prog_sin(double x) { return sin(x); }
+__device__ __forceinline__ float prog_sin(float x) { return sinf(x); }
+__device__ __forceinline__ double prog_cos(double x) { return cos(x); }
+__device__ __forceinline__ float prog_cos(float x) { return cosf(x); }
+__device__ __forceinline__ double prog_exp(double x) { return exp(x); }
+__device__ __forceinline__ float prog_exp(float x) { return expf(x); }
+__device__ __forceinline__ double prog_tanh(double x) { return tanh(x); }
+__device__ __forceinline__ float prog_tanh(float x) { return tanhf(x); }
+__device__ __forceinline__ double prog_sqrt(double x) { return sqrt(x); }     // (correctly rounded, as is T's '/')
+__device__ __forceinline__ float prog_sqrt(float x) { return sqrtf(x); }
+__device__ __forceinline__ double prog_abs(double x) { return fabs(x); }
+__device__ __forceinline__ float prog_abs(float x) { return fabsf(x); }
+
+// The interpreter: v points at the lane's column of the [slot][kProgLanes] array.  Straight line, no barrier: a lane
+// touches its own column only.
+template <typename T> __device__ __forceinline__ void program_run(const ProgDev<T>& p, T* v) {
+#pragma clang fp contract(off)
+  constexpr int S = kProgLanes;
+  for (int i = 0; i < p.n_instr; ++i) {
+    const int4 w = p.code[i];
+    T r;
+    if (w.x == PO_CONST) {
+      r = p.consts[w.z];
+    } else {
+      const T a = v[w.z * S];
+      switch (w.x) {
+        case PO_ADD: r = a + v[w.w * S]; break;
+        case PO_SUB: r = a - v[w.w * S]; break;
+        case PO_MUL: r = a * v[w.w * S]; break;
+        case PO_DIV: r = a / v[w.w * S]; break;
+        case PO_MIN: { const T b = v[w.w * S]; r = (b != b || b < a) ? b : a; } break;   // (NaN propagates, as np.minimum)
+        case PO_MAX: { const T b = v[w.w * S]; r = (b != b || b > a) ? b : a; } break;
+        case PO_NEG: r = -a; break;
+        case PO_SIN: r = prog_sin(a); break;
+        case PO_COS: r = prog_cos(a); break;
+        case PO_EXP: r = prog_exp(a); break;
+        case PO_SQRT: r = prog_sqrt(a); break;
+        case PO_ABS: r = prog_abs(a); break;
+        case PO_TANH: r = prog_tanh(a); break;
+        default: {                               // PO_POWI: ((a * a) * a) * ..., then the reciprocal of that
+          const int e = w.w < 0 ? -w.w : w.w;
+          r = e == 0 ? (T)1 : a;
+          for (int k = 1; k < e; ++k) r = r * a;
+          if (w.w < 0) r = (T)1 / r;
+        } break;
+      }
+    }
+    v[w.y * S] = r;
+  }
+}
+
+// x_next[r] = f(x[r], u[r]) for B rows, one row per lane.  A row's inputs are all in LDS before its first output is
+// written, so x_next may be x.  Rows at or past B neither read nor write.
+template <typename T>
+__global__ __launch_bounds__(kProgLanes) void program_forward_kernel(const ProgDev<T> p, const T* x, const T* u,
+                                                                     T* x_next, int B) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  constexpr int S = kProgLanes;
+  T* v = reinterpret_cast<T*>(smem_raw) + threadIdx.x;
+  const long long r = (long long)blockIdx.x * S + threadIdx.x;
+  if (r >= B) return;
+  for (int i = 0; i < p.nx; ++i) v[i * S] = x[r * p.nx + i];
+  for (int j = 0; j < p.nu; ++j) v[(p.nx + j) * S] = u[r * p.nu + j];
+  program_run<T>(p, v);
+  for (int i = 0; i < p.nx; ++i) x_next[r * p.nx + i] = v[p.out_slot[i] * S];
+}
+
+// obs[n][0] = x0[n], obs[n][t+1] = f(obs[n][t], ctrls[n][t]): one lane per trajectory, the state stays in LDS between
+// steps.  A step's outputs go through a second LDS area [nx][lane] before they become the next inputs, so an output
+// that is an input slot, or a permutation of the inputs, reads nothing already overwritten.
+template <typename T>
+__global__ __launch_bounds__(kProgLanes) void program_rollout_kernel(const ProgDev<T> p, const T* __restrict__ x0,
+                                                                     const T* __restrict__ ctrls, T* __restrict__ obs,
+                                                                     int n, int n_steps) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  constexpr int S = kProgLanes;
+  T* v = reinterpret_cast<T*>(smem_raw) + threadIdx.x;
+  T* hand = v + (size_t)p.n_slots * S;
+  const long long r = (long long)blockIdx.x * S + threadIdx.x;
+  if (r >= n) return;
+  const int nx = p.nx, nu = p.nu;
+  T* row = obs + r * (n_steps + 1) * nx;
+  const T* uc = ctrls + r * n_steps * nu;
+  for (int i = 0; i < nx; ++i) { const T x = x0[r * nx + i]; v[i * S] = x; row[i] = x; }
+  for (int t = 0; t < n_steps; ++t) {
+    for (int j = 0; j < nu; ++j) v[(nx + j) * S] = uc[(long long)t * nu + j];
+    program_run<T>(p, v);
+    for (int i = 0; i < nx; ++i) hand[i * S] = v[p.out_slot[i] * S];
+    row += nx;
+    for (int i = 0; i < nx; ++i) { const T x = hand[i * S]; v[i * S] = x; row[i] = x; }
+  }
+}
+
+}  // namespace ampc

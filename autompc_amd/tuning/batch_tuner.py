@@ -46,7 +46,7 @@ class BatchPipelineTuner:
     def __init__(self, system, evaluator, batch_size=64, sampler=None, truedyn_noise="device",
                  eval_kwargs=None, keep_trajs=False, balance=None, models=None, model_factory=None,
                  trajs=None, as_configs=False, linear_fit="host", sindy_fit="host", lasso_fit="host",
-                 stable_fit="host", mlp_fit="torch", sindy_wide_fit="host"):
+                 stable_fit="host", mlp_fit="torch", sindy_wide_fit="host", truedyn_evaluator=None):
         """truedyn_noise: the noise mode of the controllers scored against the true dynamics
         (MPPI(noise=...): "device" Philox, or "numpy" / "numpy_device" = the reference's global
         legacy stream).  eval_kwargs: extra keyword arguments for every ``evaluator.evaluate`` call
@@ -86,8 +86,19 @@ class BatchPipelineTuner:
 
         as_configs: report ``cfgs`` / ``inc_cfg`` as pipeline configurations with the reference's key names
         (`_ctrlr:horizon`, `_cost:<obs>_Q`, `_model:lr`, ...; tuning/configs.py) instead of candidate dicts;
-        candidates that came from configurations (``run(..., configs=...)``) are always reported as those."""
+        candidates that came from configurations (``run(..., configs=...)``) are always reported as those.
+
+        truedyn_evaluator: a second evaluator of `evaluator`'s class that the caller built with the analytic true
+        dynamics as its simulation model (``surrogate=DynamicsProgram.trace(system, dynamics)``).  ``run()`` then
+        fills the true-dynamics column of every batch with ``truedyn_evaluator.evaluate(shard, seed=seed,
+        index_offset=...)`` -- the whole shard in one device-resident closed loop instead of one host ``simulate()``
+        per candidate -- on the SAME shard as the surrogate pass and after the same ``fit_models(shard)``, so
+        candidates that carry a fitted ``model`` have it at hand; with ``keep_trajs`` the trajectories go to
+        ``truedyn_trajs``.  ``run(truedyn=...)`` must not be given as well.  One difference from ``truedyn_score``:
+        MPPI noise on this path is the evaluator's (seed, global evaluation index) stream, not a per-candidate seed
+        of a drop-in controller (``truedyn_noise`` does not apply)."""
         self.system, self.evaluator = system, evaluator
+        self.truedyn_evaluator = truedyn_evaluator
         self.truedyn_noise = truedyn_noise
         self.eval_kwargs = dict(eval_kwargs or {})
         # keep_trajs: also record every candidate's surrogate trajectory as (obs rows, control rows)
@@ -145,6 +156,7 @@ class BatchPipelineTuner:
         self.cfgs, self.costs, self.inc_cfgs, self.inc_costs = [], [], [], []
         self.truedyn_costs, self.inc_truedyn_costs = [], []
         self.surr_trajs = []
+        self.truedyn_trajs = []
         self._inc_cfg, self._inc_cost, self._inc_truedyn = None, float("inf"), None
 
     def _is_lqr(self):
@@ -289,7 +301,7 @@ class BatchPipelineTuner:
                                   truedyn_costs=list(self.truedyn_costs),
                                   inc_truedyn_costs=list(self.inc_truedyn_costs),
                                   surr_trajs=list(self.surr_trajs),
-                                  truedyn_trajs=[], surr_tune_result=None)
+                                  truedyn_trajs=list(self.truedyn_trajs), surr_tune_result=None)
 
     # -- the loop -----------------------------------------------------------------------------
     def truedyn_score(self, cand, truedyn, seed=0):
@@ -354,7 +366,11 @@ class BatchPipelineTuner:
         with an identically seeded `rng` (proposals are drawn redundantly on every rank so that
         no broadcast is needed); each rank evaluates its contiguous shard of every batch and the
         scores are all-gathered.  With `truedyn`, every candidate is also scored against the true
-        dynamics (recorded, not used by the search).  Returns (incumbent, PipelineTuneResult)."""
+        dynamics (recorded, not used by the search); a tuner built with ``truedyn_evaluator`` does that on the
+        device for every batch, without `truedyn`.  Returns (incumbent, PipelineTuneResult)."""
+        if truedyn is not None and self.truedyn_evaluator is not None:
+            raise ValueError("the tuner has a truedyn_evaluator: it scores the true-dynamics column; do not pass "
+                             "truedyn= as well")
         done = 0
         while done < n_iters:
             n = min(self.batch_size, n_iters - done)
@@ -367,23 +383,23 @@ class BatchPipelineTuner:
                 batch = self.ask(n, rng)
             # randomness keyed by (seed, global evaluation index): scores do not depend on the
             # world size or on the batch size
-            kept = {}
+            kept, kept_td = {}, {}
 
-            def local(shard, lo, d=done):
+            def local(shard, lo, d=done, ev=None, keep=None):
                 # (lo: the shard's first index in the batch, or -- balanced shards -- all of its indices)
                 self.fit_models(shard)
                 t0 = time.perf_counter()
                 try:
-                    return evaluate(shard, lo, d)
+                    return evaluate(shard, lo, d, ev or self.evaluator, kept if keep is None else keep)
                 finally:
                     self.eval_seconds += time.perf_counter() - t0
 
-            def evaluate(shard, lo, d):
+            def evaluate(shard, lo, d, ev, kept):
                 if not self.keep_trajs:
-                    return self.evaluator.evaluate(shard, seed=seed, index_offset=d + lo, **self.eval_kwargs)
-                sc, obs, ctl = self.evaluator.evaluate(shard, seed=seed, index_offset=d + lo,
-                                                       return_trajectories=True, **self.eval_kwargs)
-                lens = getattr(self.evaluator, "last_lengths", None)
+                    return ev.evaluate(shard, seed=seed, index_offset=d + lo, **self.eval_kwargs)
+                sc, obs, ctl = ev.evaluate(shard, seed=seed, index_offset=d + lo,
+                                           return_trajectories=True, **self.eval_kwargs)
+                lens = getattr(ev, "last_lengths", None)
                 no = self.system.obs_dim
                 ids = global_ids(lo, len(shard))
                 for i in range(len(shard)):
@@ -396,6 +412,13 @@ class BatchPipelineTuner:
             if self.keep_trajs:
                 self.surr_trajs.extend(self._gather_trajs(kept, n))
             td = None
+            if self.truedyn_evaluator is not None:
+                # the same shards as the surrogate pass (same weights), after the same fit_models(shard): a
+                # candidate's fitted model is on the rank that scores it
+                td = evaluate_sharded(lambda shard, lo: local(shard, lo, ev=self.truedyn_evaluator, keep=kept_td),
+                                      batch, weights="auto" if self.balance else None)
+                if self.keep_trajs:
+                    self.truedyn_trajs.extend(self._gather_trajs(kept_td, n))
             if truedyn is not None:
                 td = evaluate_sharded(
                     lambda shard, lo, d=done: [self.truedyn_score(c, truedyn, seed=seed + d + lo + i)

@@ -48,7 +48,7 @@ int ampc_version(void);   /* 100 * major + minor; 104: + ampc_mppi_run_legacy; 1
                            *      + ampc_mppi_plan_set_model_table, + ampc_ilqr_plan_set_model_table, + ampc_mppi_plan_set_sindy_models,
                            *      + ampc_ilqr_plan_set_sindy_models, + ampc_mppi_plan_set_linear_models, + ampc_mppi_closed_loop_linear,
                            *      + ampc_ilqr_plan_set_linear_models, + ampc_ilqr_closed_loop_linear, + ampc_ilqr_linear_table_layout,
-                           *      + ampc_lqr_gains_ex, + ampc_lqr_plan_set_loop_ex
+                           *      + ampc_lqr_gains_ex, + ampc_lqr_plan_set_loop_ex, + ampc_set_program, + ampc_program_rollout
                            *      (no bump: callers detect them by their symbols) */
 int ampc_device_count(void);
 
@@ -162,6 +162,33 @@ int ampc_sindy_pred_diff_batch(ampc_handle* h, const double* states, const doubl
  * a request beyond the 160 KB a workgroup can have is refused before any launch. */
 int ampc_sindy_pred_lds(int f64, int nx, int nu, int n_feat, int n_trig, int n_pow, int n_mon, int n_pool,
                         int n_tab, int* staged, int* lds_bytes);
+
+/* ---- model: analytic dynamics as a straight-line program (a SIMULATION model) ---------------
+ * The closed-form true dynamics of a benchmark (benchmarks/cartpole.py, cartpole_v2.py: a handful of + - * / sin cos
+ * on the observation and the control) as a list of three-address instructions over value slots, interpreted on the
+ * device one row per lane (csrc/program_kernels.hpp).  Slots 0 .. nx+nu-1 hold [x | u] on entry; instruction i is
+ * code[i] = (op, dst, a, b):
+ *    0 const  v[dst] = consts[a]         1 add   2 sub   3 mul   4 div   v[dst] = v[a] op v[b]
+ *    5 neg    6 sin   7 cos   8 exp   9 sqrt   10 abs   11 tanh          v[dst] = f(v[a])
+ *   12 powi   v[dst] = v[a] ** b, b an integer in -64..64: ((v*v)*v).., then the reciprocal for b < 0
+ *   13 min   14 max  (a NaN operand gives NaN, as numpy.minimum / maximum)
+ * and output i is v[out_slot[i]].  Every instruction rounds once in the handle's precision, in list order, with no
+ * contraction: the exactly rounded operations (all but sin / cos / exp / tanh) reproduce a numpy evaluation of the
+ * same list bit for bit.  Limits: nx <= 64, nu <= 16, n_slots <= 256, n_instr <= 4096 (256 slots plus the rollout's
+ * 64 hand-over rows of 64 lanes of f64 are the 160 KB of LDS a workgroup can have).
+ * Everything is validated on the host before anything is uploaded -- unknown opcode, dst / operand slot >= n_slots,
+ * constant index >= n_const, a slot >= nx+nu read before it is written, an out_slot nothing wrote, a limit -- and a
+ * malformed program is a return code with an ampc_last_error() text, never a launch.
+ * A handle holding a program serves ampc_mlp_pred_batch, ampc_program_rollout and, as `surrogate`, every closed loop
+ * (a model whose state starts with the observation).  It has no Jacobians (the _pred_diff_batch entries refuse it)
+ * and is no controller model (MPPI / iLQR plan creation and the LQR model list refuse it). */
+int ampc_set_program(ampc_handle* h, int nx, int nu, int n_slots, int n_instr, const int* code, int n_const,
+                     const double* consts, const int* out_slot);
+/* obs_out[n][n_steps+1][nx]: row 0 is x0[n][nx], row t+1 the program applied to row t and ctrls[n][t][nu]; one
+ * launch, one lane per trajectory, the state stays on chip between steps (utils/data_generation.py's loops).  Row t+1
+ * equals what ampc_mlp_pred_batch returns for row t bit for bit. */
+int ampc_program_rollout(ampc_handle* h, int n, int n_steps, const double* x0, const double* ctrls,
+                         double* obs_out);
 
 /* ---- cost / bounds ------------------------------------------------------------------------
  * Replaces QuadCost (quad_cost.py:7-51) as read through Cost.eval_* (cost.py:66-213).
