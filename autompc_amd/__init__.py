@@ -10,11 +10,11 @@ from .task import Task
 from .costs import Cost, QuadCost, SumCost, ThresholdCost, BoxThresholdCost
 
 from .sysid import (Model, ModelFactory, MLP, MLPFactory, SINDy, SINDyFactory, ARX, ARXFactory,
-                    Koopman, KoopmanFactory, DynamicsProgram)
+                    Koopman, KoopmanFactory, DynamicsProgram, DifferentiableProgram)
 from .control import (Controller, ControllerFactory, MPPI, MPPIFactory, IterativeLQR,
                       IterativeLQRFactory, LQR, LQRFactory)
 from .utils import simulate
 
-__all__ = ["Model", "ModelFactory", "MLP", "MLPFactory", "SINDy", "SINDyFactory", "ARX", "ARXFactory", "Koopman", "KoopmanFactory", "DynamicsProgram", "Controller", "ControllerFactory",
+__all__ = ["Model", "ModelFactory", "MLP", "MLPFactory", "SINDy", "SINDyFactory", "ARX", "ARXFactory", "Koopman", "KoopmanFactory", "DynamicsProgram", "DifferentiableProgram", "Controller", "ControllerFactory",
            "MPPI", "MPPIFactory", "IterativeLQR", "IterativeLQRFactory", "LQR", "LQRFactory", "simulate", "System", "Trajectory", "TimeStep", "zeros", "empty", "extend", "Task",
            "Cost", "QuadCost", "SumCost", "ThresholdCost", "BoxThresholdCost"]

@@ -61,6 +61,8 @@ SIGNATURES = {
     "ampc_sindy_pred_diff_batch": (c_int, [c_void_p, _dp, _dp, _dp, _dp, _dp, c_int]),
     "ampc_set_program": (c_int, [c_void_p, c_int, c_int, c_int, c_int, _ip, c_int, _dp, _ip]),
     "ampc_program_rollout": (c_int, [c_void_p, c_int, c_int, _dp, _dp, _dp]),
+    "ampc_set_program_jvp": (c_int, [c_void_p, c_int, c_int, _ip, c_int, _dp, _ip]),
+    "ampc_program_pred_diff_batch": (c_int, [c_void_p, _dp, _dp, _dp, _dp, _dp, c_int]),
     "ampc_set_quad_costs": (c_int, [c_void_p, c_int, c_int, _dp, _dp, _dp, _dp]),
     "ampc_set_indicator_costs": (c_int, [c_void_p, c_int, _ip, _dp]),
     "ampc_set_affine_quad_costs": (c_int, [c_void_p, c_int, c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
@@ -385,7 +387,8 @@ class Handle:
         """Analytic dynamics as a straight-line program (ampc_set_program; sysid/program.py): code [n_instr][4] rows
         (op, dst, a, b), consts the constant pool, out_slot [nx].  The library validates everything on the host and
         refuses a malformed program with an AmpcError before anything is uploaded.  pred_batch, program_rollout and
-        the `surrogate` argument of the closed loops serve such a handle; it has no Jacobians and takes no plans."""
+        the `surrogate` argument of the closed loops serve such a handle; it has no Jacobians and takes no plans
+        until set_program_jvp stages its JVP."""
         code = np.ascontiguousarray(code, dtype=np.int32).reshape(-1, 4)
         consts = as_f64(consts).reshape(-1)
         out_slot = np.ascontiguousarray(out_slot, dtype=np.int32).reshape(-1)
@@ -395,6 +398,18 @@ class Handle:
                                         consts.shape[0], dptr(consts), iptr(out_slot)))
         self.nx, self.nu = int(nx), int(nu)
         self._sindy = False
+
+    def set_program_jvp(self, n_slots, code, consts, out_slot):
+        """The JVP program of the staged program (ampc_set_program_jvp; sysid/program.py derives it): 2 (nx + nu)
+        inputs [x | u | dx | du], out_slot [2 nx] = [f | J . (dx, du)].  With it the handle has pred_diff_batch and
+        takes MPPI plans.  set_program and every other model call drop it."""
+        code = np.ascontiguousarray(code, dtype=np.int32).reshape(-1, 4)
+        consts = as_f64(consts).reshape(-1)
+        out_slot = np.ascontiguousarray(out_slot, dtype=np.int32).reshape(-1)
+        if self.nx is not None and out_slot.shape[0] != 2 * self.nx:
+            raise ValueError("out_slot needs two entries per state")
+        check(self.lib.ampc_set_program_jvp(self._h, int(n_slots), code.shape[0], iptr(code), consts.shape[0],
+                                            dptr(consts), iptr(out_slot)))
 
     def program_rollout(self, x0, ctrls):
         """ampc_program_rollout: obs [n][T+1][nx] from x0 [n][nx] under ctrls [n][T][nu], one launch."""

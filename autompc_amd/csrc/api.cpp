@@ -125,7 +125,7 @@ void handle_release(ampc_handle* h) {
 static void handle_free(ampc_handle* h) {
   (void)hipSetDevice(h->device);
   (void)hipStreamSynchronize(h->stream);
-  DevBuf* bufs[] = {&h->model_buf, &h->lin_buf, &h->sindy_int, &h->sindy_flt, &h->cost_buf, &h->bounds_buf, &h->ubounds_buf, &h->ind_buf, &h->s_states,
+  DevBuf* bufs[] = {&h->model_buf, &h->lin_buf, &h->sindy_int, &h->sindy_flt, &h->prog_int, &h->prog_flt, &h->jvp_int, &h->jvp_flt, &h->cost_buf, &h->bounds_buf, &h->ubounds_buf, &h->ind_buf, &h->s_states,
                     &h->s_ctrls,   &h->s_out,      &h->s_dz,     &h->s_jx,       &h->s_ju};
   for (DevBuf* b : bufs) b->release();
   if (h->own_stream) (void)hipStreamDestroy(h->stream);

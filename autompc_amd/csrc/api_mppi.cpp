@@ -118,7 +118,7 @@ template <typename T> static int plan_build(ampc_mppi_plan* p) {
     REQUIRE(p->forced_mt <= 1, "ampc_mppi_plan_set_geometry: a plan that holds a table of linear models "
                                "(ampc_mppi_plan_set_linear_models) rolls out in 16-row tiles: tile_rows must be 0 or 16");
     p->mt = 1;
-  } else if (h->has_sindy) {
+  } else if (h->has_sindy || h->has_prog) {     // one sample per lane, 64-sample tiles
     p->mt = 4;
   } else if (h->has_lin) {
     REQUIRE(p->forced_mt <= 1, "ampc_mppi_plan_set_geometry: wide linear models roll out in 16-row tiles");
@@ -151,6 +151,9 @@ template <typename T> static int plan_build(ampc_mppi_plan* p) {
   } else if (h->has_sindy) {
     std::memset(&p->L, 0, sizeof(p->L));
     p->L.extra = (2 * nx + nu + h->s_ntab) * 64;   // per-thread columns: [x|u], next x, value table
+  } else if (h->has_prog) {
+    std::memset(&p->L, 0, sizeof(p->L));
+    p->L.extra = (h->p_nslots + nx) * 64;          // per-lane columns: the value slots, the hand-over rows
   } else if (h->has_lin) {
     std::memset(&p->L, 0, sizeof(p->L));
     p->L.xu_stride = lin_xs(h->l_kp, (int)sizeof(T));
@@ -163,7 +166,11 @@ template <typename T> static int plan_build(ampc_mppi_plan* p) {
   p->lds_cost = p->L.extra;
   p->lds_aseq = round_up(p->lds_cost + h->cost_stride + 3 * nu, 4);
   p->lds_bytes = ((size_t)p->lds_aseq + (size_t)p->max_h * nu) * sizeof(T);
-  REQUIRE(p->lds_bytes <= kLdsLimit, "mppi plan: model + horizon do not fit the 160 KB LDS");
+  if (h->has_prog) p->lds_bytes = mppi_program_lds_bytes(h);    // (the kernel reads the shifted sequence from global memory)
+  REQUIRE(p->lds_bytes <= kLdsLimit,
+          h->has_prog ? "mppi plan (" + std::to_string(h->p_nslots) + " program slots, " + std::to_string(nx) + " states)" +
+                            kProgPlanLds
+                      : std::string("mppi plan: model + horizon do not fit the 160 KB LDS"));
   if (h->has_sindy && !table && !lint) {
     // what the launch will request (launch_mppi.cpp asks mppi_sindy_choice_host.hpp the same question): the map above
     // has no staged feature program in it.  A program that does not fit on top of the one-thread kernel's columns is
@@ -182,7 +189,7 @@ template <typename T> static int plan_build(ampc_mppi_plan* p) {
   {  // fused update: keep the tile's clipped noise [max_h][M][nu] (+ 2M reduction slots) in LDS
     const int e0 = round_up(p->lds_aseq + p->max_h * nu, 4);
     const size_t bytes = ((size_t)e0 + (size_t)p->max_h * M * nu + 2 * M) * sizeof(T);
-    if ((!h->has_sindy || lint) && bytes <= kLdsLimit && env_int("AMPC_FUSED_UPDATE", 1) != 0) {
+    if (((!h->has_sindy && !h->has_prog) || lint) && bytes <= kLdsLimit && env_int("AMPC_FUSED_UPDATE", 1) != 0) {
       p->lds_eps = e0;
       p->lds_red = e0 + p->max_h * M * nu;
       p->lds_bytes = bytes;
@@ -199,7 +206,7 @@ template <typename T> static int plan_build(ampc_mppi_plan* p) {
     int sid = static_shape_of<T>(h, m);
     if (sid < 0 && (p->jit = jit::get<T>(h)) != nullptr) sid = 0;
     p->static_shape = sid;
-  } else if (!h->has_sindy && !h->has_lin && !p->quad && p->mt <= 2 && env_int("AMPC_STATIC", 1) != 0) {
+  } else if (!h->has_sindy && !h->has_lin && !h->has_prog && !p->quad && p->mt <= 2 && env_int("AMPC_STATIC", 1) != 0) {
     int sid = static_shape_of<T>(h, m);
     if (sid < 0 && (p->jit = jit::get<T>(h)) != nullptr) sid = 0;      // run-time compiled shape
     const int lv = sid >= 0 ? lds_variant_of<T>(m, p->L, M, h->nw) : -1;
@@ -273,7 +280,10 @@ extern "C" int ampc_mppi_plan_create(ampc_handle* h, int B, const int* num_path,
                                      const int* horizon, const double* sigma, const double* lmda,
                                      const int* cost_index, int term_mode, ampc_mppi_plan** out) {
   REQUIRE(h && num_path && horizon && sigma && lmda && out, "ampc_mppi_plan_create: NULL argument");
-  REQUIRE(!h->has_prog, std::string("ampc_mppi_plan_create") + kProgNoPlan);
+  // (a program is a controller model once its JVP is staged beside it: ampc_set_program_jvp)
+  REQUIRE(!h->has_prog || h->has_jvp, std::string("ampc_mppi_plan_create") + kProgNoPlan);
+  REQUIRE(!h->has_prog || h->n_costs == 0 || h->obs_dim == h->nx,
+          "ampc_mppi_plan_create: a program's state is the observation: the cost blocks must be on nx observations");
   REQUIRE(h->has_model() && h->n_costs > 0 && h->has_bounds,
           "ampc_mppi_plan_create: model, cost and control bounds must be set first");
   REQUIRE(B >= 1, "ampc_mppi_plan_create: B < 1");
@@ -1682,6 +1692,8 @@ extern "C" int ampc_mppi_plan_set_state_lift(ampc_mppi_plan* p, int n_basis, con
   REQUIRE(p, "ampc_mppi_plan_set_state_lift: NULL plan");
   if (n_basis <= 0) { p->lift_n = 0; return 0; }
   REQUIRE(kinds && params, "ampc_mppi_plan_set_state_lift: NULL argument");
+  REQUIRE(!p->h->has_prog, "ampc_mppi_plan_set_state_lift: the plan's controller model is an analytic dynamics program, "
+                           "whose state is the observation");
   REQUIRE(p->lint_n == 0, "ampc_mppi_plan_set_state_lift: the plan holds a table of linear models "
                           "(ampc_mppi_plan_set_linear_models), whose lifts are per model");
   REQUIRE(p->h->obs_dim >= 1 && n_basis * p->h->obs_dim == p->h->nx,

@@ -137,6 +137,12 @@ struct ampc_handle {
   bool has_prog = false;          // analytic dynamics as a straight-line program (ampc_set_program): a SIMULATION model
   int p_nslots = 0, p_ninstr = 0, p_nconst = 0;
   DevBuf prog_int, prog_flt;      // code [n_instr][4] then out_slot [nx] (int); the constant pool (T)
+  // ... and beside it, optionally, the program's JVP (ampc_set_program_jvp): 2 (nx + nu) inputs, 2 nx outputs.  A handle
+  // with both has Jacobians and is an MPPI controller model; every ampc_set_* model call drops the JVP.
+  bool has_jvp = false;
+  int j_nslots = 0, j_ninstr = 0, j_nconst = 0;
+  DevBuf jvp_int, jvp_flt;        // code [n_instr][4] then out_slot [2 nx] (int); the constant pool (T)
+  bool prog_diff() const { return has_prog && has_jvp; }
   bool has_model() const { return has_mlp || has_sindy || has_lin || has_prog; }
   int lin_n = 0;                  // > 0: the model came from ampc_set_linear with this many states
   unsigned lin_gen = 0;           // counts ampc_set_linear calls (an LQR plan notices a re-staged model)
@@ -256,13 +262,32 @@ template <typename T> static ProgDev<T> prog_of(const ampc_handle* h) {
   return m;
 }
 
-// A program is a simulation model only: it has no Jacobians and no controller plans (api_program.cpp).
+template <typename T> static ProgDev<T> jvp_of(const ampc_handle* h) {
+  ProgDev<T> m;
+  m.nx = h->nx; m.nu = h->nu; m.n_slots = h->j_nslots; m.n_instr = h->j_ninstr;
+  m.code = (const int4*)h->jvp_int.p;
+  m.out_slot = (const int*)h->jvp_int.p + 4 * (size_t)h->j_ninstr;
+  m.consts = (const T*)h->jvp_flt.p;
+  return m;
+}
+
+// LDS bytes of mppi_rollout_program_kernel (mppi_program_kernels.hpp): [n_slots][64] slots, [nx][64] hand-over rows,
+// the shared cost block and the bounds
+inline size_t mppi_program_lds_bytes(const ampc_handle* h) {
+  return ((size_t)(h->p_nslots + h->nx) * kProgLanes + (size_t)h->cost_stride + 3 * (size_t)h->nu) * h->esz();
+}
+
+// A program alone is a simulation model: no Jacobians and no controller plans (api_program.cpp).  With its JVP staged
+// beside it (ampc_set_program_jvp) it has Jacobians and MPPI plans; iLQR / LQR plans and the model tables still refuse.
 static const char* const kProgNoJacobian =
     "the handle holds an analytic dynamics program (ampc_set_program), which has no Jacobians: pred_diff is not "
     "available on it";
 static const char* const kProgNoPlan =
     ": the handle holds an analytic dynamics program (ampc_set_program); a program is a simulation model (the "
     "surrogate of a closed loop, ampc_program_rollout), not a controller model";
+static const char* const kProgPlanLds =
+    ": the program's value slots and hand-over rows for 64 samples ((n_slots + nx) * 64 values) and the cost block need "
+    "more than the 160 KB of LDS a workgroup can have; an f32 handle halves the need";
 int program_pred_batch(ampc_handle* h, const double* states, const double* ctrls, double* out, int n);
 
 template <typename T> static SindyDev<T> sindy_of(const ampc_handle* h) {

@@ -5,6 +5,7 @@
 #ifndef AMPC_JIT_PLUGIN
 #include "mppi_sindy_table_kernels.hpp"   // (SINDy models of mixed libraries in one plan: not part of a shape plugin)
 #include "mppi_linear_table_kernels.hpp"  // (linear models of mixed state dimension in one plan: likewise)
+#include "mppi_program_kernels.hpp"       // (an analytic dynamics program as the controller model: likewise)
 #endif
 
 #ifndef AMPC_T
@@ -123,6 +124,18 @@ template <typename T> int mppi_solve_impl(ampc_mppi_plan* p) {
     } else {
       return fail("internal: table rollout in f32");
     }
+  } else if (h->has_prog) {       // analytic dynamics program (mppi_program_kernels.hpp)
+    // (the map follows the program the handle holds NOW: a program staged after the plan was built may be larger)
+    if (!h->has_jvp) return fail(std::string("ampc_mppi_solve") + kProgNoPlan);
+    const size_t lb = mppi_program_lds_bytes(h);
+    if (lb > kLdsLimit) return fail(std::string("ampc_mppi_solve") + kProgPlanLds);
+    auto launch = [&](auto kernel) -> int {
+      HIP_OK(allow_lds(kernel, lb));
+      hipLaunchKernelGGL(kernel, dim3(p->n_tiles), dim3(kProgLanes), lb, h->stream, a, prog_of<T>(h));
+      return 0;
+    };
+    if (int rc = h->n_ind > 0 ? launch(mppi_rollout_program_kernel<T, true>)
+                              : launch(mppi_rollout_program_kernel<T, false>)) return rc;
   } else if (h->has_lin) {        // wide linear model (linear_kernels.hpp)
     HIP_OK(allow_lds(linear_rollout_kernel<T>, p->lds_bytes));
     hipLaunchKernelGGL(linear_rollout_kernel<T>, dim3(p->n_tiles), dim3(64 * kLinW), p->lds_bytes, h->stream, a,

@@ -6,6 +6,8 @@
 //     PO_ADD / SUB / MUL / DIV / MIN / MAX     v[dst] = v[a] op v[b]
 //     PO_NEG / PO_ABS                          v[dst] = -v[a], |v[a]|
 //     PO_POWI   v[dst] = v[a] ** b             b an integer in -64..64: repeated multiplication, left to right
+//     PO_SIGN   v[dst] = sign(v[a])            -1, 0 or +1, NaN stays NaN      } exact; in derived (JVP) programs:
+//     PO_LT     v[dst] = v[a] < v[b] ? 1 : 0                                   } the tangents of abs, min and max
 //   output i of the row is v[out_slot[i]].
 //
 // Rounding contract: every instruction rounds once, in T, in list order -- contraction is off in the interpreter, so
@@ -17,6 +19,10 @@
 // is (256 + 64) * 64 * 8 bytes = 160 KB, exactly what a workgroup can have.  The instruction words, the constant pool
 // and out_slot are indexed by wave-uniform values only, so they arrive through scalar loads and the opcode switch is
 // a scalar branch; every result leaves through ordinary vector stores.
+//
+// Jacobians: a handle may hold, beside its program, the program's JVP (ampc_set_program_jvp; derived on the host,
+// sysid/program.py): 2 (nx + nu) inputs [x | u | dx | du], 2 nx outputs [f | J . (dx, du)], the same instruction set,
+// run by the same interpreter.  program_jacobian_kernel gives every (row, unit direction) pair a lane.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -24,7 +30,7 @@ namespace ampc {
 
 enum ProgOp {
   PO_CONST = 0, PO_ADD, PO_SUB, PO_MUL, PO_DIV, PO_NEG, PO_SIN, PO_COS, PO_EXP, PO_SQRT, PO_ABS, PO_TANH, PO_POWI,
-  PO_MIN, PO_MAX, PO_COUNT
+  PO_MIN, PO_MAX, PO_SIGN, PO_LT, PO_COUNT
 };
 
 static constexpr int kProgMaxSlots = 256;    // value slots of a program (inputs included)
@@ -79,6 +85,8 @@ template <typename T> __device__ __forceinline__ void program_run(const ProgDev<
         case PO_SQRT: r = prog_sqrt(a); break;
         case PO_ABS: r = prog_abs(a); break;
         case PO_TANH: r = prog_tanh(a); break;
+        case PO_SIGN: r = a > (T)0 ? (T)1 : (a < (T)0 ? (T)-1 : (a == (T)0 ? (T)0 : a)); break;   // (as np.sign)
+        case PO_LT: r = a < v[w.w * S] ? (T)1 : (T)0; break;
         default: {                               // PO_POWI: ((a * a) * a) * ..., then the reciprocal of that
           const int e = w.w < 0 ? -w.w : w.w;
           r = e == 0 ? (T)1 : a;
@@ -130,6 +138,37 @@ __global__ __launch_bounds__(kProgLanes) void program_rollout_kernel(const ProgD
     for (int i = 0; i < nx; ++i) hand[i * S] = v[p.out_slot[i] * S];
     row += nx;
     for (int i = 0; i < nx; ++i) { const T x = hand[i * S]; v[i * S] = x; row[i] = x; }
+  }
+}
+
+// (next, jx, ju) of B rows from the JVP program q (header comment): lane l of the launch is row l / nv, direction
+// l % nv (nv = nx + nu).  It loads [x | u] of its row into slots 0 .. nv-1 and the unit seed e_j into slots
+// nv .. 2nv-1, runs q and writes column j of the row's Jacobian -- jx[r][i][j] for j < nx, ju[r][i][j - nx] otherwise;
+// the j == 0 lane also writes out[r][i] from the value outputs.  The values are recomputed per direction: one
+// interpreter, one rounding contract.  Lanes at or past B * nv return before touching memory.
+template <typename T>
+__global__ __launch_bounds__(kProgLanes) void program_jacobian_kernel(const ProgDev<T> q, const T* __restrict__ x,
+                                                                      const T* __restrict__ u, T* __restrict__ out,
+                                                                      T* __restrict__ jx, T* __restrict__ ju, int B,
+                                                                      int nx, int nu) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  constexpr int S = kProgLanes;
+  T* v = reinterpret_cast<T*>(smem_raw) + threadIdx.x;
+  const int nv = nx + nu;
+  const long long l = (long long)blockIdx.x * S + threadIdx.x;
+  if (l >= (long long)B * nv) return;
+  const long long r = l / nv;
+  const int j = (int)(l - r * nv);
+  for (int i = 0; i < nx; ++i) v[i * S] = x[r * nx + i];
+  for (int i = 0; i < nu; ++i) v[(nx + i) * S] = u[r * nu + i];
+  for (int i = 0; i < nv; ++i) v[(nv + i) * S] = i == j ? (T)1 : (T)0;
+  program_run<T>(q, v);
+  if (j == 0)
+    for (int i = 0; i < nx; ++i) out[r * nx + i] = v[q.out_slot[i] * S];
+  if (j < nx) {
+    for (int i = 0; i < nx; ++i) jx[(r * nx + i) * nx + j] = v[q.out_slot[nx + i] * S];
+  } else {
+    for (int i = 0; i < nx; ++i) ju[(r * nx + i) * nu + (j - nx)] = v[q.out_slot[nx + i] * S];
   }
 }
 

@@ -28,7 +28,32 @@ lanes of f64, are the 160 KB of LDS a workgroup can have.  A program beyond them
 
 Refused while tracing, with ``TypeError``: anything that would make the recorded list depend on the data --
 ``bool()`` of a symbol, a comparison used in ``if``, ``np.where``, a ufunc outside the table above.  No branch is
-ever baked in silently.  A program has no Jacobians (``pred_diff*`` raise) and cannot be a controller's model.
+ever baked in silently.  A ``DynamicsProgram`` has no Jacobians (``pred_diff*`` raise) and cannot be a controller's
+model.
+
+``DifferentiableProgram`` (``prog.differentiable()``, or ``DifferentiableProgram.trace`` / ``from_code``) is the opt-in
+subclass that has both.  At construction it derives the JVP program (Jacobian-vector product, forward mode) from the
+stored ``code``: a program of the same format with ``2(nx+nu)`` inputs ``[x | u | dx | du]`` and ``2nx`` outputs
+``[f | J.(dx, du)]``.  Every write gets a fresh value id, values and tangents are emitted in list order, a tangent
+known to be zero (constants, values that depend on no input) is folded away, and ``_allocate`` assigns the slots; the
+folded program is the definition.  Tangent rules (``r`` the instruction's own result, ``ta`` / ``tb`` the operands'
+tangents, every new instruction in the order written):
+
+    add sub neg   ta + tb, ta - tb, -ta                 mul   (ta * b) + (a * tb)
+    div           (ta - r * tb) / b                     sin cos   cos(a) * ta, -(sin(a) * ta)
+    exp sqrt tanh r * ta, ta / (r + r), (1 - r * r) * ta          abs   sign(a) * ta
+    powi n        0 | ta | (n * powi(a, n-1)) * ta | n < 0: (n * (r / a)) * ta
+    min(a, b)     s = lt(b, a): (s * tb) + ((1 - s) * ta)         max(a, b)   s = lt(a, b), the same tangent
+
+Two opcodes exist for derived programs (``from_code`` / ``validate`` accept them, the tracer still refuses comparisons
+and ``np.sign``); both are exact, so the rounding contract covers JVP programs unchanged:
+
+    15 sign  v[dst] = sign(v[a])  (-1, 0, +1; NaN stays NaN)       16 lt  v[dst] = v[a] < v[b] ? 1 : 0
+
+A ``DifferentiableProgram`` has ``pred_diff`` / ``pred_diff_batch`` (host: the JVP program once per unit direction;
+device: one lane per (row, direction), csrc/program_kernels.hpp), ``stage_into`` stages the program and then its JVP,
+and a handle with both is an MPPI controller model (csrc/mppi_program_kernels.hpp).  A JVP beyond ``MAX_SLOTS`` /
+``MAX_INSTR`` raises ``ValueError`` at construction.
 """
 import heapq
 import numbers
@@ -39,11 +64,12 @@ from .. import _lib
 from .model import Model
 
 (OP_CONST, OP_ADD, OP_SUB, OP_MUL, OP_DIV, OP_NEG, OP_SIN, OP_COS, OP_EXP, OP_SQRT, OP_ABS, OP_TANH, OP_POWI,
- OP_MIN, OP_MAX) = range(15)
+ OP_MIN, OP_MAX, OP_SIGN, OP_LT) = range(17)
 OP_NAMES = ("const", "add", "sub", "mul", "div", "neg", "sin", "cos", "exp", "sqrt", "abs", "tanh", "powi", "min",
-            "max")
-_BINARY = (OP_ADD, OP_SUB, OP_MUL, OP_DIV, OP_MIN, OP_MAX)
-_UNARY = (OP_NEG, OP_SIN, OP_COS, OP_EXP, OP_SQRT, OP_ABS, OP_TANH)
+            "max", "sign", "lt")
+_TRACED = OP_NAMES[1:OP_SIGN]          # what the tracer records; sign / lt appear in derived (JVP) programs only
+_BINARY = (OP_ADD, OP_SUB, OP_MUL, OP_DIV, OP_MIN, OP_MAX, OP_LT)
+_UNARY = (OP_NEG, OP_SIN, OP_COS, OP_EXP, OP_SQRT, OP_ABS, OP_TANH, OP_SIGN)
 MAX_SLOTS, MAX_INSTR, MAX_POW, MAX_OBS, MAX_CTRL = 256, 4096, 64, 64, 16
 
 
@@ -56,10 +82,14 @@ def powi(x, n):
     return (np.ones_like(x) / r) if n < 0 else r
 
 
+def _lt(a, b):
+    return (a < b).astype(a.dtype)
+
+
 _HOST_UNARY = {OP_NEG: np.negative, OP_SIN: np.sin, OP_COS: np.cos, OP_EXP: np.exp, OP_SQRT: np.sqrt,
-               OP_ABS: np.absolute, OP_TANH: np.tanh}
+               OP_ABS: np.absolute, OP_TANH: np.tanh, OP_SIGN: np.sign}
 _HOST_BINARY = {OP_ADD: np.add, OP_SUB: np.subtract, OP_MUL: np.multiply, OP_DIV: np.divide, OP_MIN: np.minimum,
-                OP_MAX: np.maximum}
+                OP_MAX: np.maximum, OP_LT: _lt}
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -202,7 +232,7 @@ class _Sym:
         op = _UFUNC_OPS.get(ufunc)
         if op is None:
             raise TypeError("DynamicsProgram.trace: numpy.%s is not an operation a program records (it knows: %s)"
-                            % (ufunc.__name__, ", ".join(OP_NAMES[1:])))
+                            % (ufunc.__name__, ", ".join(_TRACED)))
         if op in _UNARY:
             return self._un(op)
         a, b = (self.tape.sym(x, OP_NAMES[op]) for x in inputs)
@@ -225,9 +255,10 @@ class _Sym:
         return "<traced value %d>" % self.vid
 
 
-def _allocate(n_in, instr, outputs):
+def _allocate(n_in, instr, outputs, max_slots=MAX_SLOTS):
     """Value ids -> slots, reusing a slot after its value's last use.  Inputs sit in slots 0..n_in-1 (reusable after
-    their last use too: every step reloads them); outputs stay live to the end."""
+    their last use too: every step reloads them); outputs stay live to the end.  max_slots=None: no limit here, the
+    caller looks at the count returned."""
     n_val = n_in + len(instr)
     last = [-1] * n_val
     for k, (op, a, b) in enumerate(instr):
@@ -254,7 +285,7 @@ def _allocate(n_in, instr, outputs):
             d = heapq.heappop(free)
         else:
             d, top = top, top + 1
-            if top > MAX_SLOTS:
+            if max_slots is not None and top > max_slots:
                 raise ValueError("the traced dynamics keep more than %d values alive at once "
                                  "(DynamicsProgram.MAX_SLOTS: the slots of 64 rows live in LDS)" % MAX_SLOTS)
         v = n_in + k
@@ -265,15 +296,19 @@ def _allocate(n_in, instr, outputs):
     return code, np.array([slot[v] for v in outputs], dtype=np.int32), top
 
 
-def validate(nx, nu, n_slots, code, n_const, out_slot):
-    """The checks ampc_set_program makes (ValueError here), on the host arrays."""
+def validate(nx, nu, n_slots, code, n_const, out_slot, jvp=False):
+    """The checks ampc_set_program makes (ValueError here), on the host arrays; jvp: those of ampc_set_program_jvp,
+    for a program of 2 (nx + nu) inputs and 2 nx outputs."""
     if not (1 <= nx <= MAX_OBS and 1 <= nu <= MAX_CTRL):
         raise ValueError("a program takes 1..%d observations and 1..%d controls" % (MAX_OBS, MAX_CTRL))
-    if not nx + nu <= n_slots <= MAX_SLOTS:
-        raise ValueError("n_slots = %d: must cover the %d inputs and be at most %d" % (n_slots, nx + nu, MAX_SLOTS))
+    n_in, n_out = (2 * (nx + nu), 2 * nx) if jvp else (nx + nu, nx)
+    if len(out_slot) != n_out:
+        raise ValueError("out_slot needs %d entries, not %d" % (n_out, len(out_slot)))
+    if not n_in <= n_slots <= MAX_SLOTS:
+        raise ValueError("n_slots = %d: must cover the %d inputs and be at most %d" % (n_slots, n_in, MAX_SLOTS))
     if len(code) > MAX_INSTR:
         raise ValueError("%d instructions: at most %d" % (len(code), MAX_INSTR))
-    defined = [True] * (nx + nu) + [False] * (n_slots - nx - nu)
+    defined = [True] * n_in + [False] * (n_slots - n_in)
     for k, (op, d, a, b) in enumerate(np.asarray(code).tolist()):
         if not 0 <= op < len(OP_NAMES):
             raise ValueError("instruction %d: unknown opcode %d" % (k, op))
@@ -294,6 +329,26 @@ def validate(nx, nu, n_slots, code, n_const, out_slot):
     for i, s in enumerate(np.asarray(out_slot).tolist()):
         if not 0 <= s < n_slots or not defined[s]:
             raise ValueError("out_slot[%d] = %d names no defined slot" % (i, s))
+
+
+def _run(p, V, dtype):
+    """The list of `p` (code, consts, out_slot, n_slots) on the columns of V [n][n_in], in order, every instruction
+    in `dtype`: [n][len(out_slot)]."""
+    consts = p.consts.astype(dtype)
+    v = [None] * p.n_slots
+    for i in range(V.shape[1]):
+        v[i] = V[:, i].copy()
+    with np.errstate(all="ignore"):
+        for op, d, a, b in p.code.tolist():
+            if op == OP_CONST:
+                v[d] = np.full(V.shape[0], consts[a], dtype=dtype)
+            elif op == OP_POWI:
+                v[d] = powi(v[a], b)
+            elif op in _HOST_BINARY:
+                v[d] = _HOST_BINARY[op](v[a], v[b])
+            else:
+                v[d] = _HOST_UNARY[op](v[a])
+    return np.stack([v[s] for s in p.out_slot.tolist()], axis=1)
 
 
 class DynamicsProgram(Model):
@@ -364,23 +419,7 @@ class DynamicsProgram(Model):
         U = np.asarray(ctrls, dtype=dtype).reshape(-1, nu)
         if X.shape[0] != U.shape[0]:
             raise ValueError("states and ctrls need the same number of rows")
-        consts = self.consts.astype(dtype)
-        v = [None] * self.n_slots
-        for i in range(nx):
-            v[i] = X[:, i].copy()
-        for j in range(nu):
-            v[nx + j] = U[:, j].copy()
-        with np.errstate(all="ignore"):
-            for op, d, a, b in self.code.tolist():
-                if op == OP_CONST:
-                    v[d] = np.full(X.shape[0], consts[a], dtype=dtype)
-                elif op == OP_POWI:
-                    v[d] = powi(v[a], b)
-                elif op in _HOST_BINARY:
-                    v[d] = _HOST_BINARY[op](v[a], v[b])
-                else:
-                    v[d] = _HOST_UNARY[op](v[a])
-        return np.stack([v[s] for s in self.out_slot.tolist()], axis=1)
+        return _run(self, np.concatenate([X, U], axis=1), dtype)
 
     def pred(self, state, ctrl):
         return self.evaluate(np.asarray(state, dtype=np.float64)[None, :], np.atleast_1d(ctrl)[None, :])[0]
@@ -424,3 +463,172 @@ class DynamicsProgram(Model):
         state = self.__dict__.copy()
         state["_handles"] = {}
         return state
+
+    def differentiable(self):
+        """The same arrays as a DifferentiableProgram: Jacobians, and an MPPI controller model."""
+        return DifferentiableProgram(self.system, self.code, self.consts, self.out_slot, self.n_slots,
+                                     device=self.device)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# forward-mode derivative of a program, in the same instruction set
+# ---------------------------------------------------------------------------------------------------------------
+class ProgramArrays:
+    """The arrays of a program: code, consts, out_slot, n_slots (module docstring), for n_in input slots."""
+
+    def __init__(self, n_in, code, consts, out_slot, n_slots):
+        self.n_in = int(n_in)
+        self.code = np.ascontiguousarray(code, dtype=np.int32).reshape(-1, 4)
+        self.consts = np.ascontiguousarray(consts, dtype=np.float64).reshape(-1)
+        self.out_slot = np.ascontiguousarray(out_slot, dtype=np.int32).reshape(-1)
+        self.n_slots = int(n_slots)
+
+    def evaluate(self, inputs, dtype=np.float64):
+        """out [n][len(out_slot)] for inputs [n][n_in], every instruction in `dtype`."""
+        return _run(self, np.asarray(inputs, dtype=dtype).reshape(-1, self.n_in), dtype)
+
+
+def derive_jvp(nx, nu, code, consts, out_slot):
+    """The JVP program of (code, consts, out_slot) as ProgramArrays with 2 (nx + nu) inputs [x | u | dx | du] and
+    2 nx outputs [f | J . (dx, du)] (module docstring).  No limit is checked here: n_slots and the instruction count
+    are whatever the derivative needs."""
+    nv = nx + nu
+    n_in = 2 * nv
+    instr, pool, const_id = [], [float(c) for c in np.asarray(consts, dtype=np.float64)], {}
+
+    def emit(op, a, b=0):
+        instr.append((op, a, b))
+        return n_in + len(instr) - 1
+
+    def const(value):                    # a constant the rules need (1, n, 0): loaded once, at its first use
+        key = np.float64(value).tobytes()
+        if key not in const_id:
+            pool.append(float(value))
+            const_id[key] = emit(OP_CONST, len(pool) - 1)
+        return const_id[key]
+
+    cur = list(range(nv)) + [None] * MAX_SLOTS         # slot -> the value id it holds now
+    tan = {i: nv + i for i in range(nv)}               # value id -> its tangent's value id; absent: zero
+
+    def select(s, ta, tb):               # (s * tb) + ((1 - s) * ta)
+        m1 = emit(OP_MUL, s, tb) if tb is not None else None
+        m2 = emit(OP_MUL, emit(OP_SUB, const(1.0), s), ta) if ta is not None else None
+        if m1 is None or m2 is None:
+            return m1 if m2 is None else m2
+        return emit(OP_ADD, m1, m2)
+
+    for op, d, a, b in np.asarray(code, dtype=np.int64).reshape(-1, 4).tolist():
+        if op == OP_CONST:
+            cur[d] = emit(OP_CONST, a)
+            continue
+        va, vb = cur[a], (cur[b] if op in _BINARY else b)
+        ta, tb = tan.get(va), (tan.get(vb) if op in _BINARY else None)
+        r = emit(op, va, vb)
+        t = None
+        if op == OP_ADD:
+            t = emit(OP_ADD, ta, tb) if ta is not None and tb is not None else (ta if tb is None else tb)
+        elif op == OP_SUB:
+            if tb is None:
+                t = ta
+            else:
+                t = emit(OP_SUB, ta, tb) if ta is not None else emit(OP_NEG, tb)
+        elif op == OP_NEG:
+            t = emit(OP_NEG, ta) if ta is not None else None
+        elif op == OP_MUL:
+            m1 = emit(OP_MUL, ta, vb) if ta is not None else None
+            m2 = emit(OP_MUL, va, tb) if tb is not None else None
+            t = emit(OP_ADD, m1, m2) if m1 is not None and m2 is not None else (m1 if m2 is None else m2)
+        elif op == OP_DIV:
+            if tb is None:
+                t = emit(OP_DIV, ta, vb) if ta is not None else None
+            else:
+                m = emit(OP_MUL, r, tb)
+                t = emit(OP_DIV, emit(OP_SUB, ta, m) if ta is not None else emit(OP_NEG, m), vb)
+        elif op == OP_MIN:
+            if ta is not None or tb is not None:
+                t = select(emit(OP_LT, vb, va), ta, tb)
+        elif op == OP_MAX:
+            if ta is not None or tb is not None:
+                t = select(emit(OP_LT, va, vb), ta, tb)
+        elif ta is None:
+            pass                                       # a unary operation, a power or a comparison of a constant
+        elif op == OP_SIN:
+            t = emit(OP_MUL, emit(OP_COS, va), ta)
+        elif op == OP_COS:
+            t = emit(OP_NEG, emit(OP_MUL, emit(OP_SIN, va), ta))
+        elif op == OP_EXP:
+            t = emit(OP_MUL, r, ta)
+        elif op == OP_SQRT:
+            t = emit(OP_DIV, ta, emit(OP_ADD, r, r))
+        elif op == OP_TANH:
+            one = const(1.0)
+            t = emit(OP_MUL, emit(OP_SUB, one, emit(OP_MUL, r, r)), ta)
+        elif op == OP_ABS:
+            t = emit(OP_MUL, emit(OP_SIGN, va), ta)
+        elif op == OP_POWI:
+            n = int(b)
+            if n == 1:
+                t = ta
+            elif n >= 2:
+                t = emit(OP_MUL, emit(OP_MUL, const(n), emit(OP_POWI, va, n - 1)), ta)
+            elif n < 0:
+                t = emit(OP_MUL, emit(OP_MUL, const(n), emit(OP_DIV, r, va)), ta)
+        # (sign, lt: piecewise constant -- zero tangent)
+        cur[d] = r
+        if t is not None:
+            tan[r] = t
+    outs = [cur[s] for s in np.asarray(out_slot).reshape(-1).tolist()]
+    touts = [tan[v] if v in tan else const(0.0) for v in outs]
+    jcode, jout, n_slots = _allocate(n_in, instr, outs + touts, max_slots=None)
+    return ProgramArrays(n_in, jcode, pool, jout, max(n_slots, n_in))
+
+
+class DifferentiableProgram(DynamicsProgram):
+    """A DynamicsProgram with exact Jacobians: its JVP program (`jvp`: code, consts, out_slot, n_slots) is derived at
+    construction and staged beside the program, which also makes the handle an MPPI controller model."""
+
+    def __init__(self, system, code, consts, out_slot, n_slots, device=0):
+        super().__init__(system, code, consts, out_slot, n_slots, device=device)
+        nx, nu = system.obs_dim, system.ctrl_dim
+        self.jvp = derive_jvp(nx, nu, self.code, self.consts, self.out_slot)
+        if self.jvp.n_slots > MAX_SLOTS or self.jvp.code.shape[0] > MAX_INSTR:
+            raise ValueError("the JVP program of these dynamics needs %d value slots and %d instructions "
+                             "(the program itself: %d and %d); at most %d slots (DynamicsProgram.MAX_SLOTS) and %d "
+                             "instructions (MAX_INSTR)" % (self.jvp.n_slots, self.jvp.code.shape[0], self.n_slots,
+                                                           self.code.shape[0], MAX_SLOTS, MAX_INSTR))
+        validate(nx, nu, self.jvp.n_slots, self.jvp.code, self.jvp.consts.shape[0], self.jvp.out_slot, jvp=True)
+
+    def differentiable(self):
+        return self
+
+    def evaluate_jvp(self, states, ctrls, dtype=np.float64):
+        """(next [n][nx], jx [n][nx][nx], ju [n][nx][nu]) from the JVP program on the host, once per unit direction,
+        every instruction in `dtype` -- what the device computes, lane by lane."""
+        nx, nu = self.system.obs_dim, self.system.ctrl_dim
+        nv = nx + nu
+        X = np.asarray(states, dtype=dtype).reshape(-1, nx)
+        U = np.asarray(ctrls, dtype=dtype).reshape(-1, nu)
+        if X.shape[0] != U.shape[0]:
+            raise ValueError("states and ctrls need the same number of rows")
+        n = X.shape[0]
+        V = np.zeros((n, nv, 2 * nv), dtype=dtype)
+        V[:, :, :nx], V[:, :, nx:nv] = X[:, None, :], U[:, None, :]
+        V[:, np.arange(nv), nv + np.arange(nv)] = 1.0
+        out = self.jvp.evaluate(V.reshape(n * nv, 2 * nv), dtype).reshape(n, nv, 2 * nx)
+        jac = np.ascontiguousarray(out[:, :, nx:].transpose(0, 2, 1))          # [n][i][direction]
+        return out[:, 0, :nx].copy(), np.ascontiguousarray(jac[:, :, :nx]), np.ascontiguousarray(jac[:, :, nx:])
+
+    def pred_diff(self, state, ctrl):
+        nxt, jx, ju = self.pred_diff_batch(np.asarray(state, dtype=np.float64)[None, :], np.atleast_1d(ctrl)[None, :])
+        return nxt[0], jx[0], ju[0]
+
+    def pred_diff_batch(self, states, ctrls, device=False, precision="f64"):
+        if device:
+            nx, nu = self.system.obs_dim, self.system.ctrl_dim
+            return self._dev(precision).pred_diff_batch(np.asarray(states, dtype=np.float64).reshape(-1, nx),
+                                                        np.asarray(ctrls, dtype=np.float64).reshape(-1, nu))
+        return self.evaluate_jvp(states, ctrls)
+
+    def stage_into(self, handle):
+        super().stage_into(handle)
+        handle.set_program_jvp(self.jvp.n_slots, self.jvp.code, self.jvp.consts, self.jvp.out_slot)

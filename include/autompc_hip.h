@@ -48,7 +48,8 @@ int ampc_version(void);   /* 100 * major + minor; 104: + ampc_mppi_run_legacy; 1
                            *      + ampc_mppi_plan_set_model_table, + ampc_ilqr_plan_set_model_table, + ampc_mppi_plan_set_sindy_models,
                            *      + ampc_ilqr_plan_set_sindy_models, + ampc_mppi_plan_set_linear_models, + ampc_mppi_closed_loop_linear,
                            *      + ampc_ilqr_plan_set_linear_models, + ampc_ilqr_closed_loop_linear, + ampc_ilqr_linear_table_layout,
-                           *      + ampc_lqr_gains_ex, + ampc_lqr_plan_set_loop_ex, + ampc_set_program, + ampc_program_rollout
+                           *      + ampc_lqr_gains_ex, + ampc_lqr_plan_set_loop_ex, + ampc_set_program, + ampc_program_rollout,
+                           *      + ampc_set_program_jvp, + ampc_program_pred_diff_batch
                            *      (no bump: callers detect them by their symbols) */
 int ampc_device_count(void);
 
@@ -172,6 +173,7 @@ int ampc_sindy_pred_lds(int f64, int nx, int nu, int n_feat, int n_trig, int n_p
  *    5 neg    6 sin   7 cos   8 exp   9 sqrt   10 abs   11 tanh          v[dst] = f(v[a])
  *   12 powi   v[dst] = v[a] ** b, b an integer in -64..64: ((v*v)*v).., then the reciprocal for b < 0
  *   13 min   14 max  (a NaN operand gives NaN, as numpy.minimum / maximum)
+ *   15 sign  v[dst] = -1, 0 or +1 (NaN stays NaN)    16 lt  v[dst] = v[a] < v[b] ? 1 : 0    (both exact)
  * and output i is v[out_slot[i]].  Every instruction rounds once in the handle's precision, in list order, with no
  * contraction: the exactly rounded operations (all but sin / cos / exp / tanh) reproduce a numpy evaluation of the
  * same list bit for bit.  Limits: nx <= 64, nu <= 16, n_slots <= 256, n_instr <= 4096 (256 slots plus the rollout's
@@ -181,7 +183,8 @@ int ampc_sindy_pred_lds(int f64, int nx, int nu, int n_feat, int n_trig, int n_p
  * malformed program is a return code with an ampc_last_error() text, never a launch.
  * A handle holding a program serves ampc_mlp_pred_batch, ampc_program_rollout and, as `surrogate`, every closed loop
  * (a model whose state starts with the observation).  It has no Jacobians (the _pred_diff_batch entries refuse it)
- * and is no controller model (MPPI / iLQR plan creation and the LQR model list refuse it). */
+ * and is no controller model (MPPI / iLQR plan creation and the LQR model list refuse it) -- until
+ * ampc_set_program_jvp stages the program's JVP beside it (below). */
 int ampc_set_program(ampc_handle* h, int nx, int nu, int n_slots, int n_instr, const int* code, int n_const,
                      const double* consts, const int* out_slot);
 /* obs_out[n][n_steps+1][nx]: row 0 is x0[n][nx], row t+1 the program applied to row t and ctrls[n][t][nu]; one
@@ -189,6 +192,27 @@ int ampc_set_program(ampc_handle* h, int nx, int nu, int n_slots, int n_instr, c
  * equals what ampc_mlp_pred_batch returns for row t bit for bit. */
 int ampc_program_rollout(ampc_handle* h, int n, int n_steps, const double* x0, const double* ctrls,
                          double* obs_out);
+/* The JVP (Jacobian-vector product, forward-mode derivative) of the handle's program, as a program of the same format
+ * and instruction set with 2 (nx + nu) inputs [x | u | dx | du] -- slots 0 .. 2(nx+nu)-1 on entry -- and 2 nx outputs
+ * [f(x, u) | J(x, u) . (dx, du)] in out_slot[2 nx].  Needs a handle that holds a program (ampc_set_program first); the
+ * same limits (n_slots <= 256, n_instr <= 4096) and the same host-side validation as ampc_set_program, every refusal a
+ * return code with an ampc_last_error() text before anything is uploaded.  The constants are converted to the
+ * handle's precision.  ampc_set_program and every other ampc_set_* model call drop a staged JVP.
+ * The library CANNOT check that the JVP belongs to the program: it runs what it is given (sysid/program.py derives it).
+ * A handle with a program and its JVP
+ *   - has Jacobians: ampc_program_pred_diff_batch, and ampc_mlp_pred_diff_batch forwards to it;
+ *   - is an MPPI controller model: ampc_mppi_plan_create accepts it (csrc/mppi_program_kernels.hpp: one sample per
+ *     lane; (n_slots + nx) * 64 values and the cost block must fit the 160 KB of LDS, refused otherwise), and
+ *     ampc_mppi_solve / _run / _run_legacy / _closed_loop[_scored] work as for any plan, the program's state being the
+ *     observation.  ampc_mppi_plan_set_models, the three model tables, ampc_mppi_plan_set_state_lift,
+ *     ampc_ilqr_plan_create and ampc_lqr_plan_set_models refuse a program with or without a JVP. */
+int ampc_set_program_jvp(ampc_handle* h, int n_slots, int n_instr, const int* code, int n_const, const double* consts,
+                         const int* out_slot);
+/* out[n][nx], jx[n][nx][nx], ju[n][nx][nu] of n rows from the staged JVP: one lane per (row, input direction), the
+ * value recomputed per direction by the same interpreter, so out equals ampc_mlp_pred_batch bit for bit and a JVP of
+ * exactly rounded operations equals its host evaluation bit for bit.  f64 and f32 handles. */
+int ampc_program_pred_diff_batch(ampc_handle* h, const double* states, const double* ctrls, double* out, double* jx,
+                                 double* ju, int n);
 
 /* ---- cost / bounds ------------------------------------------------------------------------
  * Replaces QuadCost (quad_cost.py:7-51) as read through Cost.eval_* (cost.py:66-213).
