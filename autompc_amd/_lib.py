@@ -63,6 +63,8 @@ SIGNATURES = {
     "ampc_program_rollout": (c_int, [c_void_p, c_int, c_int, _dp, _dp, _dp]),
     "ampc_set_program_jvp": (c_int, [c_void_p, c_int, c_int, _ip, c_int, _dp, _ip]),
     "ampc_program_pred_diff_batch": (c_int, [c_void_p, _dp, _dp, _dp, _dp, _dp, c_int]),
+    "ampc_program_set_ilqr": (c_int, [c_void_p, c_int]),
+    "ampc_ilqr_plan_jacobians": (c_int, [c_void_p, _dp, _dp, c_int]),
     "ampc_set_quad_costs": (c_int, [c_void_p, c_int, c_int, _dp, _dp, _dp, _dp]),
     "ampc_set_indicator_costs": (c_int, [c_void_p, c_int, _ip, _dp]),
     "ampc_set_affine_quad_costs": (c_int, [c_void_p, c_int, c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
@@ -410,6 +412,11 @@ class Handle:
             raise ValueError("out_slot needs two entries per state")
         check(self.lib.ampc_set_program_jvp(self._h, int(n_slots), code.shape[0], iptr(code), consts.shape[0],
                                             dptr(consts), iptr(out_slot)))
+
+    def set_program_ilqr(self, enable=True):
+        """ampc_program_set_ilqr: the opt-in that lets IlqrPlan take this handle's program (f64; needs the JVP staged).
+        set_program, set_program_jvp and every other model call clear it."""
+        check(self.lib.ampc_program_set_ilqr(self._h, int(bool(enable))))
 
     def program_rollout(self, x0, ctrls):
         """ampc_program_rollout: obs [n][T+1][nx] from x0 [n][nx] under ctrls [n][T][nu], one launch."""
@@ -938,6 +945,19 @@ class IlqrPlan:
         it, rows = ctypes.c_longlong(), ctypes.c_longlong()
         check(self.lib.ampc_ilqr_plan_stats(self._p, ctypes.byref(it), ctypes.byref(rows)))
         return {"iterations": it.value, "candidate_rows": rows.value}
+
+    def jacobians(self):
+        """(jx [B][H][nx][nx], ju [B][H][nx][nu]) as the last refresh left them (ampc_ilqr_plan_jacobians)."""
+        nx, nu = self.handle.nx, self.handle.nu
+        jx, ju = np.empty((self.B, self.H, nx, nx)), np.empty((self.B, self.H, nx, nu))
+        check(self.lib.ampc_ilqr_plan_jacobians(self._p, dptr(jx), dptr(ju), 0))
+        return jx, ju
+
+    def set_jacobians(self, jx, ju):
+        """Overwrite the plan's Jacobian rows (tests: which rows does a refresh leave alone?)."""
+        nx, nu = self.handle.nx, self.handle.nu
+        jx, ju = as_f64(jx).reshape(self.B, self.H, nx, nx), as_f64(ju).reshape(self.B, self.H, nx, nu)
+        check(self.lib.ampc_ilqr_plan_jacobians(self._p, dptr(jx), dptr(ju), 1))
 
     def solve(self, x0, uguess, max_iter=50):
         nx, nu, B, H = self.handle.nx, self.handle.nu, self.B, self.H

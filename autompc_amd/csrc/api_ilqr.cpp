@@ -35,12 +35,20 @@ template <typename T> static int ilqr_plan_build(ampc_ilqr_plan* p) {
   const MlpDev<T>& m = model_of<T>(h);
   const int nx = h->nx, nu = h->nu, B = p->B, H = p->H;
   const IlqrWork wk = make_ilqr_work(nx, nu, h->cost_stride, h->has_lin);
+  p->prog_slots = 0;
   if (h->has_sindy) {
     std::memset(&p->L, 0, sizeof(p->L));
     p->L.xu = 0;
     p->L.xu_stride = nx + nu + 1;
     p->lds_xn = round_up(16 * p->L.xu_stride, 4);
     p->L.extra = round_up(p->lds_xn + 16 * nx + 16 * h->s_ntab, 4);   // xnext + table scratch
+  } else if (h->has_prog) {        // [x | u] rows, the outputs' hand-over [16][nx], the forward program's slots [n_slots][16]
+    std::memset(&p->L, 0, sizeof(p->L));
+    p->L.xu = 0;
+    p->L.xu_stride = nx + nu + 1;
+    p->lds_xn = round_up(16 * p->L.xu_stride, 4);
+    p->L.extra = round_up(p->lds_xn + 16 * nx + 16 * h->p_nslots, 4);
+    p->prog_slots = h->p_nslots;
   } else if (h->has_lin) {         // line search: [x | u] rows for lin_tile, next states, compact work map
     std::memset(&p->L, 0, sizeof(p->L));
     p->L.xu = 0;
@@ -52,6 +60,16 @@ template <typename T> static int ilqr_plan_build(ampc_ilqr_plan* p) {
   }
   p->lds_work = p->L.extra;
   p->lds_bytes = ((size_t)p->lds_work + wk.total) * sizeof(T);
+  // a program plan whose full map does not fit (the dense cost block and the sweep's matrices grow with nx^2): the line
+  // search on the compact map -- it never touches the sweep's matrices -- and the sweep without its LDS copy of the
+  // cost block.  Same results as the full map bit for bit; plans that fit the full map keep it.
+  p->prog_compact = 0;
+  size_t sweep_bytes = (size_t)wk.total * sizeof(T);
+  if (h->has_prog && p->lds_bytes > kLdsLimit) {
+    p->prog_compact = 1;
+    p->lds_bytes = ((size_t)p->lds_work + make_ilqr_work(nx, nu, h->cost_stride, true).total) * sizeof(T);
+    sweep_bytes = (size_t)make_ilqr_work(nx, nu, 0).total * sizeof(T);
+  }
   p->use_ls4 = env_int("AMPC_LS4", 1) != 0;
   p->use_mfma_sweep = env_int("AMPC_RICCATI", 1) != 0;
   p->par_passes = env_int("AMPC_LS4_PAR", 1) != 0;
@@ -59,7 +77,7 @@ template <typename T> static int ilqr_plan_build(ampc_ilqr_plan* p) {
   { const int rb = env_int("AMPC_LS4_RB", 0); p->ls_rb = (rb == 1 || rb == 3) ? rb : 0; }
   p->static_shape = -1;
   p->jit = nullptr;
-  if (!h->has_sindy && !h->has_lin && env_int("AMPC_STATIC", 1) != 0) {
+  if (!h->has_sindy && !h->has_lin && !h->has_prog && env_int("AMPC_STATIC", 1) != 0) {
     int sid = static_shape_of<T>(h, m);
     if (sid < 0 && (p->jit = jit::get<T>(h)) != nullptr) sid = 0;      // run-time compiled shape
     if (sid >= 0) {
@@ -68,8 +86,11 @@ template <typename T> static int ilqr_plan_build(ampc_ilqr_plan* p) {
     }
     if (p->static_shape < 0) p->jit = nullptr;
   }
+  if (h->has_prog)
+    REQUIRE(p->lds_bytes <= kLdsLimit && sweep_bytes <= kLdsLimit, "ilqr plan (" + std::to_string(h->p_nslots) + " program slots, " + std::to_string(nx) +
+                                           " states)" + kProgIlqrLds);
   REQUIRE(p->lds_bytes <= kLdsLimit, "ilqr plan: model does not fit the 160 KB LDS");
-  REQUIRE((size_t)wk.total * sizeof(T) <= kLdsLimit,
+  REQUIRE(sweep_bytes <= kLdsLimit,
           "ilqr plan: the Riccati workspace for this state dimension does not fit the 160 KB LDS");
   if (h->has_lin)
     REQUIRE((size_t)make_wide_lds(nx, nu, h->obs_dim).total * sizeof(T) <= kLdsLimit,
@@ -98,7 +119,7 @@ template <typename T> static int ilqr_plan_build(ampc_ilqr_plan* p) {
   HIP_OK(hipMemsetAsync(p->flags.p, 0, (size_t)9 * B * sizeof(int), h->stream));
   const int rows = B * H;
   const int n_pad = round_up(rows, 64);
-  if (!h->has_sindy && !h->has_lin) HIP_OK(p->dz.reserve((size_t)m.n_hidden * n_pad * m.hpad * e));
+  if (!h->has_sindy && !h->has_lin && !h->has_prog) HIP_OK(p->dz.reserve((size_t)m.n_hidden * n_pad * m.hpad * e));
   HIP_OK(p->ric.reserve((size_t)kRicStride * p->B * e));
   HIP_OK(hipStreamSynchronize(h->stream));
   return 0;
@@ -108,7 +129,13 @@ extern "C" int ampc_ilqr_plan_create(ampc_handle* h, int B, int horizon, double 
                                      const int* cost_index, int clip_to_bounds,
                                      ampc_ilqr_plan** out) {
   REQUIRE(h && out, "ampc_ilqr_plan_create: NULL argument");
-  REQUIRE(!h->has_prog, std::string("ampc_ilqr_plan_create") + kProgNoPlan);
+  REQUIRE(!h->has_prog || (h->has_jvp && h->prog_ilqr), std::string("ampc_ilqr_plan_create") + kProgNoPlan);
+  if (h->has_prog) {     // the opt-in (ampc_program_set_ilqr): the sixteen-row line search on the interpreter, f64
+    REQUIRE(h->precision == AMPC_F64, "ampc_ilqr_plan_create: iLQR on an analytic dynamics program is built for f64 "
+                                      "handles; this program's handle is f32");
+    REQUIRE(h->n_costs == 0 || h->obs_dim == h->nx,
+            "ampc_ilqr_plan_create: the program's state is the observation: the cost blocks must be on nx observations");
+  }
   if (h->has_lin) {      // wide linear models: ilqr_wide.hpp (V [nx][nx] in LDS, per-thread Quu solves)
     REQUIRE(h->nx <= kLinMaxIlqrNx, "ampc_ilqr_plan_create: iLQR on wide linear models takes up to 128 model states (the "
                                     "value function's Hessian lives in LDS); larger ones run MPPI and the closed loop");
@@ -198,6 +225,36 @@ extern "C" int ampc_ilqr_plan_stats(ampc_ilqr_plan* p, long long* iterations, lo
 extern "C" int ampc_ilqr_plan_set_terminal_goal(ampc_ilqr_plan* p, int use_goal) {
   REQUIRE(p, "ampc_ilqr_plan_set_terminal_goal: NULL plan");
   p->term_goal = use_goal ? 1 : 0;
+  return 0;
+}
+
+extern "C" int ampc_ilqr_plan_jacobians(ampc_ilqr_plan* p, double* jx, double* ju, int write) {
+  REQUIRE(p && jx && ju, "ampc_ilqr_plan_jacobians: NULL argument");
+  ampc_handle* h = p->h;
+  REQUIRE(!h->has_lin && p->table_n == 0 && p->sindy_n == 0 && p->lqt_n == 0 && p->jx.p && p->ju.p,
+          "ampc_ilqr_plan_jacobians: the plan keeps no per-row Jacobians of its handle's model (a linear model's are "
+          "constant; a model table keeps its own)");
+  HIP_OK(hipSetDevice(h->device));
+  HIP_OK(hipStreamSynchronize(h->stream));
+  const size_t rows = (size_t)p->B * p->H, nx = h->nx, nu = h->nu;
+  if (h->precision == AMPC_F64) {
+    if (write) {
+      HIP_OK(upload_converted<double>(p->jx.p, jx, rows * nx * nx, h->stream));
+      HIP_OK(upload_converted<double>(p->ju.p, ju, rows * nx * nu, h->stream));
+      HIP_OK(hipStreamSynchronize(h->stream));
+    } else {
+      HIP_OK(download_converted<double>(jx, p->jx.p, rows * nx * nx, h->stream));
+      HIP_OK(download_converted<double>(ju, p->ju.p, rows * nx * nu, h->stream));
+    }
+  } else {
+    if (write) {
+      HIP_OK(upload_converted<float>(p->jx.p, jx, rows * nx * nx, h->stream));
+      HIP_OK(upload_converted<float>(p->ju.p, ju, rows * nx * nu, h->stream));
+    } else {
+      HIP_OK(download_converted<float>(jx, p->jx.p, rows * nx * nx, h->stream));
+      HIP_OK(download_converted<float>(ju, p->ju.p, rows * nx * nu, h->stream));
+    }
+  }
   return 0;
 }
 
@@ -321,6 +378,7 @@ extern "C" int ampc_ilqr_solve(ampc_ilqr_plan* p, const double* x0, const double
                                int* converged, int* iters, int* status, double* objective) {
   REQUIRE(p && x0 && uguess, "ampc_ilqr_solve: NULL argument");
   REQUIRE(max_iter >= 0, "ampc_ilqr_solve: max_iter < 0");
+  if (int rc = ilqr_program_plan_check(p, "ampc_ilqr_solve")) return rc;
   REQUIRE(p->lqt_n == 0, "ampc_ilqr_solve: the plan holds a table of linear models (ampc_ilqr_plan_set_linear_models), whose "
                          "problems name their model: use ampc_ilqr_solve_queue_var");
   HIP_OK(hipSetDevice(p->h->device));
@@ -531,6 +589,7 @@ static int check_horizons(const ampc_ilqr_plan* p, int n, const int* horizon, co
 
 static int check_models(const ampc_ilqr_plan* p, int n, const int* model_index, const char* who) {
   if (model_index) {
+    REQUIRE(p->prog_slots == 0, std::string(who) + ": model_index given" + kProgIlqrNoTable);
     REQUIRE(!p->models.empty() || p->table_n > 0 || p->sindy_n > 0 || p->lqt_n > 0,
             std::string(who) + ": model_index given but the plan has no model table (ampc_ilqr_plan_set_models)");
     const int n_models = p->table_n > 0 ? p->table_n : p->sindy_n > 0 ? p->sindy_n : p->lqt_n > 0 ? p->lqt_n : (int)p->models.size();
@@ -550,6 +609,7 @@ extern "C" int ampc_ilqr_plan_set_models(ampc_ilqr_plan* p, int n_models, ampc_h
     return 0;
   }
   REQUIRE(n_models >= 1 && models, "ampc_ilqr_plan_set_models: NULL argument");
+  REQUIRE(p->prog_slots == 0, std::string("ampc_ilqr_plan_set_models") + kProgIlqrNoTable);
   REQUIRE(p->table_n == 0, "ampc_ilqr_plan_set_models: the plan holds a table of MLP models of mixed shapes "
                            "(ampc_ilqr_plan_set_model_table); remove it first");
   REQUIRE(p->sindy_n == 0, "ampc_ilqr_plan_set_models: the plan holds a table of SINDy models "
@@ -592,6 +652,7 @@ extern "C" int ampc_ilqr_plan_set_model_table(ampc_ilqr_plan* p, int n_models, c
     p->table_models.release(); p->table_stage.release(); p->table_dz.release();
     return ilqr_plan_build<double>(p);               // (the kernel choices of the handle's shape)
   }
+  if (p->prog_slots > 0) return fail(std::string("ampc_ilqr_plan_set_model_table") + kProgIlqrNoTable);
   if (p->sindy_n > 0)
     return ilqr_table_fail("the plan holds a table of SINDy models (ampc_ilqr_plan_set_sindy_models); remove it first");
   if (p->lqt_n > 0)
@@ -694,6 +755,7 @@ extern "C" int ampc_ilqr_plan_set_sindy_models(ampc_ilqr_plan* p, int n_models, 
     return 0;
   }
   if (n_models < 1 || !models) return ilqr_sindy_table_fail("NULL argument");
+  if (p->prog_slots > 0) return fail(std::string("ampc_ilqr_plan_set_sindy_models") + kProgIlqrNoTable);
   if (p->lqt_n > 0)
     return ilqr_sindy_table_fail("the plan holds a table of linear models (ampc_ilqr_plan_set_linear_models); remove it first");
   const IlqrSindyView pv = ilqr_sindy_view(h);
@@ -743,6 +805,7 @@ extern "C" int ampc_ilqr_solve_queue_var(ampc_ilqr_plan* p, int n_problems, cons
       REQUIRE(cost_index[j] >= 0 && cost_index[j] < p->h->n_costs, "ampc_ilqr_solve_queue_var: bad cost_index");
   if (int rc = check_horizons(p, n_problems, horizon, "ampc_ilqr_solve_queue_var")) return rc;
   if (int rc = check_models(p, n_problems, model_index, "ampc_ilqr_solve_queue_var")) return rc;
+  if (int rc = ilqr_program_plan_check(p, "ampc_ilqr_solve_queue_var")) return rc;
   HIP_OK(hipSetDevice(p->h->device));
   return p->h->precision == AMPC_F64
              ? ilqr_solve_queue_impl<double>(p, n_problems, x0, uguess, cost_index, horizon, model_index, max_iter, states,
@@ -758,6 +821,7 @@ extern "C" int ampc_ilqr_solve_queue(ampc_ilqr_plan* p, int n_problems, const do
   REQUIRE(p && x0, "ampc_ilqr_solve_queue: NULL argument");
   REQUIRE(n_problems >= 1, "ampc_ilqr_solve_queue: n_problems < 1");
   REQUIRE(max_iter >= 1, "ampc_ilqr_solve_queue: max_iter < 1");
+  if (int rc = ilqr_program_plan_check(p, "ampc_ilqr_solve_queue")) return rc;
   if (cost_index)
     for (int j = 0; j < n_problems; ++j)
       REQUIRE(cost_index[j] >= 0 && cost_index[j] < p->h->n_costs, "ampc_ilqr_solve_queue: bad cost_index");
@@ -922,6 +986,7 @@ extern "C" int ampc_ilqr_closed_loop_var(ampc_ilqr_plan* p, ampc_handle* surroga
                          "whose controller states are not the observation: use ampc_ilqr_closed_loop_linear");
   if (int rc = check_horizons(p, n_chains, horizon, "ampc_ilqr_closed_loop_var")) return rc;
   if (int rc = check_models(p, n_chains, model_index, "ampc_ilqr_closed_loop_var")) return rc;
+  if (int rc = ilqr_program_plan_check(p, "ampc_ilqr_closed_loop")) return rc;
   REQUIRE(n_chains >= 1 && n_steps >= 1 && max_iter >= 1, "ampc_ilqr_closed_loop: n_chains, n_steps, max_iter must be >= 1");
   ampc_handle* sur = surrogate ? surrogate : p->h;
   REQUIRE(sur->has_model() && sur->nx == p->h->nx && sur->nu == p->h->nu,
@@ -992,6 +1057,7 @@ extern "C" int ampc_ilqr_plan_set_linear_models(ampc_ilqr_plan* p, int n_models,
     return ilqr_plan_build<double>(p);               // (the kernel choices and buffers of the handle's own model)
   }
   if (n_models < 1 || !models) return ilqr_linear_table_fail("NULL argument");
+  if (p->prog_slots > 0) return fail(std::string("ampc_ilqr_plan_set_linear_models") + kProgIlqrNoTable);
   if (h->precision != AMPC_F64) return ilqr_linear_table_fail("the table kernels are f64 only; this plan's handle is f32");
   if (!(h->lin_n > 0 && h->lin_n == h->nx))
     return ilqr_linear_table_fail("the plan handle's model is not a linear model (ampc_set_linear)");

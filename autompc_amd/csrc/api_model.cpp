@@ -305,7 +305,7 @@ static void model_staged(ampc_handle* h) {
   h->has_mlp = true;
   h->has_sindy = false;
   h->has_lin = false;
-  h->has_prog = false; h->has_jvp = false;
+  h->has_prog = false; h->has_jvp = false; h->prog_ilqr = false;
   ampc_internal_jit_kick(h);   // (needs obs_dim: if the cost is set later, ampc_set_quad_costs starts it)
 }
 
@@ -480,7 +480,7 @@ static int set_linear_wide(ampc_handle* h, int nx, int nu, const double* A, cons
   std::memset(&h->md, 0, sizeof(h->md));
   std::memset(&h->mf, 0, sizeof(h->mf));
   h->md.nx = h->mf.nx = nx; h->md.nu = h->mf.nu = nu; h->md.kin = h->mf.kin = nx + nu;
-  h->has_lin = true; h->has_mlp = false; h->has_sindy = false; h->has_prog = false; h->has_jvp = false;
+  h->has_lin = true; h->has_mlp = false; h->has_sindy = false; h->has_prog = false; h->has_jvp = false; h->prog_ilqr = false;
   return 0;
 }
 
@@ -866,7 +866,7 @@ extern "C" int ampc_set_sindy(ampc_handle* h, int nx, int nu, int n_feat, const 
   h->has_sindy = true;
   h->has_mlp = false;
   h->has_lin = false;
-  h->has_prog = false; h->has_jvp = false;
+  h->has_prog = false; h->has_jvp = false; h->prog_ilqr = false;
   return 0;
 }
 

@@ -1,6 +1,6 @@
 // api_program.cpp -- analytic dynamics as a straight-line program on a handle: ampc_set_program and
-// ampc_set_program_jvp (validation on the host, staging), the batched prediction and the Jacobians of such a handle and
-// ampc_program_rollout (program_kernels.hpp).
+// ampc_set_program_jvp (validation on the host, staging), ampc_program_set_ilqr (the iLQR opt-in), the batched
+// prediction and the Jacobians of such a handle and ampc_program_rollout (program_kernels.hpp).
 //
 // A malformed program never reaches a kernel: every opcode, slot, constant index, definition-before-use and limit is
 // checked here, before anything is uploaded, and answered with a return code and an ampc_last_error() text.
@@ -84,6 +84,7 @@ extern "C" int ampc_set_program(ampc_handle* h, int nx, int nu, int n_slots, int
   h->lin_n = 0;
   h->has_prog = true;
   h->has_jvp = false;            // (a JVP staged before belongs to the previous program)
+  h->prog_ilqr = false;
   h->has_mlp = h->has_sindy = h->has_lin = false;
   return 0;
 }
@@ -95,9 +96,19 @@ extern "C" int ampc_set_program_jvp(ampc_handle* h, int n_slots, int n_instr, co
   const int nx = h->nx, nv = h->nx + h->nu;
   if (int rc = program_check("ampc_set_program_jvp", 2 * nv, 2 * nx, n_slots, n_instr, code, n_const, out_slot)) return rc;
   h->has_jvp = false;
+  h->prog_ilqr = false;
   if (int rc = program_upload(h, &h->jvp_int, &h->jvp_flt, 2 * nx, n_instr, code, n_const, consts, out_slot)) return rc;
   h->j_nslots = n_slots; h->j_ninstr = n_instr; h->j_nconst = n_const;
   h->has_jvp = true;
+  return 0;
+}
+
+extern "C" int ampc_program_set_ilqr(ampc_handle* h, int enable) {
+  REQUIRE(h, "ampc_program_set_ilqr: NULL handle");
+  REQUIRE(h->has_prog, "ampc_program_set_ilqr: the handle holds no analytic dynamics program (ampc_set_program comes first)");
+  REQUIRE(h->has_jvp, "ampc_program_set_ilqr: the handle's program has no JVP staged (ampc_set_program_jvp comes first): "
+                      "iLQR linearises its controller model");
+  h->prog_ilqr = enable != 0;
   return 0;
 }
 

@@ -143,6 +143,9 @@ struct ampc_handle {
   int j_nslots = 0, j_ninstr = 0, j_nconst = 0;
   DevBuf jvp_int, jvp_flt;        // code [n_instr][4] then out_slot [2 nx] (int); the constant pool (T)
   bool prog_diff() const { return has_prog && has_jvp; }
+  // ampc_program_set_ilqr: the opt-in that makes a program with its JVP an iLQR controller model as well (f64 plans);
+  // cleared wherever the JVP is dropped
+  bool prog_ilqr = false;
   bool has_model() const { return has_mlp || has_sindy || has_lin || has_prog; }
   int lin_n = 0;                  // > 0: the model came from ampc_set_linear with this many states
   unsigned lin_gen = 0;           // counts ampc_set_linear calls (an LQR plan notices a re-staged model)
@@ -278,7 +281,8 @@ inline size_t mppi_program_lds_bytes(const ampc_handle* h) {
 }
 
 // A program alone is a simulation model: no Jacobians and no controller plans (api_program.cpp).  With its JVP staged
-// beside it (ampc_set_program_jvp) it has Jacobians and MPPI plans; iLQR / LQR plans and the model tables still refuse.
+// beside it (ampc_set_program_jvp) it has Jacobians and MPPI plans; iLQR plans need ampc_program_set_ilqr on top of
+// that (f64 handles); LQR plans and the model tables still refuse.
 static const char* const kProgNoJacobian =
     "the handle holds an analytic dynamics program (ampc_set_program), which has no Jacobians: pred_diff is not "
     "available on it";
@@ -288,6 +292,13 @@ static const char* const kProgNoPlan =
 static const char* const kProgPlanLds =
     ": the program's value slots and hand-over rows for 64 samples ((n_slots + nx) * 64 values) and the cost block need "
     "more than the 160 KB of LDS a workgroup can have; an f32 handle halves the need";
+static const char* const kProgIlqrLds =
+    ": the program's value slots for the 16 line-search rows (n_slots * 16 values), the rows' states, controls and "
+    "next states and the line search's scratch with the cost block, or the backward sweep's matrices, need more than "
+    "the 160 KB of LDS a workgroup can have";
+static const char* const kProgIlqrNoTable =
+    ": the plan's controller model is an analytic dynamics program (ampc_program_set_ilqr); such a plan runs on that "
+    "one program and takes no per-problem models or model tables";
 int program_pred_batch(ampc_handle* h, const double* states, const double* ctrls, double* out, int n);
 
 template <typename T> static SindyDev<T> sindy_of(const ampc_handle* h) {
@@ -643,6 +654,9 @@ struct ampc_ilqr_plan {
   TileLds L{};
   int lds_work = 0, lds_xn = 0;
   size_t lds_bytes = 0;
+  int prog_slots = 0;        // a plan on a program (ampc_program_set_ilqr): the value slots the LDS map was built for
+  int prog_compact = 0;      // ... whose full scratch map is past 160 KB: compact line-search map, sweep without an LDS
+                             // copy of the cost block (ilqr_riccati_kernel<.., GCOST>)
   int last_iterations = 0;
   long long last_ls_rows = 0;   // candidate rows the line searches of the last solve rolled out (all problems)
   // optional per-kernel timing with HIP events on the launch stream (bench.py roofline leg):
@@ -727,6 +741,7 @@ template <typename T> static IlqrArgs<T> make_ilqr_args(ampc_ilqr_plan* p, int m
   std::memset(&a, 0, sizeof(a));
   a.mlp = model_of<T>(h);
   if (h->has_sindy) a.sindy = sindy_of<T>(h);
+  if (h->has_prog) { a.prog = prog_of<T>(h); a.prog_compact = p->prog_compact; }
   if (h->has_lin) { a.lin = lin_of<T>(h); a.vj = (T*)p->vj.p; }
   if (p->lqt_n > 0) a.vj = (T*)p->vj.p;        // (a table of linear models: the sweep's scratch, whatever the handle's form)
   a.lds_xn = p->lds_xn;
@@ -809,6 +824,27 @@ template <typename T> int surrogate_step(ampc_handle* h, ampc_handle* sur, const
                                          void* x_next, int B);
 // Workgroups (slots) a per-slot launch of the running iteration needs: with the slots that have work listed first
 // (compact_on) and an upper bound of their number known from the polls, the grid ends there.
+// A plan built on a program reads the handle's program and JVP at every launch: what the handle holds NOW must still be
+// what the plan's buffers and LDS map were built for.  0, or the refusal.
+inline int ilqr_program_plan_check(const ampc_ilqr_plan* p, const char* who) {
+  const ampc_handle* h = p->h;
+  const std::string w(who);
+  if (p->prog_slots == 0) {
+    REQUIRE(!h->has_prog, w + ": the plan was built before its handle held an analytic dynamics program; create a new plan");
+    return 0;
+  }
+  REQUIRE(h->has_prog, w + ": the plan was built on an analytic dynamics program and its handle holds another model now");
+  REQUIRE(h->has_jvp && h->prog_ilqr,
+          w + ": the plan was built on an analytic dynamics program with its JVP and ampc_program_set_ilqr; the handle's "
+              "program was staged again since (ampc_set_program drops the JVP, both drop the iLQR flag): stage the JVP "
+              "and call ampc_program_set_ilqr again");
+  REQUIRE(h->nx + h->nu + 1 == p->L.xu_stride && p->lds_xn == round_up(16 * p->L.xu_stride, 4),
+          w + ": the program staged on the plan's handle has other dimensions than the one the plan was built for");
+  REQUIRE(h->p_nslots <= p->prog_slots,
+          w + ": the program staged on the plan's handle has " + std::to_string(h->p_nslots) + " value slots, the plan's "
+              "LDS map was built for " + std::to_string(p->prog_slots) + "; create a new plan");
+  return 0;
+}
 inline int ilqr_grid_slots(const ampc_ilqr_plan* p) {
   return (p->compact_on && p->active_hint > 0 && p->active_hint < p->B) ? p->active_hint : p->B;
 }

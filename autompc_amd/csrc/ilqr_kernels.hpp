@@ -28,6 +28,7 @@
 #include "mlp_tile.hpp"
 #include "sindy_kernels.hpp"
 #include "linear_kernels.hpp"
+#include "program_kernels.hpp"
 
 namespace ampc {
 
@@ -40,7 +41,11 @@ constexpr int kRicStride = 4 + kIlqrMaxLs;   // per problem: sweep sums [4], can
 template <typename T> struct IlqrArgs {
   MlpDev<T> mlp;
   SindyDev<T> sindy;             // used instead of the MLP tile when the kernel is built with DYN = 1
-  int lds_xn;                    // SINDy: [16][nx] next-state scratch (elements)
+  ProgDev<T> prog;               // ... an analytic dynamics program, DYN = 3 (program_kernels.hpp; f64 plans only)
+  int prog_compact;              // DYN = 3, plans whose full scratch map is past 160 KB (more than ~50 states): the line
+                                 // search on the compact map, the sweep with the cost block left in global memory
+  int lds_xn;                    // SINDy / program: [16][nx] next-state scratch (elements); behind it the SINDy table
+                                 // scratch, or the program's value slots [n_slots][16], one column per candidate row
   TileLds lds;
   int lds_work;                  // start of the Riccati / line-search scratch (elements)
   int H, obs_dim, cost_stride, bounded, ls_n, mode;   // mode 0: initial rollout, 1: iteration
@@ -224,7 +229,10 @@ template <typename T> __device__ __forceinline__ int ilqr_slot(const IlqrArgs<T>
   return args.slot_of ? __builtin_amdgcn_readfirstlane(args.slot_of[b]) : b;
 }
 
-template <typename T, bool WIDE = false, typename SH = DynShape>   // WIDE: model states above 32 (longer register staging)
+// GCOST: the slot's cost block is read where it lies in global memory instead of from a copy in LDS (the same values:
+// the same results bit for bit), and the scratch map has no room for it -- what lets the sweep of a plan of more than
+// ~55 states, whose dense blocks of no x no values no longer fit beside V, J, VJ and Qt, run at all (program plans).
+template <typename T, bool WIDE = false, typename SH = DynShape, bool GCOST = false>   // WIDE: model states above 32 (longer register staging)
 __global__ __launch_bounds__(kRicThreads) void ilqr_riccati_kernel(const IlqrArgs<T> args) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   T* Wr = reinterpret_cast<T*>(smem_raw);
@@ -235,16 +243,18 @@ __global__ __launch_bounds__(kRicThreads) void ilqr_riccati_kernel(const IlqrArg
   const int HS = args.H, H = args.slot_h ? args.slot_h[p] : HS;      // array stride, this slot's horizon
   if (args.active[p] == 0) return;
   const int cost_stride = SH::kStatic ? cost_block_stride(SH::no, SH::nu) : args.cost_stride;
-  const IlqrWork wk = make_ilqr_work(nx, nu, cost_stride);
+  const IlqrWork wk = make_ilqr_work(nx, nu, GCOST ? 0 : cost_stride);
   T* V = Wr + wk.V; T* v = Wr + wk.v; T* Jm = Wr + wk.J; T* VJ = Wr + wk.VJ;
   T* Qt = Wr + wk.Qt; T* qt = Wr + wk.qt; T* Km = Wr + wk.K; T* kv = Wr + wk.k;
   T* Wk = Wr + wk.Wk; T* wq = Wr + wk.wq;
-  T* xbar = Wr + wk.xbar; T* ubar = Wr + wk.ubar; T* cpar = Wr + wk.cpar; T* scal = Wr + wk.scal;
+  T* xbar = Wr + wk.xbar; T* ubar = Wr + wk.ubar; T* scal = Wr + wk.scal;
+  const T* cglob = args.costs_par + (size_t)args.cost_idx[p] * cost_stride;
+  const T* cpar = GCOST ? cglob : Wr + wk.cpar;
   const T* Qm = cpar; const T* Rm = Qm + no * no; const T* Fm = Rm + nu * nu;
   const T* goal = Fm + no * no;
   const T* clin = goal + no; const T* clint = clin + no;     // affine part of the stage / terminal cost
-  for (int i = tid; i < cost_stride; i += NTHR)
-    cpar[i] = args.costs_par[(size_t)args.cost_idx[p] * cost_stride + i];
+  if constexpr (!GCOST)
+    for (int i = tid; i < cost_stride; i += NTHR) Wr[wk.cpar + i] = cglob[i];
   __syncthreads();
   const T* st = args.states + (size_t)p * (HS + 1) * nx;
   const T* ct = args.ctrls + (size_t)p * HS * nu;
@@ -859,7 +869,9 @@ __global__ __launch_bounds__(kRicThreads) AMPC_PROBE_RIC_OCC void ilqr_riccati_m
 
 // DYN = 0: MLP dynamics through the MFMA tile;  DYN = 1: SINDy feature-library dynamics, one
 // thread per line-search candidate (the model is tiny; see sindy_kernels.hpp);  DYN = 2: wide linear
-// models (65..128 states), the K-tiled step of linear_kernels.hpp on the 16 candidate rows.
+// models (65..128 states), the K-tiled step of linear_kernels.hpp on the 16 candidate rows;  DYN = 3: an analytic
+// dynamics program (program_kernels.hpp), interpreted by the first helper lane of every candidate row on that row's
+// column of the [n_slots][16] slot area.
 template <typename T, int NT, int W, int DYN = 0, typename SH = DynShape, bool WIDE = false>
 __global__ __launch_bounds__(64 * W) void ilqr_iter_kernel(const IlqrArgs<T> args) {
   const int mode = args.slot_mode ? args.slot_mode[ilqr_slot(args)] : args.mode;   // (queue: per slot)
@@ -877,7 +889,7 @@ __global__ __launch_bounds__(64 * W) void ilqr_iter_kernel(const IlqrArgs<T> arg
   const int HS = args.H, H = args.slot_h ? args.slot_h[p] : HS;      // array stride, this slot's horizon
   const int xs_ = L.xu_stride;
   const int cost_stride = SH::kStatic ? cost_block_stride(SH::no, SH::nu) : args.cost_stride;
-  const IlqrWork wk = make_ilqr_work(nx, nu, cost_stride, DYN == 2);
+  const IlqrWork wk = make_ilqr_work(nx, nu, cost_stride, DYN == 2 || (DYN == 3 && args.prog_compact != 0));
   T* Wr = lds + (SH::kStatic ? L.extra : args.lds_work);
   T* V = Wr + wk.V; T* v = Wr + wk.v; T* Jm = Wr + wk.J; T* VJ = Wr + wk.VJ;
   T* Qt = Wr + wk.Qt; T* qt = Wr + wk.qt; T* Km = Wr + wk.K; T* kv = Wr + wk.k;
@@ -942,7 +954,7 @@ __global__ __launch_bounds__(64 * W) void ilqr_iter_kernel(const IlqrArgs<T> arg
   // barriers inside the loop are LDS-only, so neither these loads nor the line-search stores
   // (lss / lsc) stall a step.
   // nu <= 16; nx <= 32 with the MLP tile, <= 64 on the feature-library path (predicated on nu * nx)
-  constexpr int KR = (16 * (DYN == 2 ? kLinMaxIlqrNx : (DYN == 1 || WIDE) ? 64 : 32) + NTHR - 1) / NTHR;
+  constexpr int KR = (16 * (DYN == 2 ? kLinMaxIlqrNx : (DYN == 1 || DYN == 3 || WIDE) ? 64 : 32) + NTHR - 1) / NTHR;
   T kreg[KR];
   T kvr = T(0), ubr = T(0), xbr = T(0);
   auto fetch_ls = [&](int t) {
@@ -1025,6 +1037,24 @@ __global__ __launch_bounds__(64 * W) void ilqr_iter_kernel(const IlqrArgs<T> arg
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr)
           if (col < nx) xnext[acc_row<T>(lane >> 4, rr) * nx + col] = acc[rr];
+      }
+      __syncthreads();
+      for (int a = r; a < nx; a += TPS) {
+        const T xn = xnext[m * nx + a];
+        xu[m * xs_ + a] = xn;
+        if (mode == 0 && m == 0) st[(size_t)(t + 1) * nx + a] = xn;
+      }
+    } else if constexpr (DYN == 3) {
+      // The row's [x | u] into its column of the slot area, the program on that column, the outputs through xnext: the
+      // slot allocator reuses input slots, so an output may sit where an input was (program_rollout_kernel's hand-over).
+      // code, consts and out_slot are indexed by wave-uniform values only; results leave through vector stores.
+      T* xnext = lds + args.lds_xn;
+      T* slots = xnext + M * nx + m;
+      for (int a = r; a < n; a += TPS) slots[a * M] = xu[m * xs_ + a];
+      lds_barrier();
+      if (r == 0) {
+        program_run<T, M>(args.prog, slots);
+        for (int i = 0; i < nx; ++i) xnext[m * nx + i] = slots[args.prog.out_slot[i] * M];
       }
       __syncthreads();
       for (int a = r; a < nx; a += TPS) {

@@ -64,10 +64,25 @@ template <typename T> int ilqr_launch_iter(ampc_ilqr_plan* p, int mode) {
     case NUV: { auto rk = ilqr_riccati_mfma_kernel<T, NUV, SHT>; HIP_OK(allow_lds(rk, mb));          \
       hipLaunchKernelGGL(rk, dim3(Bg), dim3(kRicThreads), mb, h->stream, a); done = true; break; }
     bool done = false;
+#ifndef AMPC_JIT_PLUGIN
+    if (p->prog_compact) {   // a wide program plan: the general sweep, its cost block read from global memory
+      const size_t gb = (size_t)make_ilqr_work(h->nx, h->nu, 0).total * sizeof(T);
+      if (h->nx > 32) {
+        auto rk = ilqr_riccati_kernel<T, true, DynShape, true>;
+        HIP_OK(allow_lds(rk, gb));
+        hipLaunchKernelGGL(rk, dim3(Bg), dim3(kRicThreads), gb, h->stream, a);
+      } else {
+        auto rk = ilqr_riccati_kernel<T, false, DynShape, true>;
+        HIP_OK(allow_lds(rk, gb));
+        hipLaunchKernelGGL(rk, dim3(Bg), dim3(kRicThreads), gb, h->stream, a);
+      }
+      done = true;
+    }
+#endif
     // (the control dimensions the latency-optimised sweep is validated for; a shape-specialised
     //  build takes the same decision as the run-time-shape one, so both give identical results)
     const bool nu_ok = h->nu == 1 || h->nu == 2 || h->nu == 3 || h->nu == 4 || h->nu == 6 || h->nu == 8;
-    if (mfma_sweep && h->nx <= 32 && nu_ok) {
+    if (!done && mfma_sweep && h->nx <= 32 && nu_ok) {
       if (p->static_shape >= 0) {
 #define AMPC_SD_BODY { auto rk = ilqr_riccati_mfma_kernel<T, SH::nu, SH>; HIP_OK(allow_lds(rk, mb));   \
         hipLaunchKernelGGL(rk, dim3(Bg), dim3(kRicThreads), mb, h->stream, a); done = true; }
@@ -127,6 +142,20 @@ template <typename T> int ilqr_launch_iter(ampc_ilqr_plan* p, int mode) {
       return 0;
     }
     return fail("internal: a table of SINDy models on an f32 iLQR plan");
+  }
+  // an analytic dynamics program (ampc_program_set_ilqr): the sixteen-row kernel with the interpreter as its step, the
+  // handle's program as it is NOW (ilqr_program_plan_check: still what the plan's LDS map was built for)
+  if (h->has_prog || p->prog_slots > 0) {
+    if (int rc = ilqr_program_plan_check(p, "iLQR plan")) return rc;
+    if constexpr (sizeof(T) == 8) {
+      auto k = ilqr_iter_kernel<T, 1, 4, 3>;
+      HIP_OK(allow_lds(k, p->lds_bytes));
+      hipLaunchKernelGGL(k, dim3(Bg), dim3(256), p->lds_bytes, h->stream, a);
+      HIP_OK(hipGetLastError());
+      if (e) HIP_OK(hipEventRecord(e[2], h->stream));
+      return 0;
+    }
+    return fail("internal: an analytic dynamics program on an f32 iLQR plan");
   }
   if (h->has_sindy) {
     auto k = ilqr_iter_kernel<T, 1, 4, 1>;

@@ -102,6 +102,18 @@ template <typename T> int ilqr_refresh_jacobians(ampc_ilqr_plan* p) {
     if (p->ev_cur) { HIP_OK(hipEventRecord(p->ev_cur[3], h->stream)); HIP_OK(hipEventRecord(p->ev_cur[4], h->stream)); }
     return 0;
   }
+  if (h->has_prog || p->prog_slots > 0) {   // an analytic dynamics program: its JVP, one lane per (plan row, direction)
+    if (int rc = ilqr_program_plan_check(p, "iLQR plan")) return rc;
+    const size_t lb = (size_t)h->j_nslots * kProgLanes * sizeof(T);        // at most 256 * 64 * 8 = 128 KB
+    const long long lanes = (long long)rows * (nx + nu);
+    HIP_OK(allow_lds(ilqr_program_jacobian_kernel<T>, lb));
+    hipLaunchKernelGGL(ilqr_program_jacobian_kernel<T>, dim3((unsigned)((lanes + kProgLanes - 1) / kProgLanes)),
+                       dim3(kProgLanes), lb, h->stream, jvp_of<T>(h), (const T*)p->states.p, (const T*)p->ctrls.p,
+                       (T*)p->jx.p, (T*)p->ju.p, rows, rm);
+    HIP_OK(hipGetLastError());
+    if (p->ev_cur) { HIP_OK(hipEventRecord(p->ev_cur[3], h->stream)); HIP_OK(hipEventRecord(p->ev_cur[4], h->stream)); }
+    return 0;
+  }
   if (h->has_sindy) {
     hipLaunchKernelGGL(sindy_jacobian_kernel<T>, dim3((rows + 63) / 64), dim3(64), 0, h->stream,
                        sindy_of<T>(h), (const T*)p->states.p, (const T*)p->ctrls.p, (T*)p->jx.p,

@@ -22,9 +22,13 @@
 //
 // Jacobians: a handle may hold, beside its program, the program's JVP (ampc_set_program_jvp; derived on the host,
 // sysid/program.py): 2 (nx + nu) inputs [x | u | dx | du], 2 nx outputs [f | J . (dx, du)], the same instruction set,
-// run by the same interpreter.  program_jacobian_kernel gives every (row, unit direction) pair a lane.
+// run by the same interpreter.  program_jacobian_kernel gives every (row, unit direction) pair a lane;
+// ilqr_program_jacobian_kernel does the same for the rows of an iLQR plan's nominal trajectories (one shared body:
+// program_jacobian_lane).  The interpreter takes the column stride as a template parameter: 64 here, 16 where the
+// iLQR line search keeps one column per candidate row (ilqr_kernels.hpp, DYN = 3).
 #pragma once
 #include <hip/hip_runtime.h>
+#include "mlp_kernels.hpp"             // RowMap: the rows of an iLQR plan
 
 namespace ampc {
 
@@ -59,11 +63,10 @@ __device__ __forceinline__ float prog_sqrt(float x) { return sqrtf(x); }
 __device__ __forceinline__ double prog_abs(double x) { return fabs(x); }
 __device__ __forceinline__ float prog_abs(float x) { return fabsf(x); }
 
-// The interpreter: v points at the lane's column of the [slot][kProgLanes] array.  Straight line, no barrier: a lane
+// The interpreter: v points at the lane's column of the [slot][S] array.  Straight line, no barrier: a lane
 // touches its own column only.
-template <typename T> __device__ __forceinline__ void program_run(const ProgDev<T>& p, T* v) {
+template <typename T, int S = kProgLanes> __device__ __forceinline__ void program_run(const ProgDev<T>& p, T* v) {
 #pragma clang fp contract(off)
-  constexpr int S = kProgLanes;
   for (int i = 0; i < p.n_instr; ++i) {
     const int4 w = p.code[i];
     T r;
@@ -141,35 +144,68 @@ __global__ __launch_bounds__(kProgLanes) void program_rollout_kernel(const ProgD
   }
 }
 
+// One (row, unit direction j) pair of the JVP program q on the lane's column v: [x | u] of the row into slots
+// 0 .. nv-1 (nv = nx + nu), the unit seed e_j into slots nv .. 2nv-1, q, then column j of the row's Jacobian --
+// Jx[i][j] for j < nx, Ju[i][j - nx] otherwise; with `out`, the j == 0 lane also writes the value outputs.  The
+// values are recomputed per direction: one interpreter, one rounding contract, for every kernel that calls this.
+template <typename T>
+__device__ __forceinline__ void program_jacobian_lane(const ProgDev<T>& q, T* v, const T* __restrict__ x,
+                                                      const T* __restrict__ u, int j, T* __restrict__ out,
+                                                      T* __restrict__ Jx, T* __restrict__ Ju, int nx, int nu) {
+  constexpr int S = kProgLanes;
+  const int nv = nx + nu;
+  for (int i = 0; i < nx; ++i) v[i * S] = x[i];
+  for (int i = 0; i < nu; ++i) v[(nx + i) * S] = u[i];
+  for (int i = 0; i < nv; ++i) v[(nv + i) * S] = i == j ? (T)1 : (T)0;
+  program_run<T>(q, v);
+  if (out != nullptr && j == 0)
+    for (int i = 0; i < nx; ++i) out[i] = v[q.out_slot[i] * S];
+  if (j < nx) {
+    for (int i = 0; i < nx; ++i) Jx[i * nx + j] = v[q.out_slot[nx + i] * S];
+  } else {
+    for (int i = 0; i < nx; ++i) Ju[i * nu + (j - nx)] = v[q.out_slot[nx + i] * S];
+  }
+}
+
 // (next, jx, ju) of B rows from the JVP program q (header comment): lane l of the launch is row l / nv, direction
-// l % nv (nv = nx + nu).  It loads [x | u] of its row into slots 0 .. nv-1 and the unit seed e_j into slots
-// nv .. 2nv-1, runs q and writes column j of the row's Jacobian -- jx[r][i][j] for j < nx, ju[r][i][j - nx] otherwise;
-// the j == 0 lane also writes out[r][i] from the value outputs.  The values are recomputed per direction: one
-// interpreter, one rounding contract.  Lanes at or past B * nv return before touching memory.
+// l % nv (program_jacobian_lane).  Lanes at or past B * nv return before touching memory.
 template <typename T>
 __global__ __launch_bounds__(kProgLanes) void program_jacobian_kernel(const ProgDev<T> q, const T* __restrict__ x,
                                                                       const T* __restrict__ u, T* __restrict__ out,
                                                                       T* __restrict__ jx, T* __restrict__ ju, int B,
                                                                       int nx, int nu) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  constexpr int S = kProgLanes;
   T* v = reinterpret_cast<T*>(smem_raw) + threadIdx.x;
   const int nv = nx + nu;
-  const long long l = (long long)blockIdx.x * S + threadIdx.x;
+  const long long l = (long long)blockIdx.x * kProgLanes + threadIdx.x;
   if (l >= (long long)B * nv) return;
   const long long r = l / nv;
-  const int j = (int)(l - r * nv);
-  for (int i = 0; i < nx; ++i) v[i * S] = x[r * nx + i];
-  for (int i = 0; i < nu; ++i) v[(nx + i) * S] = u[r * nu + i];
-  for (int i = 0; i < nv; ++i) v[(nv + i) * S] = i == j ? (T)1 : (T)0;
-  program_run<T>(q, v);
-  if (j == 0)
-    for (int i = 0; i < nx; ++i) out[r * nx + i] = v[q.out_slot[i] * S];
-  if (j < nx) {
-    for (int i = 0; i < nx; ++i) jx[(r * nx + i) * nx + j] = v[q.out_slot[nx + i] * S];
-  } else {
-    for (int i = 0; i < nx; ++i) ju[(r * nx + i) * nu + (j - nx)] = v[q.out_slot[nx + i] * S];
-  }
+  program_jacobian_lane<T>(q, v, x + r * nx, u + r * nu, (int)(l - r * nv), out + r * nx, jx + r * nx * nx,
+                           ju + r * nx * nu, nx, nu);
+}
+
+// The Jacobian refresh of an iLQR plan on a program (launch_mlp.cpp): lane l is (plan row l / nv, direction l % nv),
+// n plan rows in all.  A row is read and written through the plan's RowMap as the other refresh kernels do: slot
+// rm.group(r), step rm.step(r), states [slot][H + 1][nx], ctrls [slot][H][nu], output row rm.out_row(r) of jx / ju.
+// Rows of slots that did not ask for a refresh, rows past a slot's horizon and lanes past n * nv neither read nor write.
+template <typename T>
+__global__ __launch_bounds__(kProgLanes) void ilqr_program_jacobian_kernel(const ProgDev<T> q,
+                                                                           const T* __restrict__ states,
+                                                                           const T* __restrict__ ctrls,
+                                                                           T* __restrict__ jx, T* __restrict__ ju,
+                                                                           int n, const RowMap rm) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  T* v = reinterpret_cast<T*>(smem_raw) + threadIdx.x;
+  const int nx = q.nx, nu = q.nu, nv = nx + nu;
+  const long long l = (long long)blockIdx.x * kProgLanes + threadIdx.x;
+  if (l >= (long long)n * nv) return;
+  const int r = (int)(l / nv);
+  if (!rm.live(r)) return;
+  const T* x = states + (size_t)rm.group(r) * rm.s_stride + (size_t)rm.step(r) * nx;
+  const T* u = ctrls + (size_t)rm.group(r) * rm.c_stride + (size_t)rm.step(r) * nu;
+  const size_t o = (size_t)rm.out_row(r);
+  program_jacobian_lane<T>(q, v, x, u, (int)(l - (long long)r * nv), (T*)nullptr, jx + o * nx * nx, ju + o * nx * nu,
+                           nx, nu);
 }
 
 }  // namespace ampc

@@ -53,7 +53,9 @@ and ``np.sign``); both are exact, so the rounding contract covers JVP programs u
 A ``DifferentiableProgram`` has ``pred_diff`` / ``pred_diff_batch`` (host: the JVP program once per unit direction;
 device: one lane per (row, direction), csrc/program_kernels.hpp), ``stage_into`` stages the program and then its JVP,
 and a handle with both is an MPPI controller model (csrc/mppi_program_kernels.hpp).  A JVP beyond ``MAX_SLOTS`` /
-``MAX_INSTR`` raises ``ValueError`` at construction.
+``MAX_INSTR`` raises ``ValueError`` at construction.  ``DifferentiableProgram(..., ilqr=True)`` /
+``prog.differentiable(ilqr=True)`` / ``trace`` / ``from_code`` with ``ilqr=True`` additionally make it an iLQR
+controller model (``stage_into`` sets the handle's flag after the JVP; f64, csrc/ilqr_kernels.hpp DYN = 3).
 """
 import heapq
 import numbers
@@ -369,19 +371,21 @@ class DynamicsProgram(Model):
 
     # -- construction -------------------------------------------------------------------------------------------
     @classmethod
-    def from_code(cls, system, code, consts, out_slot, n_slots=None, device=0):
-        """From the raw arrays (module docstring); n_slots defaults to the highest slot named + 1."""
+    def from_code(cls, system, code, consts, out_slot, n_slots=None, device=0, **kw):
+        """From the raw arrays (module docstring); n_slots defaults to the highest slot named + 1.  Further keywords
+        go to the class (DifferentiableProgram: ilqr=)."""
         code = np.asarray(code, dtype=np.int32).reshape(-1, 4)
         if n_slots is None:
             named = [system.obs_dim + system.ctrl_dim - 1] + [int(s) for s in np.asarray(out_slot).reshape(-1)]
             for op, d, a, b in code.tolist():
                 named += [d] + ([a] if op != OP_CONST else []) + ([b] if op in _BINARY else [])
             n_slots = max(named) + 1
-        return cls(system, code, consts, out_slot, n_slots, device=device)
+        return cls(system, code, consts, out_slot, n_slots, device=device, **kw)
 
     @classmethod
-    def trace(cls, system, fn, device=0):
-        """Record ``fn(obs, ctrl)``: called once, with object arrays of traced values of the system's dimensions."""
+    def trace(cls, system, fn, device=0, **kw):
+        """Record ``fn(obs, ctrl)``: called once, with object arrays of traced values of the system's dimensions.
+        Further keywords go to the class (DifferentiableProgram: ilqr=)."""
         nx, nu = system.obs_dim, system.ctrl_dim
         tape = _Tape(nx + nu)
         obs = np.empty(nx, dtype=object)
@@ -398,7 +402,7 @@ class DynamicsProgram(Model):
             raise ValueError("the dynamics returned %d values for %d observations" % (len(res), nx))
         outputs = [tape.sym(r, "the result").vid for r in res]
         code, out_slot, n_slots = _allocate(nx + nu, tape.instr, outputs)
-        return cls(system, code, tape.consts, out_slot, max(n_slots, nx + nu), device=device)
+        return cls(system, code, tape.consts, out_slot, max(n_slots, nx + nu), device=device, **kw)
 
     # -- Model surface --------------------------------------------------------------------------------------------
     @property
@@ -464,10 +468,11 @@ class DynamicsProgram(Model):
         state["_handles"] = {}
         return state
 
-    def differentiable(self):
-        """The same arrays as a DifferentiableProgram: Jacobians, and an MPPI controller model."""
+    def differentiable(self, ilqr=False):
+        """The same arrays as a DifferentiableProgram: Jacobians, and an MPPI controller model; ilqr=True: an iLQR
+        controller model as well (DifferentiableProgram.ilqr_plans)."""
         return DifferentiableProgram(self.system, self.code, self.consts, self.out_slot, self.n_slots,
-                                     device=self.device)
+                                     device=self.device, ilqr=ilqr)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -585,10 +590,17 @@ def derive_jvp(nx, nu, code, consts, out_slot):
 
 class DifferentiableProgram(DynamicsProgram):
     """A DynamicsProgram with exact Jacobians: its JVP program (`jvp`: code, consts, out_slot, n_slots) is derived at
-    construction and staged beside the program, which also makes the handle an MPPI controller model."""
+    construction and staged beside the program, which also makes the handle an MPPI controller model.
 
-    def __init__(self, system, code, consts, out_slot, n_slots, device=0):
+    ilqr=True (attribute ``ilqr_plans``) is the opt-in for iLQR plans: ``stage_into`` then calls
+    ``handle.set_program_ilqr()`` after the JVP, and ``IterativeLQR(system, task, prog, H)``,
+    ``IlqrCandidateEvaluator(system, task, prog, surrogate=...)`` and a tuner's ``truedyn_evaluator`` take the program as
+    their controller model: the perfect-model iLQR controller (f64).  Without it they are refused in the library, as a
+    plain program is."""
+
+    def __init__(self, system, code, consts, out_slot, n_slots, device=0, ilqr=False):
         super().__init__(system, code, consts, out_slot, n_slots, device=device)
+        self.ilqr_plans = bool(ilqr)
         nx, nu = system.obs_dim, system.ctrl_dim
         self.jvp = derive_jvp(nx, nu, self.code, self.consts, self.out_slot)
         if self.jvp.n_slots > MAX_SLOTS or self.jvp.code.shape[0] > MAX_INSTR:
@@ -598,7 +610,11 @@ class DifferentiableProgram(DynamicsProgram):
                                                            self.code.shape[0], MAX_SLOTS, MAX_INSTR))
         validate(nx, nu, self.jvp.n_slots, self.jvp.code, self.jvp.consts.shape[0], self.jvp.out_slot, jvp=True)
 
-    def differentiable(self):
+    def differentiable(self, ilqr=False):
+        """This program; with ilqr=True and the flag not set yet, a copy of it that has it."""
+        if ilqr and not self.ilqr_plans:
+            return DifferentiableProgram(self.system, self.code, self.consts, self.out_slot, self.n_slots,
+                                         device=self.device, ilqr=True)
         return self
 
     def evaluate_jvp(self, states, ctrls, dtype=np.float64):
@@ -632,3 +648,5 @@ class DifferentiableProgram(DynamicsProgram):
     def stage_into(self, handle):
         super().stage_into(handle)
         handle.set_program_jvp(self.jvp.n_slots, self.jvp.code, self.jvp.consts, self.jvp.out_slot)
+        if getattr(self, "ilqr_plans", False):
+            handle.set_program_ilqr(True)

@@ -49,7 +49,7 @@ int ampc_version(void);   /* 100 * major + minor; 104: + ampc_mppi_run_legacy; 1
                            *      + ampc_ilqr_plan_set_sindy_models, + ampc_mppi_plan_set_linear_models, + ampc_mppi_closed_loop_linear,
                            *      + ampc_ilqr_plan_set_linear_models, + ampc_ilqr_closed_loop_linear, + ampc_ilqr_linear_table_layout,
                            *      + ampc_lqr_gains_ex, + ampc_lqr_plan_set_loop_ex, + ampc_set_program, + ampc_program_rollout,
-                           *      + ampc_set_program_jvp, + ampc_program_pred_diff_batch
+                           *      + ampc_set_program_jvp, + ampc_program_pred_diff_batch, + ampc_program_set_ilqr, + ampc_ilqr_plan_jacobians
                            *      (no bump: callers detect them by their symbols) */
 int ampc_device_count(void);
 
@@ -204,8 +204,9 @@ int ampc_program_rollout(ampc_handle* h, int n, int n_steps, const double* x0, c
  *   - is an MPPI controller model: ampc_mppi_plan_create accepts it (csrc/mppi_program_kernels.hpp: one sample per
  *     lane; (n_slots + nx) * 64 values and the cost block must fit the 160 KB of LDS, refused otherwise), and
  *     ampc_mppi_solve / _run / _run_legacy / _closed_loop[_scored] work as for any plan, the program's state being the
- *     observation.  ampc_mppi_plan_set_models, the three model tables, ampc_mppi_plan_set_state_lift,
- *     ampc_ilqr_plan_create and ampc_lqr_plan_set_models refuse a program with or without a JVP. */
+ *     observation.  ampc_mppi_plan_set_models, the three model tables, ampc_mppi_plan_set_state_lift and
+ *     ampc_lqr_plan_set_models refuse a program with or without a JVP; ampc_ilqr_plan_create refuses it until
+ *     ampc_program_set_ilqr (below) has been called on the handle. */
 int ampc_set_program_jvp(ampc_handle* h, int n_slots, int n_instr, const int* code, int n_const, const double* consts,
                          const int* out_slot);
 /* out[n][nx], jx[n][nx][nx], ju[n][nx][nu] of n rows from the staged JVP: one lane per (row, input direction), the
@@ -213,6 +214,20 @@ int ampc_set_program_jvp(ampc_handle* h, int n_slots, int n_instr, const int* co
  * exactly rounded operations equals its host evaluation bit for bit.  f64 and f32 handles. */
 int ampc_program_pred_diff_batch(ampc_handle* h, const double* states, const double* ctrls, double* out, double* jx,
                                  double* ju, int n);
+/* The opt-in that makes a program with its JVP an iLQR controller model: the perfect-model iLQR plan.  Needs a handle
+ * that holds a program AND a staged JVP (a return code and an ampc_last_error() text naming what is missing otherwise);
+ * enable != 0 sets the flag, 0 clears it.  ampc_set_program, ampc_set_program_jvp and every other ampc_set_* model call
+ * clear it, where they drop the JVP.  With the flag set ampc_ilqr_plan_create accepts the handle if it is f64 (an f32
+ * program handle is refused), nx + nu <= 63, the cost blocks are on nx observations and have no indicator terms, and
+ * the line search fits the 160 KB of LDS: [16][nx + nu + 1] rows, [16][nx] next states, the forward program's
+ * [n_slots][16] value slots and the Riccati / cost workspace.  The line search (csrc/ilqr_kernels.hpp, DYN = 3) runs
+ * the interpreter on one column per candidate row, the Jacobian refresh (csrc/program_kernels.hpp) the JVP on one lane
+ * per (plan row, input direction); ampc_ilqr_solve, _solve_queue[_var] with per-problem horizons and
+ * ampc_ilqr_closed_loop[_var] against any surrogate work as on a SINDy plan, the program's state being the observation.
+ * Every launch reads the program and the JVP the handle holds THEN: a solve refuses a handle whose JVP or flag was
+ * dropped, or whose program has more value slots than the plan was built for.  ampc_ilqr_plan_set_models, the three
+ * model tables and model_index are refused on such a plan. */
+int ampc_program_set_ilqr(ampc_handle* h, int enable);
 
 /* ---- cost / bounds ------------------------------------------------------------------------
  * Replaces QuadCost (quad_cost.py:7-51) as read through Cost.eval_* (cost.py:66-213).
@@ -466,6 +481,11 @@ int ampc_ilqr_plan_timing(ampc_ilqr_plan* p, double* kernel_ms, int* iterations)
  * needs a third four-row pass -- all of them in one pass of a twelve-row tile (ls_max_iter rows per
  * iteration; same results again, csrc/ilqr_lsw.hpp).  Either pointer may be NULL. */
 int ampc_ilqr_plan_stats(ampc_ilqr_plan* p, long long* iterations, long long* candidate_rows);
+/* The plan's per-row Jacobians of its handle's model, as the last refresh left them: jx[B * horizon][nx][nx],
+ * ju[B * horizon][nx][nu], row b * horizon + t for step t of slot b.  write == 0 copies them out, write != 0 copies
+ * the caller's arrays in (a test's way to see which rows a refresh leaves alone).  Synchronises the plan's stream.
+ * Refused on plans that keep no such rows: wide linear models and plans with a model table. */
+int ampc_ilqr_plan_jacobians(ampc_ilqr_plan* p, double* jx, double* ju, int write);
 /* use_goal = 0 (default): the backward sweep is seeded with the terminal gradient exactly as the
  * reference computes it, (F + F') x_N -- Cost.eval_term_obs_cost_diff ignores the goal
  * (cost.py:195, 208-211).  use_goal != 0: (F + F') (x_N - goal), the derivative of the terminal
