@@ -166,6 +166,8 @@ SIGNATURES = {
     "ampc_mlpfit_run_epoch": (c_int, [c_void_p, c_void_p]),
     "ampc_mlpfit_steps": (c_int, [c_void_p, POINTER(ctypes.c_longlong)]),
     "ampc_mlpfit_destroy": (c_int, [c_void_p]),
+    "ampc_bo_propose": (c_int, [c_int, c_int, c_int, _dp, _dp, c_int, _dp, _dp, c_int, _dp, c_int, _dp, _ip, _ip, _ip,
+                                _dp, _dp, _dp, _dp]),
 }
 
 
@@ -1480,6 +1482,34 @@ def lasso_fit(traj_len, obs, ctrls, bases, configs, tie=None, ratio_tie=None, de
                              float(RATIO_TIE if ratio_tie is None else ratio_tie), dptr(coeffs), iptr(status),
                              dptr(margin), iptr(sweeps)))
     return [coeffs[off[i]:off[i + 1]].reshape(shapes[i]) for i in range(C)], status, margin, sweeps
+
+
+def bo_propose(X, z, hyper_w, hyper_noise, pool, q, device=0):
+    """ampc_bo_propose: one Bayesian-optimisation proposal (``tuning/proposer.py`` states the algorithm): a Matern-5/2
+    GP fitted to X [n][d], z [n] for every row (hyper_w [G][d], hyper_noise [G]) of the hyperparameter table, the
+    posterior of the row of largest log marginal likelihood over pool [m][d] and q greedy expected-improvement picks
+    with the believer update.  Returns a dict: lml [G], status [G] (1: the row was declined), chosen (-1: every row
+    declined; the picks are -1 and the other values NaN then), picks [q], pick_ei [q], pick_margin [q], mu [m],
+    var [m] (the posterior before the first pick).  Sizes over the limits are refused (AmpcError)."""
+    lib = load()
+    X, pool, hw = as_f64(X), as_f64(pool), as_f64(hyper_w)
+    z, hn = as_f64(z).ravel(), as_f64(hyper_noise).ravel()
+    if X.ndim != 2 or pool.ndim != 2 or hw.ndim != 2:
+        raise ValueError("X, pool and hyper_w must be two-dimensional")
+    n, d = X.shape
+    m, G, q = pool.shape[0], hw.shape[0], int(q)
+    if pool.shape[1] != d or hw.shape[1] != d or z.shape[0] != n or hn.shape[0] != G:
+        raise ValueError("shapes disagree: X [n][d], z [n], hyper_w [G][d], hyper_noise [G], pool [m][d]")
+    lml, mu, var = np.empty(max(G, 1)), np.empty(max(m, 1)), np.empty(max(m, 1))
+    status = np.zeros(max(G, 1), dtype=np.int32)
+    picks = np.full(max(q, 1), -1, dtype=np.int32)
+    pick_ei, pick_margin = np.empty(max(q, 1)), np.empty(max(q, 1))
+    chosen = np.full(1, -1, dtype=np.int32)
+    check(lib.ampc_bo_propose(int(device), n, d, dptr(X), dptr(z), G, dptr(hw), dptr(hn), m, dptr(pool), q, dptr(lml),
+                              iptr(status), iptr(chosen), iptr(picks), dptr(pick_ei), dptr(pick_margin), dptr(mu),
+                              dptr(var)))
+    return dict(lml=lml[:G], status=status[:G], chosen=int(chosen[0]), picks=picks[:q], pick_ei=pick_ei[:q],
+                pick_margin=pick_margin[:q], mu=mu[:m], var=var[:m])
 
 
 def stable_fit(traj_len, obs, ctrls, bases, tie=None, device=0):

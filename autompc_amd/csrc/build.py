@@ -1,8 +1,8 @@
 """Build libautompc_hip.so for gfx950 with hipcc (cross-compiles without a GPU).
 
-Thirty-six translation units compiled in parallel and linked into one shared library: api.cpp +
-api_{model,program,mppi,ilqr,lqr,linfit,sindyfit,lasso,stable,mlpfit,kstep_mlp}.cpp (the C ABI and host logic by family), launch_{mlp,mppi,ilqr,kstep,kstep_linear,kstep_sindy}.cpp
-once per precision (-DAMPC_T=double|float), launch_lqr.cpp, launch_linfit.cpp, launch_sindyfit.cpp, launch_sindyfit_wide.cpp, launch_lasso.cpp, launch_stable.cpp, launch_mlpfit.cpp, launch_kstep_mlp.cpp, launch_mppi_table.cpp, launch_ilqr_table.cpp, launch_ilqr_sindy_table.cpp and launch_ilqr_linear_table.cpp (f64 only).
+Thirty-eight translation units compiled in parallel and linked into one shared library: api.cpp +
+api_{model,program,mppi,ilqr,lqr,linfit,sindyfit,lasso,stable,mlpfit,kstep_mlp,bo}.cpp (the C ABI and host logic by family), launch_{mlp,mppi,ilqr,kstep,kstep_linear,kstep_sindy}.cpp
+once per precision (-DAMPC_T=double|float), launch_lqr.cpp, launch_linfit.cpp, launch_sindyfit.cpp, launch_sindyfit_wide.cpp, launch_lasso.cpp, launch_stable.cpp, launch_mlpfit.cpp, launch_kstep_mlp.cpp, launch_mppi_table.cpp, launch_ilqr_table.cpp, launch_ilqr_sindy_table.cpp, launch_ilqr_linear_table.cpp and launch_bo.cpp (f64 only).
 """
 import concurrent.futures
 import os
@@ -43,7 +43,9 @@ UNITS = [("api", "api.cpp", []), ("api_model", "api_model.cpp", []), ("api_progr
     ("mppi_table_double", "launch_mppi_table.cpp", ["-DAMPC_T=double", "-DAMPC_T_IS_F64=1"]),
     ("ilqr_table_double", "launch_ilqr_table.cpp", ["-DAMPC_T=double", "-DAMPC_T_IS_F64=1"]),
     ("ilqr_sindy_table_double", "launch_ilqr_sindy_table.cpp", ["-DAMPC_T=double", "-DAMPC_T_IS_F64=1"]),
-    ("ilqr_linear_table_double", "launch_ilqr_linear_table.cpp", ["-DAMPC_T=double", "-DAMPC_T_IS_F64=1"])]
+    ("ilqr_linear_table_double", "launch_ilqr_linear_table.cpp", ["-DAMPC_T=double", "-DAMPC_T_IS_F64=1"]),
+    ("api_bo", "api_bo.cpp", []),
+    ("bo_double", "launch_bo.cpp", ["-DAMPC_T=double", "-DAMPC_T_IS_F64=1"])]
 SOURCES = sorted({u[1] for u in UNITS})
 
 

@@ -6,8 +6,9 @@ into a ``PipelineTuneResult`` (:19-21, :273-313).  Here the search proposes cand
 batches (``ask``), a whole batch is evaluated at once -- sharded over the ranks of the default
 ``torch.distributed`` group, one GPU each -- and reported back (``tell``); the same
 ``PipelineTuneResult`` fields come out, filled in evaluation order.  The proposal rule is
-random search over the reference's configuration ranges (what SMAC's initial design is);
-any other proposer can drive ``ask``/``tell`` by passing ``sampler``.
+random search over the reference's configuration ranges (what SMAC's initial design is) unless a
+``proposer`` is given: ``tuning.proposer.GpProposer`` learns from every batch's scores (``tell`` hands
+them over) where the next batch should go.  ``sampler`` replaces the random draw and never sees a score.
 
 Both cost columns of the result are scores of the episode ``eval_cfg`` simulates --
 ``simulate(controller, init_obs, task.term_cond, max_steps=task.get_num_steps())`` after a
@@ -46,7 +47,7 @@ class BatchPipelineTuner:
     def __init__(self, system, evaluator, batch_size=64, sampler=None, truedyn_noise="device",
                  eval_kwargs=None, keep_trajs=False, balance=None, models=None, model_factory=None,
                  trajs=None, as_configs=False, linear_fit="host", sindy_fit="host", lasso_fit="host",
-                 stable_fit="host", mlp_fit="torch", sindy_wide_fit="host", truedyn_evaluator=None):
+                 stable_fit="host", mlp_fit="torch", sindy_wide_fit="host", truedyn_evaluator=None, proposer=None):
         """truedyn_noise: the noise mode of the controllers scored against the true dynamics
         (MPPI(noise=...): "device" Philox, or "numpy" / "numpy_device" = the reference's global
         legacy stream).  eval_kwargs: extra keyword arguments for every ``evaluator.evaluate`` call
@@ -96,7 +97,12 @@ class BatchPipelineTuner:
         candidates that carry a fitted ``model`` have it at hand; with ``keep_trajs`` the trajectories go to
         ``truedyn_trajs``.  ``run(truedyn=...)`` must not be given as well.  One difference from ``truedyn_score``:
         MPPI noise on this path is the evaluator's (seed, global evaluation index) stream, not a per-candidate seed
-        of a drop-in controller (``truedyn_noise`` does not apply)."""
+        of a drop-in controller (``truedyn_noise`` does not apply).
+
+        proposer: ``proposer(n, rng) -> n candidates`` with ``proposer.observe(candidates, scores)``
+        (``tuning.proposer.GpProposer``): ``ask`` draws from it and ``tell`` reports every batch's SURROGATE scores to
+        it (true-dynamics scores never steer the search, pipeline_tuner.py:181-184).  Not together with ``sampler``,
+        ``model_factory`` (conditional `_model:` sub-spaces) or an LQR evaluator."""
         self.system, self.evaluator = system, evaluator
         self.truedyn_evaluator = truedyn_evaluator
         self.truedyn_noise = truedyn_noise
@@ -149,7 +155,16 @@ class BatchPipelineTuner:
         self.batch_size = int(batch_size)
         if self.batch_size < 1:
             raise ValueError("batch_size must be >= 1")
-        self._sampler = sampler if sampler is not None else self._random_search
+        if proposer is not None:
+            if sampler is not None:
+                raise ValueError("proposer and sampler both propose the batch: pass one of them")
+            if model_factory is not None:
+                raise ValueError("a proposer searches given models only: conditional `_model:` sub-spaces "
+                                 "(model_factory) are not encoded")
+            if self._is_lqr():
+                raise ValueError("a proposer does not encode LQR candidates")
+        self.proposer = proposer
+        self._sampler = sampler if sampler is not None else (proposer if proposer is not None else self._random_search)
         self.reset()
 
     def reset(self):
@@ -279,6 +294,8 @@ class BatchPipelineTuner:
             raise ValueError("one score per candidate expected")
         if truedyn_scores is not None and len(truedyn_scores) != len(candidates):
             raise ValueError("one true-dynamics score per candidate expected")
+        if self.proposer is not None:
+            self.proposer.observe(candidates, scores)
         for i, (cfg, s) in enumerate(zip(candidates, scores)):
             s = float(s) if np.isfinite(s) else float("inf")
             td = None if truedyn_scores is None else float(truedyn_scores[i])

@@ -1016,6 +1016,28 @@ int ampc_lqr_closed_loop_scored(ampc_lqr_plan* p, ampc_handle* surrogate, const 
                                 const double* init_sim, int n_steps, int n_terms, const int* kinds,
                                 const double* params, double* scores, double* traj_obs, double* traj_ctrls);
 
+/* ---- Bayesian-optimisation proposal (f64) ------------------------------------------------------------------ */
+/* One proposal of a model-based tuner (autompc_amd/tuning/proposer.py states the algorithm), stateless: a zero-mean
+ * GP with the Matern-5/2 kernel k(a, b) = (1 + s + s^2 / 3) exp(-s), s = sqrt(5) |(a - b) o w|, of unit signal
+ * variance is fitted to the n observations X [n][d] (points of the unit cube), z [n] (targets) once per row (w [d],
+ * noise) of the hyperparameter table: K = k(X, X) + noise I = L L', L t = z, lml = -t't / 2 - sum log L_ii; a row whose
+ * factorisation meets a pivot that is not positive and finite is declined (hyper_status 1, lml -inf).  chosen: the
+ * accepted row of largest lml, lowest index on ties (-1: every row declined; picks are -1 and pick_ei, pick_margin, mu,
+ * var NaN then, and the call succeeds).  For the chosen row the posterior over pool [m][d]: V = L^-1 k(X, pool),
+ * mu = V't, var = max(1 - colsum V^2, 1e-12) (mu, var: before the first pick), expected improvement for minimisation
+ * against min z, and q greedy picks: the unpicked point of largest EI (lowest index on ties; a NaN EI counts as
+ * -inf), then the "believer" update c = k(pool, p_j) - V'V[:, j], row r = c / sqrt(max(c_j + noise, 1e-12)) appended
+ * to V, var = max(var - r^2, 1e-12), the mean kept, EI recomputed.  pick_ei [q]: the pick's EI; pick_margin [q]:
+ * (EI_best - EI_second) / EI_best over the unpicked points (second taken as 0 when the pick was the last unpicked
+ * point; 0 when EI_best <= 0).
+ * Refused before any launch: n outside 1..2048, d outside 1..64, n_hyper outside 1..64, m outside 1..65536, q outside
+ * 1..min(m, 256).  Deterministic (fixed-order sums, no atomics): the same inputs give the same bits.  Synchronises. */
+int ampc_bo_propose(int device, int n, int d, const double* X, const double* z, int n_hyper,
+                    const double* hyper_w /*[n_hyper][d]*/, const double* hyper_noise /*[n_hyper]*/, int m,
+                    const double* pool, int q, double* lml /*[n_hyper]*/, int* hyper_status /*[n_hyper]*/,
+                    int* chosen, int* picks /*[q]*/, double* pick_ei, double* pick_margin, double* mu /*[m]*/,
+                    double* var /*[m]*/);
+
 #ifdef __cplusplus
 }
 #endif
